@@ -3,7 +3,7 @@
 tag=${1:-cfg}
 repo="$(cd "$(dirname "$0")/.." && pwd)"; mkdir -p "$repo/gpurun_out"; out="$repo/gpurun_out/${tag}_configs.jsonl"; : > "$out"
 cd "$repo"
-run() { timeout 300 python bench.py --cpu-sample 0 --spmv-large-mult 0 "$@" 2>/dev/null | tail -1 >> "$out"; }
+run() { timeout 300 python bench.py --full --cpu-sample 0 --spmv-large-mult 0 "$@" 2>/dev/null | tail -1 >> "$out"; }
 run --workload nuclear_24h --batch 256
 run --workload nuclear_24h
 run --workload wind_pem_48h

@@ -6,9 +6,9 @@ repo="$(cd "$(dirname "$0")/.." && pwd)"; out="$repo/gpurun_out"; mkdir -p "$out
 export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > "$out/${tag}_smoke.log" 2>&1; tail -2 "$out/${tag}_smoke.log"
 timeout 1500 python -m pytest tests -m gpu -q --timeout 900 > "$out/${tag}_tests.log" 2>&1; tail -4 "$out/${tag}_tests.log"
-python bench.py > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"; tail -c 300 "$out/${tag}_bench.json"; echo
+python bench.py --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"; tail -c 300 "$out/${tag}_bench.json"; echo
 # same-round kernel trace of the default line's kernels (pdlp_solve_kernel, spmv_step_kernel; without the configs array and the CPU leg)
-( cd /tmp; rm -rf /tmp/trz; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/trz -- python $repo/bench.py --cpu-sample 0 --no-configs > /dev/null 2>&1
+( cd /tmp; rm -rf /tmp/trz; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/trz -- python $repo/bench.py --full --cpu-sample 0 --no-configs > /dev/null 2>&1
   f=$(find /tmp/trz -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$out/${tag}_kernel_stats.csv" && head -6 "$f" | cut -c1-200 )
 timeout 200 python tools/gpu_bidder_profile.py > "$out/${tag}_bidder_profile.log" 2>&1; head -30 "$out/${tag}_bidder_profile.log" | tail -22
 {

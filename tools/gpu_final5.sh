@@ -7,7 +7,7 @@ repo="$(cd "$(dirname "$0")/.." && pwd)"; out="$repo/gpurun_out"; mkdir -p "$out
 export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" > "$out/${tag}_smoke.log" 2>&1; tail -2 "$out/${tag}_smoke.log"
 timeout 900 python -m pytest tests -m gpu -q --timeout 600 > "$out/${tag}_tests.log" 2>&1; tail -4 "$out/${tag}_tests.log"
-python bench.py > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"; tail -c 300 "$out/${tag}_bench.json"; echo
-( cd /tmp; rm -rf /tmp/trz; timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/trz -- python $repo/bench.py --cpu-sample 0 --no-configs > /dev/null 2>&1
+python bench.py --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"; tail -c 300 "$out/${tag}_bench.json"; echo
+( cd /tmp; rm -rf /tmp/trz; timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/trz -- python $repo/bench.py --full --cpu-sample 0 --no-configs > /dev/null 2>&1
   f=$(find /tmp/trz -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$out/${tag}_kernel_stats.csv" && head -6 "$f" | cut -c1-200 )
 bash tools/gpu_ipm_par.sh $tag " " | tail -12 | cut -c1-220

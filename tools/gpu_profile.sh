@@ -10,8 +10,8 @@ wl=${2:-}
 repo="$(cd "$(dirname "$0")/.." && pwd)"
 out="$repo/gpurun_out"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-bench="python $repo/bench.py"
-[ -n "$wl" ] && bench="python $repo/bench.py --workload $wl --no-spmv"
+bench="python $repo/bench.py --full"
+[ -n "$wl" ] && bench="python $repo/bench.py --full --workload $wl --no-spmv"
 $bench > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 tail -c 600 "$out/${tag}_bench.json"; echo
 rm -rf /tmp/prof_trace; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_trace -- $bench --cpu-sample 0 --no-configs > /dev/null 2>&1

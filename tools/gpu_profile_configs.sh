@@ -9,7 +9,7 @@ export TMPDIR=/tmp; cd /tmp
 configs="wind_battery_24h:4096 wind_pem_48h:4096 nuclear_24h:256 nuclear_24h:4096 wind_battery_48h:4096"
 for cfg in $configs; do
   wl=${cfg%%:*}; B=${cfg##*:}
-  bench="python $repo/bench.py --workload $wl --batch $B --cpu-sample 0 --no-spmv --no-eps4 --no-configs"
+  bench="python $repo/bench.py --full --workload $wl --batch $B --cpu-sample 0 --no-spmv --no-eps4 --no-configs"
   i=0
   for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAVES"; do
     i=$((i+1)); rm -rf /tmp/pc_$i
@@ -42,12 +42,12 @@ PY
   cp "$out/${tag}_${wl}_B${B}_pmc_summary.csv" "$out/${tag}_${wl}_B${B}_pmc_iterations.json" "$repo/profiles/" 2>/dev/null
 done
 # the lines themselves (same box, same build): headline with its CPU leg, SpMV figures and the eps = 1e-4 entry; the others GPU only
-python $repo/bench.py > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"; tail -c 400 "$out/${tag}_bench.json"; echo
+python $repo/bench.py --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"; tail -c 400 "$out/${tag}_bench.json"; echo
 rm -f "$out/${tag}_configs.jsonl"
 for cfg in $configs; do
   wl=${cfg%%:*}; B=${cfg##*:}
   [ "$cfg" = "wind_battery_24h:4096" ] && continue
-  timeout 200 python $repo/bench.py --workload $wl --batch $B --cpu-sample 0 --no-spmv --no-configs 2>/dev/null | tail -1 >> "$out/${tag}_configs.jsonl"
+  timeout 200 python $repo/bench.py --full --workload $wl --batch $B --cpu-sample 0 --no-spmv --no-configs 2>/dev/null | tail -1 >> "$out/${tag}_configs.jsonl"
 done
 python - "$out/${tag}_configs.jsonl" <<'PY'
 import json, sys

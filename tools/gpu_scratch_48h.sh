@@ -6,7 +6,7 @@ tag=${1:-r62b}
 repo="$(cd "$(dirname "$0")/.." && pwd)"; out="$repo/gpurun_out"; mkdir -p "$out"
 export TMPDIR=/tmp; cd /tmp
 rocprofv3 -L 2>/dev/null | grep -o "TCC_HIT_sum\|TCC_MISS_sum\|TCC_EA0_RDREQ_sum\|TCC_EA0_WRREQ_sum\|SQ_INSTS_VMEM_RD\|SQ_INSTS_VMEM_WR\|SQ_INSTS_FLAT\|SQ_INST_CYCLES_VMEM\|SQ_WAIT_INST_ANY\|SQ_ACTIVE_INST_ANY\|SQ_ACTIVE_INST_VMEM\|SQ_ACTIVE_INST_FLAT\|TCP_TCC_READ_REQ_sum\|TCP_TCC_WRITE_REQ_sum\|TCC_REQ_sum\|TCC_READ_sum\|TCC_WRITE_sum\|SQ_INSTS_VALU\|SQ_INSTS_LDS\|SQ_INSTS_SALU" | sort -u | tr '\n' ' ' > "$out/${tag}_available_counters.txt"; cat "$out/${tag}_available_counters.txt"; echo
-bench="python $repo/bench.py --workload wind_battery_48h --batch 4096 --cpu-sample 0 --no-spmv --no-eps4 --no-configs --steps 8 --warmup 1 --streams 8 --min-time 0"
+bench="python $repo/bench.py --full --workload wind_battery_48h --batch 4096 --cpu-sample 0 --no-spmv --no-eps4 --no-configs --steps 8 --warmup 1 --streams 8 --min-time 0"
 i=0
 for set in "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_VALU SQ_INSTS_LDS" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1)); rm -rf /tmp/ps_$i
@@ -31,6 +31,6 @@ print("wave cycles %.4g: parked (WAIT_ANY) %.3f, issue-stalled (WAIT_INST_ANY) %
     g("SQ_WAVE_CYCLES"), g("SQ_WAIT_ANY") / g("SQ_WAVE_CYCLES"), g("SQ_WAIT_INST_ANY") / g("SQ_WAVE_CYCLES"), g("SQ_ACTIVE_INST_ANY") / g("SQ_WAVE_CYCLES"),
     g("SQ_ACTIVE_INST_VMEM") / g("SQ_WAVE_CYCLES"), g("SQ_ACTIVE_INST_LDS") / g("SQ_WAVE_CYCLES"), g("SQ_ACTIVE_INST_VALU") / g("SQ_WAVE_CYCLES")))
 PY
-timeout 200 python $repo/bench.py --workload wind_battery_48h --batch 4096 --cpu-sample 0 --no-spmv --no-configs 2>/dev/null | tail -1 > "$out/${tag}_48h_line.json"
+timeout 200 python $repo/bench.py --full --workload wind_battery_48h --batch 4096 --cpu-sample 0 --no-spmv --no-configs 2>/dev/null | tail -1 > "$out/${tag}_48h_line.json"
 python -c "
 import json; d=json.load(open('$out/${tag}_48h_line.json')); print('line:', d['value'], d['ms_per_step'], d['config'].get('single_batch_latency_ms'))"
