@@ -23,33 +23,10 @@
 #include <cstdint>
 
 #include "../../include/dsp_hip.h"
+#include "dsp_bid_cents.hpp"
 #include "dsp_device.hpp"
 
 namespace dsp {
-
-constexpr long long kBidDrop = 0x7fffffffffffffffll;        // key of a pair that takes no part: sorts behind every real key
-constexpr long long kBidOff = 1ll << 31;
-
-// round(a, 2) * 100 as an integer, for finite |a| < 2e7 (anything else: 0, and the caller drops the pair).
-__device__ __forceinline__ long long bid_cents(double a) {
-#pragma clang fp contract(off)
-  const double p = a * 200.0;                      // rounded product
-  const double c = a * 134217729.0;                // Veltkamp split (2^27 + 1)
-  const double hi = c - (c - a);
-  const double lo = a - hi;
-  const double err = (hi * 200.0 - p) + lo * 200.0;   // exact: a * 200 = p + err
-  double r = floor(a * 100.0);                     // the exact floor is r or r +- 1
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    if (((p - 2.0 * r) + err) < 0.0) r -= 1.0;
-    if (((p - (2.0 * r + 2.0)) + err) >= 0.0) r += 1.0;
-  }
-  const double d = (p - (2.0 * r + 1.0)) + err;    // sign of a * 100 - (r + 1/2), exact
-  const bool odd = fmod(r, 2.0) != 0.0;
-  if (d > 0.0 || (d == 0.0 && odd)) r += 1.0;      // above the midpoint, or on it with an odd floor: ties to even
-  const bool ok = (fabs(a) < 2.0e7);               // false for NaN / inf too
-  return ok ? (long long)r : 0ll;
-}
 
 __global__ __launch_bounds__(1024) void bid_points_kernel(dsp_bid_request rq, int N) {
 #pragma clang fp contract(off)
@@ -68,7 +45,7 @@ __global__ __launch_bounds__(1024) void bid_points_kernel(dsp_bid_request rq, in
       const double price = rq.price[(size_t)s * rq.ldp + t];
       const long long pc = bid_cents(power), cc = bid_cents(price);
       const bool keep = ((double)pc / 100.0 >= rq.p_min) && fabs(power) < INFINITY && fabs(price) < INFINITY;
-      if (keep) key = pc * 4294967296ll + ((kBidOff - 1) - cc);      // low half in [0, 2^32): price descending inside a power
+      if (keep) key = bid_key(pc, cc);
     }
     keys[s] = key;
   }

@@ -359,6 +359,47 @@ int dsp_bid_points(const dsp_bid_request *rq, void *hipStream) {
   return DSP_OK;
 }
 
+// arguments of the stochastic mode's entry points, checked on the host: nothing is launched on a bad descriptor
+static bool market_state_ok(const dsp_market_state *st) {
+  if (!st || st->B < 0 || st->N < 1 || st->S < 1 || st->S > DSP_MARKET_MAX_S) return false;
+  if (st->backcast ? (st->D < 1 || st->S > st->D || 24ll * st->D > st->N) : st->S != 1) return false;
+  return st->start && st->hour && st->da_series && st->rt_series;
+}
+static bool market_col_ok(int32_t col, int32_t n) { return col >= 0 && col < n; }
+
+int dsp_market_prepare(const dsp_market_state *st, const dsp_market_model *m, int32_t k, void *hipStream) {
+  if (!market_state_ok(st) || !m || k < -1 || k > 23 || m->n < 1 || m->T < 1 || m->T > DSP_MARKET_MAX_T) return DSP_ERR_INVALID;
+  if (!st->cf_series || !st->soc || !st->thr || !m->c || !m->lb || !m->ub || !m->base_c) return DSP_ERR_INVALID;
+  if (k >= 0 && (!st->da_offer || !st->da_prices)) return DSP_ERR_INVALID;
+  if (!market_col_ok(m->soc_init, m->n) || !market_col_ok(m->thr_init, m->n)) return DSP_ERR_INVALID;
+  for (int t = 0; t < m->T; ++t)
+    if (!market_col_ok(m->wind_cols[t], m->n) || !market_col_ok(m->pt_cols[t][0], m->n) || !market_col_ok(m->pt_cols[t][1], m->n) ||
+        !market_col_ok(m->pda_cols[t], m->n))
+      return DSP_ERR_INVALID;
+  if (st->B == 0) return DSP_OK;
+  HIP_TRY(launch_market_prepare(*st, *m, (int)k, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
+int dsp_market_clear(const dsp_market_state *st, const dsp_market_model *m, const dsp_wb_model *tr, int32_t k, int32_t T,
+                     double *dispatch, int32_t *curve, int32_t *count, void *hipStream) {
+  if (!market_state_ok(st) || !m || k < -1 || k > 23 || m->n < 1 || m->T < 1 || m->T > DSP_MARKET_MAX_T || T < 1 || T > m->T) return DSP_ERR_INVALID;
+  if (!m->x || !m->status || !dispatch || !curve || !count) return DSP_ERR_INVALID;
+  if (k < 0 ? (T > 24 || !st->da_prices || tr) : T > 8) return DSP_ERR_INVALID;
+  for (int t = 0; t < T; ++t)
+    if (k < 0 ? !market_col_ok(m->pda_cols[t], m->n) : (!market_col_ok(m->pt_cols[t][0], m->n) || !market_col_ok(m->pt_cols[t][1], m->n)))
+      return DSP_ERR_INVALID;
+  if (tr) {
+    if (tr->T != T || tr->n < 1 || tr->m < 1 || !tr->lb || !tr->ub || !tr->rlo || !tr->rhi || !st->cf_series || !st->soc || !st->thr) return DSP_ERR_INVALID;
+    if (!market_col_ok(tr->soc_init, tr->n) || !market_col_ok(tr->thr_init, tr->n)) return DSP_ERR_INVALID;
+    for (int t = 0; t < T; ++t)
+      if (!market_col_ok(tr->wind_cols[t], tr->n) || !market_col_ok(tr->track_rows[t], tr->m)) return DSP_ERR_INVALID;
+  }
+  if (st->B == 0) return DSP_OK;
+  HIP_TRY(launch_market_clear(*st, *m, tr, (int)k, (int)T, dispatch, curve, count, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
 void dsp_default_options(dsp_options *o) {
   if (!o) return;
   std::memset(o, 0, sizeof(*o));

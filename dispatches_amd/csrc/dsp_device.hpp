@@ -170,6 +170,10 @@ hipError_t launch_solve_f32(int cpl, int rpl, const SolveArgs &a, int num_cus, s
                             int *threads, size_t *lds);
 // bid-curve points of a solved batch (dsp_bids.hip)
 hipError_t launch_bid_points(const dsp_bid_request &rq, hipStream_t st);
+// stochastic mode of the wind + battery double loop (dsp_market.hip): scenario fan-out, curve + clearing
+hipError_t launch_market_prepare(const dsp_market_state &st, const dsp_market_model &m, int k, hipStream_t stream);
+hipError_t launch_market_clear(const dsp_market_state &st, const dsp_market_model &m, const dsp_wb_model *tr, int k, int T, double *dispatch,
+                               int32_t *curve, int32_t *count, hipStream_t stream);
 hipError_t launch_spmv(int cpl, int rpl, const SpmvArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t st);
 
 #endif

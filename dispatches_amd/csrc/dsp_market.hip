@@ -1,0 +1,198 @@
+// dsp_market.hip — the stochastic mode of the wind + battery double loop on the device, gfx950 only (include/dsp_hip.h: dsp_market_*).
+//
+// Reference behaviour (run_double_loop_battery.py:81-105, 230-250): a Backcaster hands the Bidder n_scenario price scenarios taken
+// from the last days' realised prices, the Bidder solves one LP per scenario and assembles a (power, marginal price) curve per hour
+// (idaes Bidder._assemble_bids), the market dispatches the plant along that curve at the price that occurs.  Here for B plants at
+// once; the S rows of plant b are rows b * S + i of the bidding LPs' batches.
+//
+//   market_prepare_kernel   scenario fan-out, one lane per row: objective entries, day-ahead power bounds, wind availability, realised
+//                           state and objective constant of the row, prices gathered by the Backcaster's index rule (no stored
+//                           history: in the price-taker setting the realised prices ARE the series).
+//   market_clear_kernel     curve + clearing, one lane per (plant, period): the <= 16 composite keys of the lane (dsp_bid_cents.hpp)
+//                           sit in registers and are sorted by a fully unrolled bitonic compare-exchange network (static register
+//                           indices only: no LDS, no scratch - 0 bytes of scratch for every instantiation, checked with
+//                           -Rpass-analysis=kernel-resource-usage); duplicates, the zero-power point and the running maximum are one
+//                           pass over the sorted registers, which also clears the curve at the price that occurs.
+//
+// Every product is made opaque before it is added (as in wb_rolling_kernel, dsp_capi.hip): the results are bit-identical to the
+// tensor operations of dispatches_amd/rolling.py (use_fused=False), which is how the kernels are tested.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/dsp_hip.h"
+#include "dsp_bid_cents.hpp"
+#include "dsp_device.hpp"
+
+namespace dsp {
+
+__device__ __forceinline__ double mk_opaque(double v) { asm volatile("" : "+v"(v)); return v; }
+
+// index into the circular series of the price scenario i of plant (start st0) asked at hour-of-day hod for period t (clock h)
+__device__ __forceinline__ long long mk_index(const dsp_market_state &s, long long st0, long long h, int i, int hod, int t) {
+  if (!s.backcast) return (st0 + h + t) % s.N;
+  const long long D = s.D, d = h / 24;
+  const long long pos = (24 * (D - 1 - i) + hod + t) % (24 * D);
+  long long v = (st0 + 24 * (d - D) + pos) % s.N;
+  return v < 0 ? v + s.N : v;
+}
+
+__global__ void __launch_bounds__(256) market_prepare_kernel(dsp_market_state s, dsp_market_model m, int k) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= s.B * s.S) return;
+  const int b = r / s.S, i = r - b * s.S;
+  const long long h = *s.hour, st0 = s.start[b];
+  const int hod = k < 0 ? 0 : k;
+  const int known = k < 0 ? 0 : min(m.T, 24 - k);
+  double *c = m.c + (size_t)r * m.n, *lb = m.lb + (size_t)r * m.n, *ub = m.ub + (size_t)r * m.n;
+  double avail_sum = 0.0;
+  for (int t = 0; t < m.T; ++t) {
+    const double rtp = s.rt_series[mk_index(s, st0, h, i, hod, t)];
+    const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : s.da_series[mk_index(s, st0, h, i, hod, t)];
+    const double r3 = mk_opaque(__dmul_rn(1e-3, rtp));
+    c[m.pt_cols[t][0]] = __dsub_rn(m.base_c[m.pt_cols[t][0]], r3);
+    c[m.pt_cols[t][1]] = __dsub_rn(m.base_c[m.pt_cols[t][1]], r3);
+    c[m.pda_cols[t]] = __dsub_rn(m.base_c[m.pda_cols[t]], mk_opaque(__dsub_rn(dap, rtp)));
+    const double avail = mk_opaque(__dmul_rn(m.wind_kw, s.cf_series[(st0 + h + t) % s.N]));      // capacity factors: the realised window
+    ub[m.wind_cols[t]] = avail;
+    avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
+    const double fix = t < known ? s.da_offer[(size_t)b * 24 + k + t] : 0.0;
+    lb[m.pda_cols[t]] = fix;
+    ub[m.pda_cols[t]] = t < known ? fix : INFINITY;
+  }
+  if (m.c0) m.c0[r] = __dadd_rn(m.c0_base, mk_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
+  const double soc = s.soc[b], thr = s.thr[b];
+  lb[m.soc_init] = soc; ub[m.soc_init] = soc;
+  lb[m.thr_init] = thr; ub[m.thr_init] = thr;
+}
+
+template <int SP>
+__global__ void __launch_bounds__(256) market_clear_kernel(dsp_market_state s, dsp_market_model m, dsp_wb_model tr, int has_tr, int k, int T,
+                                                           double *dispatch, int32_t *curve, int32_t *count) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= s.B * T) return;
+  const int b = g / T, t = g - b * T;
+  const int S = s.S;
+  const long long h = *s.hour, st0 = s.start[b];
+  const int hod = k < 0 ? 0 : k;
+  const double *series = k < 0 ? s.da_series : s.rt_series;
+  const int ca = k < 0 ? m.pda_cols[t] : m.pt_cols[t][0], cb = m.pt_cols[t][1];
+  // ---- the S pairs of this plant and period as sort keys, in registers ----
+  long long keys[SP];
+  bool any_bad = false;
+#pragma unroll
+  for (int i = 0; i < SP; ++i) {
+    long long key = kBidDrop;
+    if (i < S) {
+      const size_t row = (size_t)b * S + i;
+      if (m.status[row] == 0) {
+        const double *x = m.x + row * m.n;
+        const double power = k < 0 ? x[ca] : __dmul_rn(1e-3, mk_opaque(__dadd_rn(x[ca], x[cb])));
+        const double price = series[mk_index(s, st0, h, i, hod, t)];
+        const long long pc = bid_cents(power), cc = bid_cents(price);
+        if (pc >= 0 && fabs(power) < INFINITY && fabs(price) < INFINITY) key = bid_key(pc, cc);
+      } else {
+        any_bad = true;
+      }
+      if (t == 0 && m.flags && s.uncertified && (m.flags[row] & DSP_FLAG_OBJ_WAIVED))
+        atomicAdd(reinterpret_cast<unsigned long long *>(s.uncertified), 1ull);
+    }
+    keys[i] = key;
+  }
+  if (any_bad && s.bad) *s.bad = 1;
+  // ---- bitonic network, ascending (every index a compile-time constant after unrolling) ----
+#pragma unroll
+  for (int kk = 2; kk <= SP; kk <<= 1) {
+#pragma unroll
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+#pragma unroll
+      for (int i = 0; i < SP; ++i) {
+        const int l = i ^ j;
+        if (l > i) {
+          const long long a = keys[i], c = keys[l];
+          const bool swap = (a > c) == ((i & kk) == 0);
+          keys[i] = swap ? c : a;
+          keys[l] = swap ? a : c;
+        }
+      }
+    }
+  }
+  // ---- the price that occurs: realised for the day-ahead market and for the hour at hand, scenario 0's for the look-ahead hours ----
+  const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[mk_index(s, st0, h, 0, hod, t)];
+  // ---- lowest price among the distinct points (the inserted zero-power point takes it) ----
+  const bool has0 = keys[0] != kBidDrop && bid_key_power(keys[0]) == 0;      // powers are >= 0 and ascending
+  long long lowest = 0x7fffffffffffffffll;
+  int n = 0;
+#pragma unroll
+  for (int i = 0; i < SP; ++i) {
+    const bool first = keys[i] != kBidDrop && (i == 0 || bid_key_power(keys[i]) != bid_key_power(keys[i ? i - 1 : 0]));
+    if (first) { lowest = min(lowest, bid_key_price(keys[i])); ++n; }
+  }
+  // ---- distinct points in order with the running maximum, cleared on the way ----
+  int32_t *out = curve + (size_t)g * (S + 1) * 2;
+  int pos = 0;
+  long long run = 0, cleared = 0;
+  auto emit = [&](long long U, long long M) {
+    run = pos == 0 ? M : max(run, M);
+    out[2 * pos] = (int32_t)U;
+    out[2 * pos + 1] = (int32_t)run;
+    if (pos == 0 || !s.price_taker || __ddiv_rn((double)run, 100.0) <= lmp) cleared = U;
+    ++pos;
+  };
+  if (!has0) emit(0, n == 0 ? 0 : lowest);
+#pragma unroll
+  for (int i = 0; i < SP; ++i) {
+    const bool first = keys[i] != kBidDrop && (i == 0 || bid_key_power(keys[i]) != bid_key_power(keys[i ? i - 1 : 0]));
+    if (first) emit(bid_key_power(keys[i]), bid_key_price(keys[i]));
+  }
+  count[g] = pos;
+  for (int q = pos; q <= S; ++q) { out[2 * q] = 0; out[2 * q + 1] = 0; }
+  const double disp = __ddiv_rn((double)cleared, 100.0);
+  dispatch[g] = disp;
+  if (k < 0) {
+    s.da_prices[(size_t)b * 24 + t] = lmp;
+    return;
+  }
+  if (!has_tr) return;
+  // ---- the tracker's LP of this hour (what phase 1 of dsp_wb_rolling_update writes, with the cleared dispatch) ----
+  double *rlo = tr.rlo + (size_t)b * tr.m, *rhi = tr.rhi + (size_t)b * tr.m;
+  rlo[tr.track_rows[t]] = disp;
+  rhi[tr.track_rows[t]] = disp;
+  if (t == 0) {
+    double *lb = tr.lb + (size_t)b * tr.n, *ub = tr.ub + (size_t)b * tr.n;
+    double avail_sum = 0.0;
+    for (int q = 0; q < tr.T; ++q) {
+      const double avail = mk_opaque(__dmul_rn(tr.wind_kw, s.cf_series[(st0 + h + q) % s.N]));
+      ub[tr.wind_cols[q]] = avail;
+      avail_sum = q ? __dadd_rn(avail_sum, avail) : avail;
+    }
+    if (tr.c0) tr.c0[b] = __dadd_rn(tr.c0_base, mk_opaque(__dmul_rn(tr.waste_per_kw, avail_sum)));
+    const double soc = s.soc[b], thr = s.thr[b];
+    lb[tr.soc_init] = soc; ub[tr.soc_init] = soc;
+    lb[tr.thr_init] = thr; ub[tr.thr_init] = thr;
+  }
+}
+
+hipError_t launch_market_prepare(const dsp_market_state &st, const dsp_market_model &m, int k, hipStream_t stream) {
+  const long long rows = (long long)st.B * st.S;
+  hipLaunchKernelGGL(market_prepare_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, st, m, k);
+  return hipGetLastError();
+}
+
+hipError_t launch_market_clear(const dsp_market_state &st, const dsp_market_model &m, const dsp_wb_model *tr, int k, int T, double *dispatch,
+                               int32_t *curve, int32_t *count, hipStream_t stream) {
+  const long long lanes = (long long)st.B * T;
+  const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+  const dsp_wb_model trv = tr ? *tr : dsp_wb_model{};
+  const int has_tr = tr != nullptr;
+#define DSP_MK_LAUNCH(SP) hipLaunchKernelGGL(market_clear_kernel<SP>, grid, block, 0, stream, st, m, trv, has_tr, k, T, dispatch, curve, count)
+  if (st.S <= 1) DSP_MK_LAUNCH(1);
+  else if (st.S <= 2) DSP_MK_LAUNCH(2);
+  else if (st.S <= 4) DSP_MK_LAUNCH(4);
+  else if (st.S <= 8) DSP_MK_LAUNCH(8);
+  else DSP_MK_LAUNCH(16);
+#undef DSP_MK_LAUNCH
+  return hipGetLastError();
+}
+
+}  // namespace dsp

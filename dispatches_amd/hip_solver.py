@@ -107,10 +107,11 @@ class DspLoopState(C.Structure):
 
 EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_step", "dsp_get_dims",
                     "dsp_get_scaling", "dsp_destroy", "dsp_strerror", "dsp_last_hip_error", "dsp_version",
-                    "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash")
+                    "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
+                    "dsp_market_prepare", "dsp_market_clear")
 
 
-ABI_VERSION = 12         # DSP_VERSION of the include/dsp_hip.h these structures mirror
+ABI_VERSION = 13         # DSP_VERSION of the include/dsp_hip.h these structures mirror
 
 
 BID_MAX_HOURS, BID_MAX_SCENARIOS = 64, 16384
@@ -121,6 +122,27 @@ class DspBidRequest(C.Structure):
     _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("ldx", C.c_int32), ("ldp", C.c_int32), ("terms", C.c_int32), ("reserved", C.c_int32),
                 ("x", C.c_void_p), ("price", C.c_void_p), ("ok", C.c_void_p), ("out", C.c_void_p), ("p_min", C.c_double),
                 ("col", (C.c_int32 * 2) * BID_MAX_HOURS), ("val", (C.c_double * 2) * BID_MAX_HOURS), ("constant", C.c_double * BID_MAX_HOURS)]
+
+
+MARKET_MAX_T, MARKET_MAX_S = 48, 16
+
+
+class DspMarketModel(C.Structure):
+    """include/dsp_hip.h: dsp_market_model (ABI 13) - a bidding LP of the stochastic double loop, B * S rows"""
+    _fields_ = [("c", C.c_void_p), ("lb", C.c_void_p), ("ub", C.c_void_p), ("base_c", C.c_void_p), ("x", C.c_void_p), ("c0", C.c_void_p),
+                ("status", C.c_void_p), ("flags", C.c_void_p),
+                ("n", C.c_int32), ("T", C.c_int32), ("soc_init", C.c_int32), ("thr_init", C.c_int32),
+                ("wind_cols", C.c_int32 * MARKET_MAX_T), ("pt_cols", (C.c_int32 * 2) * MARKET_MAX_T), ("pda_cols", C.c_int32 * MARKET_MAX_T),
+                ("wind_kw", C.c_double), ("c0_base", C.c_double), ("waste_per_kw", C.c_double)]
+
+
+class DspMarketState(C.Structure):
+    """include/dsp_hip.h: dsp_market_state (ABI 13)"""
+    _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("D", C.c_int32), ("N", C.c_int32), ("backcast", C.c_int32), ("price_taker", C.c_int32),
+                ("start", C.c_void_p), ("hour", C.c_void_p),
+                ("da_series", C.c_void_p), ("rt_series", C.c_void_p), ("cf_series", C.c_void_p),
+                ("soc", C.c_void_p), ("thr", C.c_void_p), ("da_offer", C.c_void_p), ("da_prices", C.c_void_p),
+                ("bad", C.c_void_p), ("uncertified", C.c_void_p)]
 
 
 def source_hash(root: Optional[str] = None) -> Optional[str]:
@@ -202,6 +224,10 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_update.restype = C.c_int
     lib.dsp_bid_points.argtypes = [C.POINTER(DspBidRequest), vp]
     lib.dsp_bid_points.restype = C.c_int
+    lib.dsp_market_prepare.argtypes = [C.POINTER(DspMarketState), C.POINTER(DspMarketModel), i32, vp]
+    lib.dsp_market_prepare.restype = C.c_int
+    lib.dsp_market_clear.argtypes = [C.POINTER(DspMarketState), C.POINTER(DspMarketModel), C.POINTER(DspWbModel), i32, i32, vp, vp, vp, vp]
+    lib.dsp_market_clear.restype = C.c_int
     lib.dsp_last_hip_error.restype = C.c_int
     if path == _LIB_PATH:
         _lib = lib

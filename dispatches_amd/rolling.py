@@ -26,6 +26,13 @@ Scenario k is the plant seen through the price / capacity-factor year that start
 RTS-GMLC series (the BASELINE config-4 windows of SURVEY.md 8(d)).  Shards are contiguous scenario ranges: one rank
 per GPU runs its shard with no communication and the per-scenario annual results are all-gathered once at the end
 (dispatches_amd.distributed.gather_device_results).
+
+Stochastic mode (n_price_scenarios / forecaster="backcast" / market="price_taker"; run_double_loop_battery.py:81-105, 230-250): the
+bidder does not know the prices.  Every plant bids on S scenarios a Backcaster takes from the last days' realised prices (rows b * S + i
+of ONE batch of B * S bidding LPs), the S solutions of a period become one (power, marginal price) curve as Bidder._assemble_bids builds
+it, and the market dispatches the plant along that curve at the price that occurs (workflow/market.py).  The methods `_forecast`,
+`_day_ahead_step_stochastic` and `_hour_step_stochastic` are its executable specification as tensor operations; csrc/dsp_market.hip is
+the same arithmetic in two kernels, bit for bit.  With the default arguments none of it runs.
 """
 from __future__ import annotations
 
@@ -133,6 +140,21 @@ class _DeviceModel:
         w.status, w.flags = self.out["status"].data_ptr(), self.out["flags"].data_ptr()       # (folded into the loop's flags by the next phase)
         return w
 
+    def market_struct(self):
+        """dsp_market_model of this bidding LP (include/dsp_hip.h) for the stochastic mode's kernels: B * S rows, any horizon <= 48"""
+        from .hip_solver import DspMarketModel
+        w = DspMarketModel()
+        w.c, w.lb, w.ub, w.base_c, w.x = (t.data_ptr() for t in (self.c, self.lb, self.ub, self.base_c, self.out["x"]))
+        w.c0 = self.c0.data_ptr()
+        w.status, w.flags = self.out["status"].data_ptr(), self.out["flags"].data_ptr()
+        w.n, w.T, w.soc_init, w.thr_init = self.lp.n, self.T, self.soc_init, self.thr_init
+        wc, pt, pda = self.wind_cols.cpu().tolist(), self.pt_cols.cpu().tolist(), self.pda_cols.cpu().tolist()
+        for t in range(self.T):
+            w.wind_cols[t], w.pda_cols[t] = wc[t], pda[t]
+            w.pt_cols[t][0], w.pt_cols[t][1] = pt[t]
+        w.wind_kw, w.c0_base, w.waste_per_kw = self.wind_kw, self._c0_base, self._waste_per_kw
+        return w
+
     def power_output(self, x):
         return 1e-3 * x[:, self.pt_cols].sum(dim=2)                                            # [B, T] MW
 
@@ -148,7 +170,8 @@ class _DeviceModel:
 class BatchedWindBatteryDoubleLoop:
     def __init__(self, n_scenarios, device=0, first_scenario=0, series="rts_gmlc_309.npz", stride=17,
                  day_ahead_horizon=48, real_time_horizon=4, tracking_horizon=4, wind_mw=200.0, batt_mw=25.0,
-                 price_cap=500.0, warm_start=True, lp_backend=None, use_graphs=True, use_fused=True, record=None, simplex_warm=True, warm_patience=10000):
+                 price_cap=500.0, warm_start=True, lp_backend=None, use_graphs=True, use_fused=True, record=None, simplex_warm=True, warm_patience=10000,
+                 n_price_scenarios=1, forecaster="perfect", max_historical_days=10, market="stub"):
         """lp_backend: None = the HIP solver on GPU `device`; tests pass a factory lp -> object with DeviceLP.solve's
         signature working on CPU tensors (tests/_highs_solver.py::HighsTensorLP), which runs the SAME window / objective /
         state-hand-off logic without a GPU.
@@ -162,13 +185,34 @@ class BatchedWindBatteryDoubleLoop:
         record: (plants, days) - keep, for these plants of the batch (local indices) and up to `days` simulated days, the state every
         LP was built from and its whole solution, hour by hour, in device buffers (what the reference's record_results keeps per hour,
         wind_battery_double_loop.py:276-340): `recorded()` returns them.  The writes are indexed by the device clock, so they are part
-        of the captured day like everything else."""
+        of the captured day like everything else.
+        n_price_scenarios, forecaster, max_historical_days, market: the STOCHASTIC mode (module docstring).  forecaster="backcast": every plant bids on S = n_price_scenarios price scenarios, scenario i
+        being the (i + 1)-th most recent of the D = max_historical_days whole days before the simulated day of the plant's own circular
+        series (workflow/forecaster.py::Backcaster, with the realised prices as its history; days before the start of the simulation are
+        taken from the series, wrapping); the S solutions of a period become one bid curve (workflow/bid_curves.py, p_min = 0).
+        market="price_taker": the plant is dispatched along its curve at the price that occurs (workflow/market.py::clear_price_taker;
+        look-ahead periods of the hourly market at scenario 0's prices); "stub": at the curve's last point.  The defaults are the
+        deterministic loop, unchanged.  In the stochastic mode `record` keeps all S bidding solutions, the curves and the dispatches,
+        and results() reports `offered_mwh` (the day-ahead curves' last points) next to the cleared `da_energy_mwh`."""
         import torch
         from .workflow import Tracker
         self.B = B = int(n_scenarios)
+        self.S = S = int(n_price_scenarios)
+        self.D = D = int(max_historical_days)
+        if forecaster not in ("perfect", "backcast") or market not in ("stub", "price_taker"):
+            raise ValueError(f"forecaster is 'perfect' or 'backcast' and market 'stub' or 'price_taker', not {forecaster!r} / {market!r}")
+        if forecaster == "backcast" and not 1 <= S <= min(16, D):
+            raise ValueError(f"forecaster='backcast' needs 1 <= n_price_scenarios <= min(16, max_historical_days), not {S} (max_historical_days={D})")
+        if forecaster == "perfect" and S != 1:
+            raise ValueError("forecaster='perfect' knows one price scenario: n_price_scenarios must be 1")
+        self.forecaster, self.market = forecaster, market
+        self.stochastic = forecaster != "perfect" or market != "stub"
+        rows = B * S                                                       # rows of the bidding LPs' batches (plant b, scenario i: row b * S + i)
         self.dev = dev = torch.device("cuda", device) if lp_backend is None else torch.device("cpu")
         s = scenarios.load_series(series)
         self.N = N = len(s["rt_lmp"])
+        if self.stochastic and (24 * D > N or tracking_horizon > real_time_horizon):
+            raise ValueError("the stochastic mode needs max_historical_days whole days inside the series and tracking_horizon <= real_time_horizon")
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float64), device=dev)
         self.da_series = t(np.clip(s["da_lmp"], 0.0, price_cap))
         self.rt_series = t(np.clip(s["rt_lmp"], 0.0, price_cap))
@@ -189,11 +233,11 @@ class BatchedWindBatteryDoubleLoop:
         tracker._pass_market_dispatch([0.0] * tracking_horizon)           # dispatch rows become equalities
         tr_model = tracker.model
         self.penalty = float(bidder.real_time_underbid_penalty)
-        self.da = _DeviceModel(da_model, B, dev, device, hints=getattr(da_model, "solver_hints", None), lp_backend=lp_backend,
+        self.da = _DeviceModel(da_model, rows, dev, device, hints=getattr(da_model, "solver_hints", None), lp_backend=lp_backend,
                                waste_cost_per_kw=bidder.bidding_model_object.wind_waste_penalty * 1e-3,
                                cf_template_sum=float(np.sum(s["rt_cf"][:day_ahead_horizon])))
         waste = bidder.bidding_model_object.wind_waste_penalty * 1e-3
-        self.rt = _DeviceModel(rt_model, B, dev, device, hints=getattr(rt_model, "solver_hints", None), lp_backend=lp_backend,
+        self.rt = _DeviceModel(rt_model, rows, dev, device, hints=getattr(rt_model, "solver_hints", None), lp_backend=lp_backend,
                                waste_cost_per_kw=waste, cf_template_sum=float(np.sum(s["rt_cf"][:real_time_horizon])))
         self.tr = _DeviceModel(tr_model, B, dev, device, hints=getattr(tr_model, "solver_hints", None), lp_backend=lp_backend,
                                waste_cost_per_kw=waste, cf_template_sum=float(np.sum(s["rt_cf"][:tracking_horizon])))
@@ -228,8 +272,8 @@ class BatchedWindBatteryDoubleLoop:
             if lp_backend is None and self.da.opts is not None:
                 import os
                 self.da.opts.warm_patience = int(os.environ.get("DSP_WARM_PATIENCE", warm_patience))
-            self.da_x0 = torch.zeros((B, da_model.lp.n), dtype=torch.float64, device=dev)
-            self.da_y0 = torch.zeros((B, max(da_model.lp.m, 1)), dtype=torch.float64, device=dev)
+            self.da_x0 = torch.zeros((rows, da_model.lp.n), dtype=torch.float64, device=dev)
+            self.da_y0 = torch.zeros((rows, max(da_model.lp.m, 1)), dtype=torch.float64, device=dev)
         self.tr.track_rows = idx([tr_model.block.kept_row_index(r) for r in tr_model.tracking_rows])
         self.tr.c[:] = t(tr_model.c[0])
         # ---- realised state + annual accumulators (device) -----------------------------------------------------------
@@ -242,13 +286,22 @@ class BatchedWindBatteryDoubleLoop:
         self.hour_t = torch.zeros((), dtype=torch.int64, device=dev)      # the clock ON THE DEVICE (graphs replay across days)
         self.da_offer = torch.zeros((B, 24), dtype=torch.float64, device=dev)
         self.da_prices = torch.zeros((B, 24), dtype=torch.float64, device=dev)
-        self.da_pw = torch.zeros(B, dtype=torch.float64, device=dev)
+        self.da_pw = torch.zeros(rows, dtype=torch.float64, device=dev)
         self.delivered = z()
         self._hundred = torch.full((), 100.0, dtype=torch.float64, device=dev)
         self.solves = 0
         self.use_graphs = bool(use_graphs) and lp_backend is None
         self.simplex_warm = bool(simplex_warm) and lp_backend is None      # hourly LPs start from the previous hour's basis (_DeviceModel.solve)
         self.use_fused = bool(use_fused) and lp_backend is None and real_time_horizon <= 8 and tracking_horizon <= 8
+        if self.stochastic:
+            from .hip_solver import MARKET_MAX_T
+            self.use_fused = self.use_fused and day_ahead_horizon <= MARKET_MAX_T
+            # curves (integer cents: power, price; `count` points each) and dispatches of the current day / hour, persistent like everything a step touches
+            i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+            self.da_curve, self.da_count = i32(B, 24, S + 1, 2), i32(B, 24)
+            self.rt_curve, self.rt_count = i32(B, tracking_horizon, S + 1, 2), i32(B, tracking_horizon)
+            self.rt_dispatch = torch.zeros((B, tracking_horizon), dtype=torch.float64, device=dev)
+            self.offered_mwh = z()
         if self.use_fused:
             from .hip_solver import DspWbState, load_library
             self._lib = load_library()
@@ -261,16 +314,30 @@ class BatchedWindBatteryDoubleLoop:
             st.delivered, st.revenue, st.energy_mwh = self.delivered.data_ptr(), self.revenue.data_ptr(), self.energy_mwh.data_ptr()
             st.bad, st.uncertified = self.bad.data_ptr(), self.uncertified.data_ptr()
             self._wb_state, self._wb_rt, self._wb_tr = st, self.rt.wb_struct(needs_state=False), self.tr.wb_struct()
+            if self.stochastic:
+                from .hip_solver import DspMarketState
+                mk = DspMarketState()
+                mk.B, mk.S, mk.D, mk.N = B, S, D, N
+                mk.backcast, mk.price_taker = int(forecaster == "backcast"), int(market == "price_taker")
+                for name in ("start", "hour", "da_series", "rt_series", "cf_series", "soc", "thr", "da_offer", "da_prices", "bad", "uncertified"):
+                    setattr(mk, name, getattr(st, name))
+                self._mk_state, self._mk_da, self._mk_rt = mk, self.da.market_struct(), self.rt.market_struct()
         self._graphs = {}                                                  # "da" / hour of day -> captured hipGraph
         self._rec = None
         if record is not None:
             plants, days = record
             R, H = len(plants), 24 * int(days)
             buf = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+            sc = (S,) if self.stochastic else ()                            # stochastic mode: every scenario's bidding solution
             self._rec = dict(plants=idx(plants), days=int(days),
-                             state=buf(H + 1, R, 2), rt_x=buf(H + 1, R, self.rt.lp.n), tr_x=buf(H + 1, R, self.tr.lp.n),
-                             rt_obj=buf(H + 1, R), tr_obj=buf(H + 1, R),
-                             da_state=buf(int(days) + 1, R, 2), da_x=buf(int(days) + 1, R, self.da.lp.n), da_obj=buf(int(days) + 1, R))
+                             state=buf(H + 1, R, 2), rt_x=buf(H + 1, R, *sc, self.rt.lp.n), tr_x=buf(H + 1, R, self.tr.lp.n),
+                             rt_obj=buf(H + 1, R, *sc), tr_obj=buf(H + 1, R),
+                             da_state=buf(int(days) + 1, R, 2), da_x=buf(int(days) + 1, R, *sc, self.da.lp.n), da_obj=buf(int(days) + 1, R, *sc))
+            if self.stochastic:
+                ibuf = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+                Dn, Ttr = int(days) + 1, tracking_horizon
+                self._rec.update(da_curve=ibuf(Dn, R, 24, S + 1, 2), da_count=ibuf(Dn, R, 24), da_dispatch=buf(Dn, R, 24),
+                                 rt_curve=ibuf(H + 1, R, Ttr, S + 1, 2), rt_count=ibuf(H + 1, R, Ttr), rt_dispatch=buf(H + 1, R, Ttr))
             self._day_t = torch.zeros((), dtype=torch.int64, device=dev)
             self._limit_h = torch.full((), H, dtype=torch.int64, device=dev)      # (rows past the recorded span land in the spare last row)
             self._limit_d = torch.full((), int(days), dtype=torch.int64, device=dev)
@@ -288,6 +355,9 @@ class BatchedWindBatteryDoubleLoop:
         H, D = min(self.hour, 24 * r["days"]), min(self.hour // 24, r["days"])
         out = {k: r[k][:H].cpu().numpy() for k in ("state", "rt_x", "tr_x", "rt_obj", "tr_obj")}
         out.update({k: r[k][:D].cpu().numpy() for k in ("da_state", "da_x", "da_obj")})
+        if self.stochastic:
+            out.update({k: r[k][:H].cpu().numpy() for k in ("rt_curve", "rt_count", "rt_dispatch")})
+            out.update({k: r[k][:D].cpu().numpy() for k in ("da_curve", "da_count", "da_dispatch")})
         out["plants"] = r["plants"].cpu().numpy()
         return out
 
@@ -298,6 +368,8 @@ class BatchedWindBatteryDoubleLoop:
                   self.da_offer, self.da_prices):
             t.zero_()
         self.bad.zero_()
+        if self.stochastic:
+            self.offered_mwh.zero_()
         if self.warm_start:
             self.da_x0.zero_(), self.da_y0.zero_()
         self.hour = self.solves = 0
@@ -363,6 +435,169 @@ class BatchedWindBatteryDoubleLoop:
         self.da_offer.copy_(out["x"][:, m.pda_cols][:, :24])
         self.da_prices.copy_(da[:, :24])
         self.da_energy_mwh += self.da_offer.sum(1)
+
+    # -- stochastic mode: backcast scenarios, bid curves, market clearing ---------------------------------------------------------
+    def _forecast(self, series, T, hod):
+        """[B, S, T] price scenarios asked at hour-of-day `hod` of the current day (clock read on the device).  Backcast: exactly
+        Backcaster._forecast over the D whole days before the current day of every plant's own circular series -
+        pos = (24 (D - 1 - i) + hod + t) mod 24 D into that history, i.e. series[(start + 24 (d - D) + pos) mod N]."""
+        import torch
+        if self.forecaster == "perfect":
+            return self._window(series, T)[:, None, :]
+        D = self.D
+        d = torch.div(self.hour_t, 24, rounding_mode="floor")
+        i, t = torch.arange(self.S, device=self.dev)[:, None], torch.arange(T, device=self.dev)[None, :]
+        pos = (24 * (D - 1 - i) + hod + t) % (24 * D)
+        return series[(self.start[:, None, None] + 24 * (d - D) + pos[None]) % self.N]
+
+    def _rows(self, v):
+        """per-plant values [B, ...] -> per-row [B * S, ...] (a plant's S rows are adjacent)"""
+        return v if self.S == 1 else v.repeat_interleave(self.S, dim=0)
+
+    def _set_state_rows(self, m):
+        """_set_state for a bidding model of B * S rows: the plant's state, wind availability and objective constant in each of its rows"""
+        soc, thr = self._rows(self.soc), self._rows(self.thr)
+        m.lb[:, m.soc_init] = soc
+        m.ub[:, m.soc_init] = soc
+        m.lb[:, m.thr_init] = thr
+        m.ub[:, m.thr_init] = thr
+        avail = m.wind_kw * self._window(self.cf_series, m.T)
+        m.ub[:, m.wind_cols] = self._rows(avail)
+        total = avail[:, 0]
+        for t in range(1, m.T):
+            total = total + avail[:, t]
+        m.c0.copy_(self._rows(m._c0_base + m._waste_per_kw * total))
+
+    def _curves(self, power, price, status):
+        """power, price [B, S, Tc]; status [B * S] -> (U, M [S + 1, B * Tc] int64 cents, count [B * Tc]) - workflow/market.py::plant_curves"""
+        import torch
+        from .workflow.market import plant_curves
+        B, S, Tc = power.shape
+        lanes = lambda a: a.expand(B, S, Tc).permute(1, 0, 2).reshape(S, B * Tc)
+        return plant_curves(torch, lanes(power), lanes(price), lanes((status == 0).reshape(B, S, 1)))
+
+    def _clear(self, U, M, count, lmp):
+        import torch
+        from .workflow.market import clear_curves
+        return clear_curves(torch, U, M, count, lmp.reshape(-1), self._hundred, price_taker=self.market == "price_taker").reshape(lmp.shape)
+
+    def _store_curves(self, curve, cnt, U, M, count):
+        import torch
+        B, Tc = cnt.shape
+        curve.copy_(torch.stack([U.t().reshape(B, Tc, self.S + 1), M.t().reshape(B, Tc, self.S + 1)], dim=3))
+        cnt.copy_(count.reshape(B, Tc))
+
+    def _market(self, fn, *args):
+        import ctypes as C
+        import torch
+        rc = fn(C.byref(self._mk_state), *args, C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"{fn.__name__} failed ({rc})")
+
+    def _day_ahead_step_stochastic(self):
+        """Day-ahead bids of the stochastic mode (capturable): B * S 48-h LPs - row b * S + i on scenario i's day-ahead and real-time
+        prices, plant b's state and wind -, one curve per plant-hour from the S day_ahead_power values and day-ahead forecasts, cleared
+        at the realised day-ahead price (market="stub": at its last point).  Rolling warm start per row: scenario i of day d + 1 over
+        its first 24 h is scenario i of day d over its last 24 h, so yesterday's row shifted by 24 h is as close a point as in the
+        deterministic loop."""
+        import ctypes as C
+        import torch
+        m, B, S = self.da, self.B, self.S
+        if self.use_fused:
+            self._market(self._lib.dsp_market_prepare, C.byref(self._mk_da), -1)
+        else:
+            da, rt = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T), self._forecast(self.rt_series, m.T, 0).expand(B, S, m.T)
+            self._set_prices(m, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
+            self._set_state_rows(m)
+            m.lb.index_fill_(1, m.pda_cols, 0.0)
+            m.ub.index_fill_(1, m.pda_cols, float("inf"))
+        if self.warm_start:
+            out = m.solve(B * S, x0=self.da_x0, y0=self.da_y0, primal_weight=self.da_pw)
+            torch.index_select(out["x"], 1, self.da_cmap, out=self.da_x0)
+            torch.index_select(out["y"], 1, self.da_rmap, out=self.da_y0)
+        else:
+            if not self.weight_only:
+                self.da_pw.zero_()
+            out = m.solve(B * S, primal_weight=self.da_pw)
+        if self.use_fused:                            # (status / flags of the solve: folded into bad / uncertified by the kernel)
+            self._market(self._lib.dsp_market_clear, C.byref(self._mk_da), None, -1, 24, C.c_void_p(self.da_offer.data_ptr()),
+                         C.c_void_p(self.da_curve.data_ptr()), C.c_void_p(self.da_count.data_ptr()))
+        else:
+            self._check(out)
+            power = out["x"][:, m.pda_cols[:24]].reshape(B, S, 24)
+            U, M, count = self._curves(power, self._forecast(self.da_series, 24, 0), out["status"])
+            realised = self._window(self.da_series, 24)
+            self.da_offer.copy_(self._clear(U, M, count, realised))
+            self.da_prices.copy_(realised)
+            self._store_curves(self.da_curve, self.da_count, U, M, count)
+        if self._rec is not None:
+            self._record("da_state", torch.stack([self.soc, self.thr], 1), daily=True)
+            self._record("da_x", out["x"].reshape(B, S, -1), daily=True)
+            self._record("da_obj", out["obj"].reshape(B, S), daily=True)
+            for key, v in (("da_curve", self.da_curve), ("da_count", self.da_count), ("da_dispatch", self.da_offer)):
+                self._record(key, v, daily=True)
+        self.da_energy_mwh += self.da_offer.sum(1)
+        last = torch.gather(self.da_curve[:, :, :, 0], 2, (self.da_count.to(torch.int64) - 1)[:, :, None])[:, :, 0]
+        self.offered_mwh += (last.to(torch.float64) / self._hundred).sum(1)
+
+    def _hour_step_stochastic(self, k):
+        """Hour k of the day in the stochastic mode (capturable): B * S real-time LPs (scenario i = the real-time backcast at hour-of-day
+        k; realised day-ahead prices and the cleared day_ahead_power inside the cleared day, backcast day-ahead prices beyond it), one
+        curve per plant and tracked period from (P_T, real-time forecast), cleared at the realised real-time price for the hour at hand
+        and at scenario 0's forecast for the look-ahead periods; tracking (B LPs), state hand-off, revenue and clock as _hour_step."""
+        import ctypes as C
+        import torch
+        m, tr, B, S = self.rt, self.tr, self.B, self.S
+        hour = k if self.simplex_warm else None
+        if self._rec is not None:
+            self._record("state", torch.stack([self.soc, self.thr], 1))
+        if self.use_fused:
+            self._market(self._lib.dsp_market_prepare, C.byref(self._mk_rt), k)
+            m.solve(B * S, hour=hour)
+            self._market(self._lib.dsp_market_clear, C.byref(self._mk_rt), C.byref(self._wb_tr), k, tr.T, C.c_void_p(self.rt_dispatch.data_ptr()),
+                         C.c_void_p(self.rt_curve.data_ptr()), C.c_void_p(self.rt_count.data_ptr()))
+            tr.solve(B, hour=hour)
+        else:
+            rt_f = self._forecast(self.rt_series, m.T, k).expand(B, S, m.T)
+            da_f = self._forecast(self.da_series, m.T, k).expand(B, S, m.T).clone()
+            known = min(m.T, 24 - k)                                     # hours of the horizon inside the cleared day
+            da_f[:, :, :known] = self.da_prices[:, None, k:k + known]
+            self._set_prices(m, da_f.reshape(B * S, m.T), rt_f.reshape(B * S, m.T))
+            self._set_state_rows(m)
+            m.lb.index_fill_(1, m.pda_cols, 0.0)
+            m.ub.index_fill_(1, m.pda_cols, float("inf"))
+            m.lb[:, m.pda_cols[:known]] = self._rows(self.da_offer[:, k:k + known])
+            m.ub[:, m.pda_cols[:known]] = self._rows(self.da_offer[:, k:k + known])
+            out = m.solve(B * S, hour=hour) if m.opts is not None else m.solve(B * S)
+            self._check(out)
+            power = m.power_output(out["x"])[:, :tr.T].reshape(B, S, tr.T)
+            U, M, count = self._curves(power, rt_f[:, :, :tr.T], out["status"])
+            lmp = torch.cat([self._window(self.rt_series, 1), rt_f[:, 0, 1:tr.T]], dim=1)
+            self.rt_dispatch.copy_(self._clear(U, M, count, lmp))
+            self._store_curves(self.rt_curve, self.rt_count, U, M, count)
+            self._set_state(tr)
+            tr.rlo[:, tr.track_rows] = self.rt_dispatch
+            tr.rhi[:, tr.track_rows] = self.rt_dispatch
+            out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
+            self._check(out)
+        if self._rec is not None:
+            self._record("rt_x", m.out["x"].reshape(B, S, -1))
+            self._record("rt_obj", m.out["obj"].reshape(B, S))
+            self._record("tr_x", tr.out["x"])
+            self._record("tr_obj", tr.out["obj"])
+            for key, v in (("rt_curve", self.rt_curve), ("rt_count", self.rt_count), ("rt_dispatch", self.rt_dispatch)):
+                self._record(key, v)
+        if self.use_fused:
+            self._fused(2, k)                         # delivered power, 2-dp state hand-off, revenue, energy, clock: unchanged
+            return
+        x = tr.out["x"]
+        rt0 = self._window(self.rt_series, 1)[:, 0]
+        self.delivered.copy_(tr.power_output(x)[:, 0])
+        self.soc.copy_(torch.round(x[:, tr.soc0] * 100.0) / self._hundred)
+        self.thr.copy_(torch.round(x[:, tr.thr0] * 100.0) / self._hundred)
+        self.revenue += self.delivered * rt0 + self.da_offer[:, k] * (self.da_prices[:, k] - rt0)
+        self.energy_mwh += self.delivered
+        self.hour_t += 1
 
     def _fused(self, phase, k):
         import ctypes as C
@@ -446,15 +681,15 @@ class BatchedWindBatteryDoubleLoop:
     def day_ahead(self):
         """Day-ahead bids of every plant for the day that starts at self.hour: returns the offers [B, 24] (= cleared dispatch)."""
         self.day_start = self.hour
-        self._run("da", self._day_ahead_step)
-        self.solves += self.B
+        self._run("da", self._day_ahead_step_stochastic if self.stochastic else self._day_ahead_step)
+        self.solves += self.B * self.S
         return self.da_offer.clone()
 
     def hour_step(self):
         """Real-time bid, stub clearing, tracking and state hand-off of ONE hour for every plant (all on the device)."""
         k = self.hour - self.day_start                                  # hour of the day
-        self._run(k, lambda: self._hour_step(k))
-        self.solves += 2 * self.B
+        self._run(k, (lambda: self._hour_step_stochastic(k)) if self.stochastic else (lambda: self._hour_step(k)))
+        self.solves += self.B * self.S + self.B
         self.hour += 1
         return self.delivered.clone()
 
@@ -466,7 +701,10 @@ class BatchedWindBatteryDoubleLoop:
 
     def results(self):
         """Per-scenario totals so far (device tensors) + whether every solve was optimal (one device->host sync)."""
-        return dict(obj=self.revenue, energy_mwh=self.energy_mwh, soc=self.soc, throughput=self.thr), not bool(self.bad.item())
+        res = dict(obj=self.revenue, energy_mwh=self.energy_mwh, soc=self.soc, throughput=self.thr)
+        if self.stochastic:                            # what the market left on the table: offered (the curves' last points) against cleared
+            res.update(da_energy_mwh=self.da_energy_mwh, offered_mwh=self.offered_mwh)
+        return res, not bool(self.bad.item())
 
 
 class PipelinedDoubleLoops:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 12
+#define DSP_VERSION 13
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -435,6 +435,64 @@ typedef struct dsp_bid_request {
   double constant[DSP_BID_MAX_HOURS];
 } dsp_bid_request;
 int dsp_bid_points(const dsp_bid_request *rq, void *hipStream);
+
+/* Stochastic mode of the wind + battery double loop ON THE DEVICE (ABI 13; dispatches_amd/rolling.py, n_price_scenarios / forecaster /
+ * market): every plant b bids on S price scenarios - rows b * S + i of the bidding LPs' batches -, its (power, marginal price) pairs of
+ * a period become ONE bid curve, and the market dispatches the plant along that curve at the price that occurs.
+ *   scenario i with the backcast forecaster, hour-of-day `hod`, on simulated day d = hour / 24, period t:
+ *     series[(start[b] + 24 (d - D) + (24 (D - 1 - i) + hod + t) mod (24 D)) mod N]      (workflow/forecaster.py: Backcaster._forecast
+ *   over the D whole days before day d of the plant's own circular series); with the perfect forecaster: series[(start[b] + hour + t) mod N].
+ *   curve of (plant, period): both numbers of every pair to integer cents exactly as Python's round(v, 2), pairs of rows whose solve is
+ *   not optimal or with negative power dropped, the highest price per distinct power, the point (0, lowest price or 0) in front if no
+ *   pair sits at power 0, running maximum over the prices: U_0 < U_1 < ..., M_0 <= M_1 <= ... (workflow/bid_curves.py with p_min = 0).
+ *   clearing (workflow/market.py: clear_price_taker): dispatch = max{ U_j : M_j / 100 <= lmp }, U_0 if there is none; with the stub
+ *   market the curve's last point. */
+#define DSP_MARKET_MAX_T 48
+#define DSP_MARKET_MAX_S 16
+typedef struct dsp_market_model {
+  double *c, *lb, *ub;                 /* [B * S][n] per-row vectors of a bidding LP (the dsp_batch inputs of its solves)          */
+  const double *base_c;                /* [n] cost vector without prices                                                          */
+  const double *x;                     /* [B * S][n] solution of its last solve                                                   */
+  double *c0;                          /* [B * S] objective constant of every row or NULL                                         */
+  const int32_t *status, *flags;       /* [B * S] outputs of its last solve (flags may be NULL)                                   */
+  int32_t n, T;                        /* columns, horizon (T <= DSP_MARKET_MAX_T)                                                */
+  int32_t soc_init, thr_init;          /* columns fixed to the realised state of charge / energy throughput                       */
+  int32_t wind_cols[DSP_MARKET_MAX_T]; /* wind production column of every period (upper bound = availability)                     */
+  int32_t pt_cols[DSP_MARKET_MAX_T][2];/* P_T[t] = 1e-3 (x[a] + x[b])                                                             */
+  int32_t pda_cols[DSP_MARKET_MAX_T];  /* day-ahead power column of every period                                                  */
+  double wind_kw, c0_base, waste_per_kw;
+} dsp_market_model;
+
+typedef struct dsp_market_state {
+  int32_t B, S, D, N;                  /* plants, scenarios per plant (<= DSP_MARKET_MAX_S), history days, length of the series   */
+  int32_t backcast, price_taker;       /* 0 / 1: forecaster (0 = perfect: S must be 1), market (0 = stub)                         */
+  const int64_t *start;                /* [B] first hour of every plant's year in the series                                      */
+  const int64_t *hour;                 /* [1] the clock (read only here)                                                          */
+  const double *da_series, *rt_series, *cf_series;   /* [N]                                                                       */
+  const double *soc, *thr;             /* [B] realised state                                                                      */
+  const double *da_offer;              /* [B][24] cleared day-ahead dispatch of the current day (read by dsp_market_prepare, k >= 0)    */
+  double *da_prices;                   /* [B][24] realised day-ahead prices of the current day (written by the day-ahead clearing)    */
+  uint8_t *bad;                        /* [1] or NULL: set to 1 when a bidding solve left a status other than optimal             */
+  int64_t *uncertified;                /* [1] or NULL: + the rows a solve left flagged DSP_FLAG_OBJ_WAIVED                        */
+} dsp_market_state;
+
+/* Scenario fan-out: objective, mutable bounds and objective constant of the B * S rows of bidding model `m` for the solve that follows.
+ * k = -1: the day-ahead LP at hour 0 of the day (day_ahead_power free in every period); k = 0 .. 23: the real-time LP of hour-of-day k
+ * (day-ahead prices and day_ahead_power of the periods inside the cleared day from da_prices / da_offer, as phase 0 of
+ * dsp_wb_rolling_update).  One lane per row.  DSP_ERR_INVALID (nothing launched) for a NULL buffer, S or D out of range, a column
+ * index outside [0, n). */
+int dsp_market_prepare(const dsp_market_state *st, const dsp_market_model *m, int32_t k, void *hipStream);
+
+/* Curve + clearing, one lane per (plant, period t < T): the S keys of the lane live in registers and are sorted by an unrolled
+ * compare-exchange network.  Outputs: dispatch [B][T] MW, curve [B][T][S + 1][2] int32 cents (power, price; unused slots 0),
+ * count [B][T] points of each curve.  Rows with status != 0 offer nothing and set dsp_market_state::bad.
+ * k = -1 (day-ahead, T = 24): power = x[day_ahead_power column of t], prices = the day-ahead forecast, cleared at the realised
+ *   day-ahead price; the realised prices go to da_prices (the loop passes its da_offer buffer as `dispatch`).
+ * k = 0 .. 23 (real time, T <= 8): power = P_T[t], prices = the real-time forecast at hour-of-day k, cleared at the realised
+ *   real-time price for t = 0 and at scenario 0's forecast for t >= 1.  With `tr` (the tracking model; may be NULL) the lane also
+ *   does what phase 1 of dsp_wb_rolling_update does for the tracker: dispatch -> its dispatch rows, realised state, wind availability, c0. */
+int dsp_market_clear(const dsp_market_state *st, const dsp_market_model *m, const dsp_wb_model *tr, int32_t k, int32_t T,
+                     double *dispatch, int32_t *curve, int32_t *count, void *hipStream);
 
 /* Introspection */
 int dsp_get_dims(const dsp_handle *h, int32_t *n, int32_t *m, int64_t *nnz);
