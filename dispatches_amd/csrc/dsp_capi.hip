@@ -400,6 +400,63 @@ int dsp_market_clear(const dsp_market_state *st, const dsp_market_model *m, cons
   return DSP_OK;
 }
 
+// ... and of the descriptor loop's (dsp_loop_market_*): every index a kernel would use is checked here, nothing is launched otherwise
+static bool loop_market_state_ok(const dsp_loop_market_state *st) {
+  if (!st || st->B < 0 || st->N < 1 || st->S < 1 || st->S > DSP_MARKET_MAX_S || st->p_min_cents < 0 || st->p_min_cents > 2000000000ll) return false;
+  if (st->backcast ? (st->D < 1 || st->S > st->D || 24ll * st->D > st->N) : st->S != 1) return false;
+  return st->start && st->hour && st->da_series && st->rt_series;
+}
+static bool loop_market_model_ok(const dsp_loop_market_model *m) {
+  return m && m->n >= 1 && m->T >= 1 && m->T <= DSP_MARKET_MAX_T && m->n_state >= 0 && m->n_state <= 2;
+}
+
+int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, int32_t k, void *hipStream) {
+  if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < -1 || k > 23) return DSP_ERR_INVALID;
+  if (!m->c || !m->lb || !m->ub || !m->base_c || !m->c0) return DSP_ERR_INVALID;
+  if (k >= 0 && (!st->da_offer || !st->da_prices)) return DSP_ERR_INVALID;
+  if (m->n_state > 0 && !st->state) return DSP_ERR_INVALID;
+  for (int j = 0; j < m->n_state; ++j)
+    if (!market_col_ok(m->state_init[j], m->n)) return DSP_ERR_INVALID;
+  const bool wind = m->wind_cols[0] >= 0;
+  if (wind && !st->cf_series) return DSP_ERR_INVALID;
+  for (int t = 0; t < m->T; ++t) {
+    if (!market_col_ok(m->pda_cols[t], m->n) || (wind && !market_col_ok(m->wind_cols[t], m->n))) return DSP_ERR_INVALID;
+    for (int e = 0; e < 2; ++e)
+      if (m->pt_cols[t][e] != -1 && !market_col_ok(m->pt_cols[t][e], m->n)) return DSP_ERR_INVALID;
+  }
+  if (st->B == 0) return DSP_OK;
+  HIP_TRY(launch_loop_market_prepare(*st, *m, (int)k, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
+int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market_model *m, const dsp_loop_model *tr, int32_t k, int32_t T,
+                          double *dispatch, int32_t *curve, int32_t *count, void *hipStream) {
+  if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < -1 || k > 23 || T < 1 || T > m->T) return DSP_ERR_INVALID;
+  if (!m->x || !m->status || !dispatch || !curve || !count) return DSP_ERR_INVALID;
+  if (k < 0 ? (T > 24 || !st->da_prices || tr) : T > DSP_LOOP_MAX_T) return DSP_ERR_INVALID;
+  for (int t = 0; t < T; ++t) {
+    if (k < 0) {
+      if (!market_col_ok(m->pda_cols[t], m->n)) return DSP_ERR_INVALID;
+    } else {
+      for (int e = 0; e < 2; ++e)
+        if (m->pt_cols[t][e] != -1 && !market_col_ok(m->pt_cols[t][e], m->n)) return DSP_ERR_INVALID;
+    }
+  }
+  if (tr) {
+    if (tr->T != T || tr->n < 1 || tr->m < 1 || tr->n_state != m->n_state || !tr->lb || !tr->ub || !tr->rlo || !tr->rhi || !tr->c0) return DSP_ERR_INVALID;
+    if (tr->n_state > 0 && !st->state) return DSP_ERR_INVALID;
+    for (int j = 0; j < tr->n_state; ++j)
+      if (!market_col_ok(tr->state_init[j], tr->n)) return DSP_ERR_INVALID;
+    const bool wind = tr->wind_cols[0] >= 0;
+    if (wind && !st->cf_series) return DSP_ERR_INVALID;
+    for (int t = 0; t < T; ++t)
+      if (!market_col_ok(tr->track_rows[t], tr->m) || (wind && !market_col_ok(tr->wind_cols[t], tr->n))) return DSP_ERR_INVALID;
+  }
+  if (st->B == 0) return DSP_OK;
+  HIP_TRY(launch_loop_market_clear(*st, *m, tr, (int)k, (int)T, dispatch, curve, count, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
 void dsp_default_options(dsp_options *o) {
   if (!o) return;
   std::memset(o, 0, sizeof(*o));

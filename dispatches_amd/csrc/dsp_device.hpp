@@ -174,6 +174,10 @@ hipError_t launch_bid_points(const dsp_bid_request &rq, hipStream_t st);
 hipError_t launch_market_prepare(const dsp_market_state &st, const dsp_market_model &m, int k, hipStream_t stream);
 hipError_t launch_market_clear(const dsp_market_state &st, const dsp_market_model &m, const dsp_wb_model *tr, int k, int T, double *dispatch,
                                int32_t *curve, int32_t *count, hipStream_t stream);
+// ... and of the descriptor loop of any flowsheet (dsp_loop_market_*)
+hipError_t launch_loop_market_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, int k, hipStream_t stream);
+hipError_t launch_loop_market_clear(const dsp_loop_market_state &st, const dsp_loop_market_model &m, const dsp_loop_model *tr, int k, int T,
+                                    double *dispatch, int32_t *curve, int32_t *count, hipStream_t stream);
 hipError_t launch_spmv(int cpl, int rpl, const SpmvArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t st);
 
 #endif

@@ -14,6 +14,11 @@
 //                           -Rpass-analysis=kernel-resource-usage); duplicates, the zero-power point and the running maximum are one
 //                           pass over the sorted registers, which also clears the curve at the price that occurs.
 //
+//   loop_market_prepare_kernel / loop_market_clear_kernel   the same two for ANY flowsheet, by descriptor (dsp_loop_market_*; rolling_flowsheets.py):
+//                           power P_T = (x[a] ca + x[b] cb) + const, curves that start at the generator's p_min, <= 2 state columns,
+//                           optional wind; the clearing lanes also write the tracker's LP (a dsp_loop_model).  VGPRs / scratch of every
+//                           instantiation: profiles/loop_market_kernel_resources.txt.
+//
 // Every product is made opaque before it is added (as in wb_rolling_kernel, dsp_capi.hip): the results are bit-identical to the
 // tensor operations of dispatches_amd/rolling.py (use_fused=False), which is how the kernels are tested.
 #include <hip/hip_runtime.h>
@@ -66,6 +71,27 @@ __global__ void __launch_bounds__(256) market_prepare_kernel(dsp_market_state s,
   lb[m.thr_init] = thr; ub[m.thr_init] = thr;
 }
 
+// bitonic network over SP keys in registers, ascending (every index a compile-time constant after unrolling); shared by both clearing kernels
+template <int SP>
+__device__ __forceinline__ void mk_sort(long long (&keys)[SP]) {
+#pragma unroll
+  for (int kk = 2; kk <= SP; kk <<= 1) {
+#pragma unroll
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+#pragma unroll
+      for (int i = 0; i < SP; ++i) {
+        const int l = i ^ j;
+        if (l > i) {
+          const long long a = keys[i], c = keys[l];
+          const bool swap = (a > c) == ((i & kk) == 0);
+          keys[i] = swap ? c : a;
+          keys[l] = swap ? a : c;
+        }
+      }
+    }
+  }
+}
+
 template <int SP>
 __global__ void __launch_bounds__(256) market_clear_kernel(dsp_market_state s, dsp_market_model m, dsp_wb_model tr, int has_tr, int k, int T,
                                                            double *dispatch, int32_t *curve, int32_t *count) {
@@ -100,23 +126,7 @@ __global__ void __launch_bounds__(256) market_clear_kernel(dsp_market_state s, d
     keys[i] = key;
   }
   if (any_bad && s.bad) *s.bad = 1;
-  // ---- bitonic network, ascending (every index a compile-time constant after unrolling) ----
-#pragma unroll
-  for (int kk = 2; kk <= SP; kk <<= 1) {
-#pragma unroll
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-#pragma unroll
-      for (int i = 0; i < SP; ++i) {
-        const int l = i ^ j;
-        if (l > i) {
-          const long long a = keys[i], c = keys[l];
-          const bool swap = (a > c) == ((i & kk) == 0);
-          keys[i] = swap ? c : a;
-          keys[l] = swap ? a : c;
-        }
-      }
-    }
-  }
+  mk_sort<SP>(keys);
   // ---- the price that occurs: realised for the day-ahead market and for the hour at hand, scenario 0's for the look-ahead hours ----
   const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[mk_index(s, st0, h, 0, hod, t)];
   // ---- lowest price among the distinct points (the inserted zero-power point takes it) ----
@@ -192,6 +202,188 @@ hipError_t launch_market_clear(const dsp_market_state &st, const dsp_market_mode
   else if (st.S <= 8) DSP_MK_LAUNCH(8);
   else DSP_MK_LAUNCH(16);
 #undef DSP_MK_LAUNCH
+  return hipGetLastError();
+}
+
+// ---- the same two kernels for a flowsheet given by a descriptor (include/dsp_hip.h: dsp_loop_market_*; rolling_flowsheets.py) ----------
+// Bit-identical to BatchedDoubleLoop's tensor form (use_fused=False): every product opaque before it is added, sums in the order of t.
+static_assert(sizeof(dsp_loop_market_state) + sizeof(dsp_loop_market_model) + sizeof(dsp_loop_model) + 64 <= 4096,
+              "the descriptors travel as by-value kernel arguments: HIP's limit is 4 KB");
+
+__device__ __forceinline__ long long lmk_index(const dsp_loop_market_state &s, long long st0, long long h, int i, int hod, int t) {
+  if (!s.backcast) return (st0 + h + t) % s.N;
+  const long long D = s.D, d = h / 24;
+  const long long pos = (24 * (D - 1 - i) + hod + t) % (24 * D);
+  long long v = (st0 + 24 * (d - D) + pos) % s.N;
+  return v < 0 ? v + s.N : v;
+}
+
+__global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m, int k) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= s.B * s.S) return;
+  const int b = r / s.S, i = r - b * s.S;
+  const long long h = *s.hour, st0 = s.start[b];
+  const int hod = k < 0 ? 0 : k;
+  const int known = k < 0 ? 0 : min(m.T, 24 - k);
+  const bool wind = m.wind_cols[0] >= 0;
+  double *c = m.c + (size_t)r * m.n, *lb = m.lb + (size_t)r * m.n, *ub = m.ub + (size_t)r * m.n;
+  double avail_sum = 0.0, price_sum = 0.0;
+  for (int t = 0; t < m.T; ++t) {
+    const long long at = lmk_index(s, st0, h, i, hod, t);
+    const double rtp = s.rt_series[at];
+    const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : s.da_series[at];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int col = m.pt_cols[t][e];
+      if (col >= 0) c[col] = __dsub_rn(m.base_c[col], mk_opaque(__dmul_rn(m.pt_coef[t][e], rtp)));
+    }
+    const int pda = m.pda_cols[t];
+    c[pda] = __dsub_rn(m.base_c[pda], mk_opaque(__dsub_rn(dap, rtp)));
+    const double pc = mk_opaque(__dmul_rn(rtp, m.pt_const[t]));
+    price_sum = t ? __dadd_rn(price_sum, pc) : pc;
+    if (wind) {
+      const double avail = mk_opaque(__dmul_rn(m.wind_kw, s.cf_series[(st0 + h + t) % s.N]));     // capacity factors: the realised window
+      ub[m.wind_cols[t]] = avail;
+      avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
+    }
+    const double fix = t < known ? s.da_offer[(size_t)b * 24 + k + t] : 0.0;
+    lb[pda] = fix;
+    ub[pda] = t < known ? fix : INFINITY;
+  }
+  double c0 = mk_opaque(__dsub_rn(m.c0_base, price_sum));
+  if (wind) c0 = __dadd_rn(c0, mk_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
+  m.c0[r] = c0;
+  for (int j = 0; j < m.n_state; ++j) {
+    const double v = s.state[(size_t)b * m.n_state + j];
+    lb[m.state_init[j]] = v; ub[m.state_init[j]] = v;
+  }
+}
+
+template <int SP>
+__global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_state s, dsp_loop_market_model m, dsp_loop_model tr, int has_tr,
+                                                                int k, int T, double *dispatch, int32_t *curve, int32_t *count) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= s.B * T) return;
+  const int b = g / T, t = g - b * T;
+  const int S = s.S;
+  const long long h = *s.hour, st0 = s.start[b];
+  const long long pmin = s.p_min_cents;
+  const int hod = k < 0 ? 0 : k;
+  const double *series = k < 0 ? s.da_series : s.rt_series;
+  const int ca = k < 0 ? m.pda_cols[t] : m.pt_cols[t][0], cb = k < 0 ? -1 : m.pt_cols[t][1];
+  const double fa = m.pt_coef[t][0], fb = m.pt_coef[t][1], fc = m.pt_const[t];
+  // ---- the S pairs of this plant and period as sort keys, in registers ----
+  long long keys[SP];
+  bool any_bad = false;
+#pragma unroll
+  for (int i = 0; i < SP; ++i) {
+    long long key = kBidDrop;
+    if (i < S) {
+      const size_t row = (size_t)b * S + i;
+      if (m.status[row] == 0) {
+        const double *x = m.x + row * m.n;
+        double power;
+        if (k < 0) {
+          power = x[ca];
+        } else {
+          double p = ca >= 0 ? mk_opaque(__dmul_rn(x[ca], fa)) : 0.0;
+          if (cb >= 0) p = mk_opaque(__dadd_rn(p, mk_opaque(__dmul_rn(x[cb], fb))));
+          power = __dadd_rn(p, fc);
+        }
+        const double price = series[lmk_index(s, st0, h, i, hod, t)];
+        const long long pc = bid_cents(power), cc = bid_cents(price);
+        if (pc >= pmin && fabs(power) < INFINITY && fabs(price) < INFINITY) key = bid_key(pc, cc);
+      } else {
+        any_bad = true;
+      }
+      if (t == 0 && m.flags && s.uncertified && (m.flags[row] & DSP_FLAG_OBJ_WAIVED))
+        atomicAdd(reinterpret_cast<unsigned long long *>(s.uncertified), 1ull);
+    }
+    keys[i] = key;
+  }
+  if (any_bad && s.bad) *s.bad = 1;
+  mk_sort<SP>(keys);
+  // ---- the price that occurs: realised for the day-ahead market and for the hour at hand, scenario 0's for the look-ahead hours ----
+  const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[lmk_index(s, st0, h, 0, hod, t)];
+  // ---- lowest price among the distinct points (the inserted p_min point takes it) ----
+  const bool has_min = keys[0] != kBidDrop && bid_key_power(keys[0]) == pmin;      // powers are >= p_min and ascending
+  long long lowest = 0x7fffffffffffffffll;
+  int n = 0;
+#pragma unroll
+  for (int i = 0; i < SP; ++i) {
+    const bool first = keys[i] != kBidDrop && (i == 0 || bid_key_power(keys[i]) != bid_key_power(keys[i ? i - 1 : 0]));
+    if (first) { lowest = min(lowest, bid_key_price(keys[i])); ++n; }
+  }
+  // ---- distinct points in order with the running maximum, cleared on the way ----
+  int32_t *out = curve + (size_t)g * (S + 1) * 2;
+  int pos = 0;
+  long long run = 0, cleared = 0;
+  auto emit = [&](long long U, long long M) {
+    run = pos == 0 ? M : max(run, M);
+    out[2 * pos] = (int32_t)U;
+    out[2 * pos + 1] = (int32_t)run;
+    if (pos == 0 || !s.price_taker || __ddiv_rn((double)run, 100.0) <= lmp) cleared = U;
+    ++pos;
+  };
+  if (!has_min) emit(pmin, n == 0 ? 0 : lowest);
+#pragma unroll
+  for (int i = 0; i < SP; ++i) {
+    const bool first = keys[i] != kBidDrop && (i == 0 || bid_key_power(keys[i]) != bid_key_power(keys[i ? i - 1 : 0]));
+    if (first) emit(bid_key_power(keys[i]), bid_key_price(keys[i]));
+  }
+  count[g] = pos;
+  for (int q = pos; q <= S; ++q) { out[2 * q] = 0; out[2 * q + 1] = 0; }
+  const double disp = __ddiv_rn((double)cleared, 100.0);
+  dispatch[g] = disp;
+  if (k < 0) {
+    s.da_prices[(size_t)b * 24 + t] = lmp;
+    return;
+  }
+  if (!has_tr) return;
+  // ---- the tracker's LP of this hour (what phase 1 of dsp_loop_update writes, with the cleared dispatch) ----
+  double *rlo = tr.rlo + (size_t)b * tr.m, *rhi = tr.rhi + (size_t)b * tr.m;
+  const double rhs = __dsub_rn(disp, tr.pt_const[t]);
+  rlo[tr.track_rows[t]] = rhs;
+  rhi[tr.track_rows[t]] = rhs;
+  if (t == 0) {
+    double *lb = tr.lb + (size_t)b * tr.n, *ub = tr.ub + (size_t)b * tr.n;
+    double c0 = tr.c0_base;
+    if (tr.wind_cols[0] >= 0) {
+      double avail_sum = 0.0;
+      for (int q = 0; q < tr.T; ++q) {
+        const double avail = mk_opaque(__dmul_rn(tr.wind_kw, s.cf_series[(st0 + h + q) % s.N]));
+        ub[tr.wind_cols[q]] = avail;
+        avail_sum = q ? __dadd_rn(avail_sum, avail) : avail;
+      }
+      c0 = __dadd_rn(c0, mk_opaque(__dmul_rn(tr.waste_per_kw, avail_sum)));
+    }
+    tr.c0[b] = c0;
+    for (int j = 0; j < tr.n_state; ++j) {
+      const double v = s.state[(size_t)b * tr.n_state + j];
+      lb[tr.state_init[j]] = v; ub[tr.state_init[j]] = v;
+    }
+  }
+}
+
+hipError_t launch_loop_market_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, int k, hipStream_t stream) {
+  const long long rows = (long long)st.B * st.S;
+  hipLaunchKernelGGL(loop_market_prepare_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, st, m, k);
+  return hipGetLastError();
+}
+
+hipError_t launch_loop_market_clear(const dsp_loop_market_state &st, const dsp_loop_market_model &m, const dsp_loop_model *tr, int k, int T,
+                                    double *dispatch, int32_t *curve, int32_t *count, hipStream_t stream) {
+  const long long lanes = (long long)st.B * T;
+  const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+  const dsp_loop_model trv = tr ? *tr : dsp_loop_model{};
+  const int has_tr = tr != nullptr;
+#define DSP_LMK_LAUNCH(SP) hipLaunchKernelGGL(loop_market_clear_kernel<SP>, grid, block, 0, stream, st, m, trv, has_tr, k, T, dispatch, curve, count)
+  if (st.S <= 1) DSP_LMK_LAUNCH(1);
+  else if (st.S <= 2) DSP_LMK_LAUNCH(2);
+  else if (st.S <= 4) DSP_LMK_LAUNCH(4);
+  else if (st.S <= 8) DSP_LMK_LAUNCH(8);
+  else DSP_LMK_LAUNCH(16);
+#undef DSP_LMK_LAUNCH
   return hipGetLastError();
 }
 

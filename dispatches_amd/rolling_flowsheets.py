@@ -12,8 +12,15 @@ written once over a small DESCRIPTOR of the flowsheet's rolling-horizon state:
 Everything per plant lives in HBM and is updated by device index operations; the solves go through the C ABI on device pointers
 (day-ahead: PDLP kernel; 4-h / 12-h LPs: in-wave simplex first); the steps of a day are captured into hipGraphs on the second day and
 replayed.  Power output and objective come from the flowsheet's own expressions as dense rows (P_T = PT x + PT_const), so nothing
-below knows a flowsheet's columns except through the descriptor.  The market is the stub of rolling.py (every offer clears at its
-maximum; day-ahead bids of day d at hour 0 of day d)."""
+below knows a flowsheet's columns except through the descriptor.  By default the market is the stub of rolling.py (every offer clears
+at its maximum; day-ahead bids of day d at hour 0 of day d).
+
+Stochastic mode (n_price_scenarios / forecaster="backcast" / market="price_taker"; the reference's nuclear double loop runs a Bidder with
+n_scenario = 3 on a Backcaster, nuclear_flowsheet_double_loop.ipynb): the semantics of rolling.py's stochastic mode over the descriptor.
+Every plant bids on S backcast scenarios (rows b * S + i of the bidding batches), the S solutions of a period become one bid curve that
+starts at the generator's p_min (400 MW for the nuclear unit, Bidder._assemble_bids), a price-taker market dispatches the plant along it,
+and the tracker follows the cleared dispatch.  `_day_ahead_step_stochastic` / `_hour_step_stochastic` are the executable specification as
+tensor operations; csrc/dsp_market.hip (dsp_loop_market_*) is the same arithmetic in two kernels, bit for bit."""
 from __future__ import annotations
 
 import numpy as np
@@ -73,6 +80,31 @@ class _Model:
     def power_output(self, x):
         return x @ self.PT.T + self.PT_const                              # [B, T] MW
 
+    def terms(self):
+        """P_T[t] = (x[a] ca + x[b] cb) + const_t as index / coefficient arrays [T, 2] (-1 / 0.0: no such term): the stochastic mode's
+        elementwise form of the power output, the one its kernels compute"""
+        PT = self.PT.cpu().numpy()
+        cols, coef = np.full((self.T, 2), -1, np.int64), np.zeros((self.T, 2))
+        for t in range(self.T):
+            nz = np.nonzero(PT[t])[0]
+            if len(nz) > 2:
+                raise ValueError("the stochastic mode takes power outputs of at most two columns per period")
+            cols[t, :len(nz)], coef[t, :len(nz)] = nz, PT[t, nz]
+        return cols, coef
+
+    def set_terms(self, dev):
+        import torch
+        cols, coef = self.terms()
+        t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+        used = cols >= 0
+        self.term_cols, self.term_coef = t(cols[used], torch.int64), t(coef[used], torch.float64)      # the objective entries the prices touch
+        self.term_t = t(np.nonzero(used)[0], torch.int64)
+        self.pt_a, self.pt_b = t(np.maximum(cols[:, 0], 0), torch.int64), t(np.maximum(cols[:, 1], 0), torch.int64)
+        self.pt_ca, self.pt_cb = t(coef[:, 0], torch.float64), t(coef[:, 1], torch.float64)
+        self.has_const = bool((self.PT_const != 0).any().item())
+        self.base_c0_t = torch.full((), self.base_c0, dtype=torch.float64, device=dev)
+        return cols
+
     def solve(self, B, hour=None):
         opts = self.opts if (hour is None or self.opts is None) else (self.opts_first if hour == 0 else self.opts_warm)
         self.out = self.dlp.solve(B, self.c, self.lb, self.ub, self.rlo if self.lp.m else None, self.rhi if self.lp.m else None,
@@ -124,20 +156,39 @@ def _templates(flowsheet, day_ahead_horizon, tracking_horizon):
 
 class BatchedDoubleLoop:
     def __init__(self, flowsheet, n_scenarios, device=0, first_scenario=0, day_ahead_horizon=48, tracking_horizon=4, lp_backend=None,
-                 use_graphs=True, use_fused=True, simplex_warm=True):
+                 use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
+                 market="stub"):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
-        descriptor (dsp_loop_update, include/dsp_hip.h) - the nuclear loop of 256 plants is launch-bound otherwise (21 ms per simulated day)."""
+        descriptor (dsp_loop_update, include/dsp_hip.h) - the nuclear loop of 256 plants is launch-bound otherwise (21 ms per simulated day).
+        n_price_scenarios, forecaster, max_historical_days, market: the STOCHASTIC mode, with the meaning and the validation of
+        BatchedWindBatteryDoubleLoop (rolling.py): forecaster="backcast" bids on S scenarios out of the D last days of the
+        plant's own circular series, market="price_taker" dispatches along the bid curve at the price that occurs ("stub": at its last
+        point).  The curves start at the generator's p_min.  The defaults are the deterministic loop, unchanged."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
+        self.S = S = int(n_price_scenarios)
+        self.D = D = int(max_historical_days)
+        if forecaster not in ("perfect", "backcast") or market not in ("stub", "price_taker"):
+            raise ValueError(f"forecaster is 'perfect' or 'backcast' and market 'stub' or 'price_taker', not {forecaster!r} / {market!r}")
+        if forecaster == "backcast" and not 1 <= S <= min(16, D):
+            raise ValueError(f"forecaster='backcast' needs 1 <= n_price_scenarios <= min(16, max_historical_days), not {S} (max_historical_days={D})")
+        if forecaster == "perfect" and S != 1:
+            raise ValueError("forecaster='perfect' knows one price scenario: n_price_scenarios must be 1")
+        self.forecaster, self.market = forecaster, market
+        self.stochastic = forecaster != "perfect" or market != "stub"
+        rows = B * S                                                       # rows of the bidding batches (plant b, scenario i: row b * S + i)
         self.dev = dev = torch.device("cuda", device) if lp_backend is None else torch.device("cpu")
         bidder, da_model, rt_model, tracker, d = _templates(flowsheet, day_ahead_horizon, tracking_horizon)
         tr_model = tracker.model
         self.bidder, self.tracker_template = bidder, tracker
         da_s, rt_s, cf_s = d["prices"]
         self.N = N = len(rt_s)
+        if self.stochastic and (24 * D > N or tracking_horizon > len(rt_model.HOUR) or not 24 <= len(da_model.HOUR) <= 48):
+            raise ValueError("the stochastic mode needs max_historical_days whole days inside the series, tracking_horizon <= the real-time "
+                             "horizon and a day-ahead horizon of 24 .. 48 periods")
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float64), device=dev)
         idx = lambda cols: torch.as_tensor(np.asarray(cols, np.int64), device=dev)
         self.da_series, self.rt_series = t(da_s), t(rt_s)
@@ -153,8 +204,8 @@ class BatchedDoubleLoop:
             f = getattr(model.block, fam)
             cols = [p["wind"].index for p in f["periods"]]
             return cols, f["wind_kw"], d["per_kw"], f["wind_kw"] * float(np.sum(cf_s[:len(cols)]))
-        mk = lambda model: _Model(model, fam, B, dev, device, power, d["init"](model.block), wind_of(model), lp_backend)
-        self.da, self.rt, self.tr = mk(da_model), mk(rt_model), mk(tr_model)
+        mk = lambda model, nb: _Model(model, fam, nb, dev, device, power, d["init"](model.block), wind_of(model), lp_backend)
+        self.da, self.rt, self.tr = mk(da_model, rows), mk(rt_model, rows), mk(tr_model, B)
         self.da.pda_cols, self.rt.pda_cols = idx(da_model.pda_cols), idx(rt_model.pda_cols)
         self.tr.track_rows = idx([tr_model.block.kept_row_index(r) for r in tr_model.tracking_rows])
         self.tr.state_real = d["real"](tr_model.block)
@@ -173,8 +224,23 @@ class BatchedDoubleLoop:
         self.simplex_warm = bool(simplex_warm) and lp_backend is None
         self._graphs, self._warm = {}, False
         self.use_fused = bool(use_fused) and lp_backend is None and self.rt.T <= 16 and self.tr.T <= 16 and len(self.scale) <= 2
+        if self.stochastic:
+            self.p_min_cents = int(round(float(bidder.bidding_model_object.model_data.p_min) * 100.0))     # Bidder._assemble_bids: p_min of the generator
+            for m in (self.da, self.rt):
+                cols = m.set_terms(dev)
+                if set(cols[cols >= 0].tolist()) & set(m.pda_cols.cpu().tolist()):
+                    raise ValueError("a column is both a term of the power output and day_ahead_power: the prices' objective entries would collide")
+            i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+            # curves (integer cents: power, price; `count` points each) and dispatches of the current day / hour: persistent, like everything a step touches
+            self.da_curve, self.da_count = i32(B, 24, S + 1, 2), i32(B, 24)
+            self.rt_curve, self.rt_count = i32(B, self.tr.T, S + 1, 2), i32(B, self.tr.T)
+            self.rt_dispatch = z(B, self.tr.T)
+            self.da_energy_mwh, self.offered_mwh = z(B), z(B)
+            self._hundred = torch.full((), 100.0, dtype=torch.float64, device=dev)
         if self.use_fused:
             self._fused_setup()
+            if self.stochastic:
+                self._market_setup()
 
     def _fused_setup(self):
         from .hip_solver import DspLoopModel, DspLoopState, load_library
@@ -220,6 +286,46 @@ class BatchedDoubleLoop:
         self._loop_state = st
         self._loop_rt = struct(self.rt, pda=self.rt.pda_cols.cpu().tolist())
         self._loop_tr = struct(self.tr, track=self.tr.track_rows.cpu().tolist(), real=self.tr.state_real)
+
+    def _market_setup(self):
+        from .hip_solver import DspLoopMarketModel, DspLoopMarketState
+        mk = DspLoopMarketState()
+        mk.B, mk.S, mk.D, mk.N = self.B, self.S, self.D, self.N
+        mk.backcast, mk.price_taker = int(self.forecaster == "backcast"), int(self.market == "price_taker")
+        for name in ("start", "hour", "da_series", "rt_series", "cf_series", "state", "da_offer", "da_prices", "bad", "uncertified"):
+            setattr(mk, name, getattr(self._loop_state, name))
+        mk.p_min_cents = self.p_min_cents
+
+        def struct(m):
+            w = DspLoopMarketModel()
+            w.c, w.lb, w.ub, w.base_c, w.x, w.c0 = (t.data_ptr() for t in (m.c, m.lb, m.ub, m.base_c, m.out["x"], m.c0))
+            w.status, w.flags = m.out["status"].data_ptr(), m.out["flags"].data_ptr()
+            w.n, w.T, w.n_state = m.lp.n, m.T, len(self.scale)
+            cols, coef = m.terms()
+            PTc, pda = m.PT_const.cpu().numpy(), m.pda_cols.cpu().tolist()
+            wind = m.wind[0].cpu().tolist() if m.wind is not None else []
+            for t in range(len(w.pda_cols)):
+                live = t < m.T
+                for e in range(2):
+                    w.pt_cols[t][e] = int(cols[t, e]) if live else -1
+                    w.pt_coef[t][e] = float(coef[t, e]) if live else 0.0
+                w.pt_const[t] = float(PTc[t]) if live else 0.0
+                w.pda_cols[t] = int(pda[t]) if live else -1
+                w.wind_cols[t] = int(wind[t]) if t < len(wind) else -1
+            for j in range(2):
+                w.state_init[j] = m.state_init[j] if j < len(m.state_init) else 0
+            w.wind_kw = m.wind[1] if m.wind is not None else 0.0
+            w.waste_per_kw = m.wind[2] if m.wind is not None else 0.0
+            w.c0_base = m.base_c0
+            return w
+        self._mk_state, self._mk_da, self._mk_rt = mk, struct(self.da), struct(self.rt)
+
+    def _market(self, fn, *args):
+        import ctypes as C
+        import torch
+        rc = fn(C.byref(self._mk_state), *args, C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"{fn.__name__} failed ({rc})")
 
     def _fused(self, phase, k):
         import ctypes as C
@@ -310,6 +416,163 @@ class BatchedDoubleLoop:
         self.energy_mwh += self.delivered
         self.hour_t += 1
 
+    # -- stochastic mode: backcast scenarios, bid curves from p_min, market clearing (semantics: rolling.py, generalised over the descriptor) --
+    def _forecast(self, series, T, hod):
+        """[B, S, T] price scenarios asked at hour-of-day `hod` of the current day: Backcaster._forecast over the D whole days before
+        the current day of every plant's own circular series (rolling.py::_forecast)"""
+        import torch
+        if self.forecaster == "perfect":
+            return self._window(series, T)[:, None, :]
+        D = self.D
+        d = torch.div(self.hour_t, 24, rounding_mode="floor")
+        i, t = torch.arange(self.S, device=self.dev)[:, None], torch.arange(T, device=self.dev)[None, :]
+        pos = (24 * (D - 1 - i) + hod + t) % (24 * D)
+        return series[(self.start[:, None, None] + 24 * (d - D) + pos[None]) % self.N]
+
+    def _rows(self, v):
+        """per-plant values [B, ...] -> per-row [B * S, ...] (a plant's S rows are adjacent)"""
+        return v if self.S == 1 else v.repeat_interleave(self.S, dim=0)
+
+    def _avail(self, m):
+        """wind availability of the window [B, T] and its sum accumulated in the order of t (the kernels' order: bit-identical constants)"""
+        cols, kw, per_kw = m.wind
+        avail = kw * self._window(self.cf_series, m.T)
+        total = avail[:, 0]
+        for t in range(1, m.T):
+            total = total + avail[:, t]
+        return cols, avail, per_kw * total
+
+    def _set_rows(self, m, da, rt):
+        """objective, state, wind and objective constant of the B * S rows of a bidding model on prices da, rt [B * S, T]:
+        c0 = (base_c0 - sum_t rt[t] PT_const[t]) + per_kw sum_t avail[t], both sums in the order of t; products rounded on their own"""
+        m.c[:, m.term_cols] = m.base_c[m.term_cols] - m.term_coef * rt[:, m.term_t]
+        m.c[:, m.pda_cols] = m.base_c[m.pda_cols] - (da - rt)
+        if m.has_const:                               # (an all-zero PT_const leaves base_c0 - 0 = base_c0: the loop is skipped, the value is the same)
+            psum = rt[:, 0] * m.PT_const[0]
+            for t in range(1, m.T):
+                psum = psum + rt[:, t] * m.PT_const[t]
+            c0 = m.base_c0_t - psum
+        else:
+            c0 = m.base_c0_t.expand(rt.shape[0])
+        for j, col in enumerate(m.state_init):
+            v = self._rows(self.state[:, j])
+            m.lb[:, col] = v
+            m.ub[:, col] = v
+        if m.wind is not None:
+            cols, avail, waste = self._avail(m)
+            m.ub[:, cols] = self._rows(avail)
+            c0 = c0 + self._rows(waste)
+        m.c0.copy_(c0)
+
+    def _set_tracker(self):
+        """the tracker's LP on the cleared dispatch: dispatch rows = dispatch - PT_const, state, wind, c0 = base_c0 + per_kw sum_t avail[t]"""
+        tr = self.tr
+        rhs = self.rt_dispatch - tr.PT_const
+        tr.rlo[:, tr.track_rows] = rhs
+        tr.rhi[:, tr.track_rows] = rhs
+        for j, col in enumerate(tr.state_init):
+            tr.lb[:, col] = self.state[:, j]
+            tr.ub[:, col] = self.state[:, j]
+        if tr.wind is not None:
+            cols, avail, waste = self._avail(tr)
+            tr.ub[:, cols] = avail
+            tr.c0.copy_(tr.base_c0 + waste)
+        else:
+            tr.c0.fill_(tr.base_c0)
+
+    def _curves(self, power, price, status):
+        """power, price [B, S, Tc]; status [B * S] -> (U, M [S + 1, B * Tc] int64 cents, count [B * Tc]) - workflow/market.py::plant_curves"""
+        import torch
+        from .workflow.market import plant_curves
+        B, S, Tc = power.shape
+        lanes = lambda a: a.expand(B, S, Tc).permute(1, 0, 2).reshape(S, B * Tc)
+        return plant_curves(torch, lanes(power), lanes(price), lanes((status == 0).reshape(B, S, 1)), p_min_cents=self.p_min_cents)
+
+    def _clear(self, U, M, count, lmp):
+        import torch
+        from .workflow.market import clear_curves
+        return clear_curves(torch, U, M, count, lmp.reshape(-1), self._hundred, price_taker=self.market == "price_taker").reshape(lmp.shape)
+
+    def _store_curves(self, curve, cnt, U, M, count):
+        import torch
+        B, Tc = cnt.shape
+        curve.copy_(torch.stack([U.t().reshape(B, Tc, self.S + 1), M.t().reshape(B, Tc, self.S + 1)], dim=3))
+        cnt.copy_(count.reshape(B, Tc))
+
+    def _day_ahead_step_stochastic(self):
+        """B * S day-ahead LPs (row b * S + i on scenario i's prices, plant b's state and wind, day_ahead_power free), one curve per
+        plant-hour from the S day_ahead_power values and day-ahead forecasts, cleared at the realised day-ahead price"""
+        import ctypes as C
+        import torch
+        m, B, S = self.da, self.B, self.S
+        if self.use_fused:
+            self._market(self._lib.dsp_loop_market_prepare, C.byref(self._mk_da), -1)
+        else:
+            da, rt = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T), self._forecast(self.rt_series, m.T, 0).expand(B, S, m.T)
+            self._set_rows(m, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
+            m.lb.index_fill_(1, m.pda_cols, 0.0)
+            m.ub.index_fill_(1, m.pda_cols, float("inf"))
+        out = m.solve(B * S)
+        if self.use_fused:                            # (status / flags of the solve: folded into bad / uncertified by the kernel)
+            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_da), None, -1, 24, C.c_void_p(self.da_offer.data_ptr()),
+                         C.c_void_p(self.da_curve.data_ptr()), C.c_void_p(self.da_count.data_ptr()))
+        else:
+            self._check(out)
+            power = out["x"][:, m.pda_cols[:24]].reshape(B, S, 24)
+            U, M, count = self._curves(power, self._forecast(self.da_series, 24, 0), out["status"])
+            realised = self._window(self.da_series, 24)
+            self.da_offer.copy_(self._clear(U, M, count, realised))
+            self.da_prices.copy_(realised)
+            self._store_curves(self.da_curve, self.da_count, U, M, count)
+        self.da_energy_mwh += self.da_offer.sum(1)
+        last = torch.gather(self.da_curve[:, :, :, 0], 2, (self.da_count.to(torch.int64) - 1)[:, :, None])[:, :, 0]
+        self.offered_mwh += (last.to(torch.float64) / self._hundred).sum(1)
+
+    def _hour_step_stochastic(self, k):
+        """Hour k of the day: B * S real-time LPs (scenario i = the real-time backcast at hour-of-day k; realised day-ahead prices and the
+        cleared day_ahead_power inside the cleared day), one curve per plant and tracked period from (P_T, real-time forecast), cleared
+        at the realised price for the hour at hand and at scenario 0's forecast for the look-ahead periods; tracking of the cleared
+        dispatch (B LPs); state hand-off, revenue and clock as _hour_step."""
+        import ctypes as C
+        import torch
+        m, tr, B, S = self.rt, self.tr, self.B, self.S
+        hour = k if self.simplex_warm else None
+        if self.use_fused:
+            self._market(self._lib.dsp_loop_market_prepare, C.byref(self._mk_rt), k)
+            m.solve(B * S, hour=hour)
+            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_rt), C.byref(self._loop_tr), k, tr.T, C.c_void_p(self.rt_dispatch.data_ptr()),
+                         C.c_void_p(self.rt_curve.data_ptr()), C.c_void_p(self.rt_count.data_ptr()))
+            tr.solve(B, hour=hour)
+            self._fused(2, k)                         # delivered power, state hand-off, revenue, energy, clock: unchanged (reads the tracker only)
+            return
+        rt_f = self._forecast(self.rt_series, m.T, k).expand(B, S, m.T)
+        da_f = self._forecast(self.da_series, m.T, k).expand(B, S, m.T).clone()
+        known = min(m.T, 24 - k)                                          # hours of the horizon inside the cleared day
+        da_f[:, :, :known] = self.da_prices[:, None, k:k + known]
+        self._set_rows(m, da_f.reshape(B * S, m.T), rt_f.reshape(B * S, m.T))
+        m.lb.index_fill_(1, m.pda_cols, 0.0)
+        m.ub.index_fill_(1, m.pda_cols, float("inf"))
+        m.lb[:, m.pda_cols[:known]] = self._rows(self.da_offer[:, k:k + known])
+        m.ub[:, m.pda_cols[:known]] = self._rows(self.da_offer[:, k:k + known])
+        out = m.solve(B * S, hour=hour) if m.opts is not None else m.solve(B * S)
+        self._check(out)
+        x, Tc = out["x"], tr.T
+        power = (x[:, m.pt_a[:Tc]] * m.pt_ca[:Tc] + x[:, m.pt_b[:Tc]] * m.pt_cb[:Tc]) + m.PT_const[:Tc]      # two-term elementwise form, not a matmul
+        U, M, count = self._curves(power.reshape(B, S, Tc), rt_f[:, :, :Tc], out["status"])
+        rt0 = self._window(self.rt_series, 1)
+        self.rt_dispatch.copy_(self._clear(U, M, count, torch.cat([rt0, rt_f[:, 0, 1:Tc]], dim=1)))
+        self._store_curves(self.rt_curve, self.rt_count, U, M, count)
+        self._set_tracker()
+        out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
+        self._check(out)
+        x, rt0 = out["x"], rt0[:, 0]
+        self.delivered.copy_(tr.power_output(x)[:, 0])
+        for j, col in enumerate(tr.state_real):
+            self.state[:, j] = torch.round(x[:, col] * self.scale[j]) / self._scale_t[j]
+        self.revenue += self.delivered * rt0 + self.da_offer[:, k] * (self.da_prices[:, k] - rt0)
+        self.energy_mwh += self.delivered
+        self.hour_t += 1
+
     def _run(self, key, fn):
         import torch
         if not self.use_graphs or not self._warm:
@@ -326,14 +589,14 @@ class BatchedDoubleLoop:
     # -- the loop ----------------------------------------------------------------------------------------------------------------------
     def day_ahead(self):
         self.day_start = self.hour
-        self._run("da", self._day_ahead_step)
-        self.solves += self.B
+        self._run("da", self._day_ahead_step_stochastic if self.stochastic else self._day_ahead_step)
+        self.solves += self.B * self.S
         return self.da_offer.clone()
 
     def hour_step(self):
         k = self.hour - self.day_start
-        self._run(k, lambda: self._hour_step(k))
-        self.solves += 2 * self.B
+        self._run(k, (lambda: self._hour_step_stochastic(k)) if self.stochastic else (lambda: self._hour_step(k)))
+        self.solves += self.B * self.S + self.B
         self.hour += 1
         return self.delivered.clone()
 
@@ -347,7 +610,12 @@ class BatchedDoubleLoop:
         for t in (self.state, self.revenue, self.energy_mwh, self.delivered, self.da_offer, self.da_prices, self.hour_t, self.uncertified):
             t.zero_()
         self.bad.zero_()
+        if self.stochastic:
+            self.da_energy_mwh.zero_(), self.offered_mwh.zero_()
         self.hour = self.solves = 0
 
     def results(self):
-        return dict(obj=self.revenue, energy_mwh=self.energy_mwh, state=self.state), not bool(self.bad.item())
+        res = dict(obj=self.revenue, energy_mwh=self.energy_mwh, state=self.state)
+        if self.stochastic:                            # what the market left on the table: offered (the curves' last points) against cleared
+            res.update(da_energy_mwh=self.da_energy_mwh, offered_mwh=self.offered_mwh)
+        return res, not bool(self.bad.item())

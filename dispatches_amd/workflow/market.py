@@ -22,15 +22,16 @@ def clear_price_taker(U, M, lmp):
     return float(U[covered].max()) if covered.any() else float(U[0])
 
 
-def plant_curves(torch, power, price, ok):
+def plant_curves(torch, power, price, ok, p_min_cents=0):
     """power, price: [S, L] float64 - the S scenarios' pairs of L independent (plant, period) lanes; ok [S, L] bool (False: the row's
-    solve was not optimal, it offers nothing).  The arithmetic of `bid_curves.sorted_pairs` + `bid_curves.curves` with p_min = 0, per
-    lane: integer cents, pairs with negative power dropped, sorted by power ascending / price descending, the highest price per distinct
-    power, the point (0, lowest price seen or 0) in front if no pair sits at 0, running maximum over the prices.
+    solve was not optimal, it offers nothing); p_min_cents: the generator's minimum power in integer cents (0 for the wind + battery
+    plant, 40000 for the 400 MW nuclear unit).  The arithmetic of `bid_curves.sorted_pairs` + `bid_curves.curves`, per lane: integer
+    cents, pairs with power below p_min dropped, sorted by power ascending / price descending, the highest price per distinct power, the
+    point (p_min, lowest price seen or 0) in front if no pair sits at p_min, running maximum over the prices.
     -> (U [S + 1, L], M [S + 1, L] int64 cents, unused slots 0; count [L])."""
     S, L = power.shape
     pc, cc = cents(torch, power), cents(torch, price)
-    keep = (pc >= 0) & ok & torch.isfinite(power) & torch.isfinite(price)
+    keep = (pc >= p_min_cents) & ok & torch.isfinite(power) & torch.isfinite(price)
     key = torch.where(keep, pc * (1 << 32) + ((_KEY_OFF - 1) - cc), torch.full_like(pc, _DROP))
     key, _ = torch.sort(key, dim=0)
     live = key != _DROP
@@ -39,7 +40,7 @@ def plant_curves(torch, power, price, ok):
     first = live.clone()
     first[1:] &= ps[1:] != ps[:-1]
     n = first.sum(dim=0)
-    ins = ~(first & (ps == 0)).any(dim=0)                                   # no point at p_min = 0: one is inserted in front
+    ins = ~(first & (ps == p_min_cents)).any(dim=0)                         # no point at p_min: one is inserted in front
     lowest = torch.where(first, cs, torch.full_like(cs, _DROP)).min(dim=0).values
     lowest = torch.where(n == 0, torch.zeros_like(lowest), lowest)
     dest = torch.where(first, torch.cumsum(first.to(torch.int64), dim=0) - 1 + ins.to(torch.int64), torch.full_like(ps, S + 1))
@@ -48,7 +49,7 @@ def plant_curves(torch, power, price, ok):
     U.scatter_(0, dest, ps)
     M.scatter_(0, dest, cs)
     U, M = U[:S + 1], M[:S + 1]
-    U[0] = torch.where(ins, torch.zeros_like(U[0]), U[0])
+    U[0] = torch.where(ins, torch.full_like(U[0], p_min_cents), U[0])
     M[0] = torch.where(ins, lowest, M[0])
     count = n + ins.to(torch.int64)
     valid = torch.arange(S + 1, device=power.device)[:, None] < count[None, :]

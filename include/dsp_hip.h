@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 13
+#define DSP_VERSION 14
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -493,6 +493,64 @@ int dsp_market_prepare(const dsp_market_state *st, const dsp_market_model *m, in
  *   does what phase 1 of dsp_wb_rolling_update does for the tracker: dispatch -> its dispatch rows, realised state, wind availability, c0. */
 int dsp_market_clear(const dsp_market_state *st, const dsp_market_model *m, const dsp_wb_model *tr, int32_t k, int32_t T,
                      double *dispatch, int32_t *curve, int32_t *count, void *hipStream);
+
+/* The same stochastic mode for ANY flowsheet of the reference, described instead of hard-coded (ABI 14; dispatches_amd/rolling_flowsheets.py:
+ * BatchedDoubleLoop with n_price_scenarios / forecaster / market).  Scenarios, rows (b * S + i), curve and clearing rules are those of
+ * dsp_market_* above, generalised three ways:
+ *   power of a real-time pair   P_T[t] = (x[a] * pt_coef[t][0] + x[b] * pt_coef[t][1]) + pt_const[t]   (a term with column -1 is left out;
+ *                               day-ahead pairs: x[pda_cols[t]]);
+ *   minimum power               pairs whose rounded power is below p_min_cents are dropped and the point in front of a curve that has no
+ *                               pair AT p_min_cents is (p_min_cents, lowest price or 0): Bidder._assemble_bids with the generator's
+ *                               model_data.p_min (400 MW for the nuclear unit, 0 for the wind plants);
+ *   state and wind              n_state <= 2 state columns fixed to state[b][j]; wind columns optional (wind_cols[0] = -1: none).
+ * Objective of row r on its scenario's prices (every product rounded on its own, sums in the order of t):
+ *   c[col] = base_c[col] - pt_coef * rt[t] on the P_T columns, c[pda_cols[t]] = base_c[..] - (da[t] - rt[t]),
+ *   c0[r]  = (c0_base - sum_t rt[t] * pt_const[t]) + waste_per_kw * sum_t (wind availability of period t)    (last term with wind only). */
+typedef struct dsp_loop_market_model {
+  double *c, *lb, *ub;                 /* [B * S][n] per-row vectors of a bidding LP                                              */
+  const double *base_c;                /* [n] cost vector without prices                                                          */
+  const double *x;                     /* [B * S][n] solution of its last solve                                                   */
+  double *c0;                          /* [B * S] objective constant of every row                                                 */
+  const int32_t *status, *flags;       /* [B * S] outputs of its last solve (flags may be NULL)                                   */
+  int32_t n, T, n_state, reserved;     /* columns, horizon (T <= DSP_MARKET_MAX_T), state columns (<= 2)                          */
+  int32_t pt_cols[DSP_MARKET_MAX_T][2];/* -1 = no such term                                                                       */
+  double  pt_coef[DSP_MARKET_MAX_T][2];
+  double  pt_const[DSP_MARKET_MAX_T];
+  int32_t pda_cols[DSP_MARKET_MAX_T];  /* day-ahead power column of every period                                                  */
+  int32_t wind_cols[DSP_MARKET_MAX_T]; /* wind production column of every period; wind_cols[0] = -1: the flowsheet has no wind    */
+  int32_t state_init[2];               /* columns fixed to the realised state                                                     */
+  double wind_kw, c0_base, waste_per_kw;
+} dsp_loop_market_model;
+
+typedef struct dsp_loop_market_state {
+  int32_t B, S, D, N;                  /* as dsp_market_state                                                                     */
+  int32_t backcast, price_taker;
+  const int64_t *start;                /* [B]                                                                                     */
+  const int64_t *hour;                 /* [1] the clock (read only here)                                                          */
+  const double *da_series, *rt_series, *cf_series;   /* [N] (cf_series NULL without wind)                                         */
+  const double *state;                 /* [B][n_state] realised state (NULL with n_state = 0)                                     */
+  const double *da_offer;              /* [B][24] cleared day-ahead dispatch of the current day (read by prepare, k >= 0)         */
+  double *da_prices;                   /* [B][24] realised day-ahead prices of the current day (written by the day-ahead clearing) */
+  uint8_t *bad;                        /* [1] or NULL                                                                             */
+  int64_t *uncertified;                /* [1] or NULL                                                                             */
+  int64_t p_min_cents;                 /* minimum power of the generator in integer cents (>= 0)                                  */
+} dsp_loop_market_state;
+
+/* Scenario fan-out of bidding model `m` (B * S rows), one lane per row.  k = -1: the day-ahead LP (day_ahead_power free in every period);
+ * k = 0 .. 23: the real-time LP of hour-of-day k (day-ahead prices and day_ahead_power of the min(T, 24 - k) periods inside the cleared
+ * day from da_prices / da_offer).  DSP_ERR_INVALID, nothing launched and nothing written, for: a NULL buffer that is used; S, D, T,
+ * n_state or k out of range; a used column index outside [0, n); n_state > 0 with a NULL state; wind columns with a NULL cf_series. */
+int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, int32_t k, void *hipStream);
+
+/* Curve + clearing, one lane per (plant, period t < T), keys in registers as dsp_market_clear.  Outputs as dsp_market_clear: dispatch
+ * [B][T] MW, curve [B][T][S + 1][2] int32 cents, count [B][T]; status / flags of the bidding solve are folded into bad / uncertified.
+ * k = -1 (T <= 24): day-ahead pairs, cleared at the realised day-ahead price, which goes to da_prices; `tr` must be NULL.
+ * k = 0 .. 23 (T <= DSP_LOOP_MAX_T): real-time pairs, cleared at the realised price (t = 0) / scenario 0's forecast (t >= 1).  With `tr`
+ * (the tracking model of B rows, tr->T == T) the lanes also write the tracker's LP of this hour: dispatch rows = dispatch[t] -
+ * tr->pt_const[t], state columns, wind availability and c0 = c0_base + waste_per_kw * sum_t availability (as phase 1 of dsp_loop_update).
+ * Refusals as dsp_loop_market_prepare, and for a dispatch row of `tr` outside [0, tr->m). */
+int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market_model *m, const dsp_loop_model *tr, int32_t k, int32_t T,
+                          double *dispatch, int32_t *curve, int32_t *count, void *hipStream);
 
 /* Introspection */
 int dsp_get_dims(const dsp_handle *h, int32_t *n, int32_t *m, int64_t *nnz);
