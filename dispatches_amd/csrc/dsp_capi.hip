@@ -457,6 +457,31 @@ int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market
   return DSP_OK;
 }
 
+// parametrized bidding of the descriptor loop (dsp_param.hip): every index and pointer a lane would use is checked here
+int dsp_loop_param_step(const dsp_loop_param_state *st, const dsp_loop_model *tr, int32_t phase, int32_t k, void *hipStream) {
+  if (!st || !tr || st->B < 1 || st->N < 24 || tr->T < 1 || tr->T > DSP_LOOP_MAX_T) return DSP_ERR_INVALID;
+  if (phase < 0 || phase > 2 || (phase == 0 ? k != -1 : (k < 0 || k > 23))) return DSP_ERR_INVALID;
+  if (!st->start || !st->hour || !st->da_series || !st->rt_series || !st->da_cf_series || !st->rt_cf_series || !st->bid_price ||
+      !st->storage_mw)
+    return DSP_ERR_INVALID;
+  if (phase == 0) {
+    if (!st->da_offer || !st->da_prices || !st->da_curve || !st->da_count) return DSP_ERR_INVALID;
+  } else if (phase == 1) {
+    if (!st->rt_dispatch || !st->rt_curve || !st->rt_count) return DSP_ERR_INVALID;
+    if (tr->n < 1 || tr->m < 1 || tr->n_state < 0 || tr->n_state > 2 || !tr->lb || !tr->ub || !tr->rlo || !tr->rhi || !tr->c0) return DSP_ERR_INVALID;
+    if (tr->n_state > 0 && !st->state) return DSP_ERR_INVALID;
+    for (int j = 0; j < tr->n_state; ++j)
+      if (!market_col_ok(tr->state_init[j], tr->n)) return DSP_ERR_INVALID;
+    const bool wind = tr->wind_cols[0] >= 0;
+    for (int t = 0; t < tr->T; ++t)
+      if (!market_col_ok(tr->track_rows[t], tr->m) || (wind && !market_col_ok(tr->wind_cols[t], tr->n))) return DSP_ERR_INVALID;
+  } else {
+    if (!st->h2_kg || !tr->x || tr->n < 1 || !market_col_ok(st->pem_col, tr->n)) return DSP_ERR_INVALID;
+  }
+  HIP_TRY(launch_loop_param_step(*st, *tr, (int)phase, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
 void dsp_default_options(dsp_options *o) {
   if (!o) return;
   std::memset(o, 0, sizeof(*o));

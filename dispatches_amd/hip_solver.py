@@ -108,10 +108,10 @@ class DspLoopState(C.Structure):
 EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_step", "dsp_get_dims",
                     "dsp_get_scaling", "dsp_destroy", "dsp_strerror", "dsp_last_hip_error", "dsp_version",
                     "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
-                    "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear")
+                    "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step")
 
 
-ABI_VERSION = 14         # DSP_VERSION of the include/dsp_hip.h these structures mirror
+ABI_VERSION = 15         # DSP_VERSION of the include/dsp_hip.h these structures mirror
 
 
 BID_MAX_HOURS, BID_MAX_SCENARIOS = 64, 16384
@@ -162,6 +162,17 @@ class DspLoopMarketState(C.Structure):
                 ("da_series", C.c_void_p), ("rt_series", C.c_void_p), ("cf_series", C.c_void_p),
                 ("state", C.c_void_p), ("da_offer", C.c_void_p), ("da_prices", C.c_void_p),
                 ("bad", C.c_void_p), ("uncertified", C.c_void_p), ("p_min_cents", C.c_int64)]
+
+
+class DspLoopParamState(C.Structure):
+    """include/dsp_hip.h: dsp_loop_param_state (ABI 15) - parametrized two-tier bidding of the descriptor loop"""
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("price_taker", C.c_int32), ("battery", C.c_int32),
+                ("start", C.c_void_p), ("hour", C.c_void_p),
+                ("da_series", C.c_void_p), ("rt_series", C.c_void_p), ("da_cf_series", C.c_void_p), ("rt_cf_series", C.c_void_p),
+                ("state", C.c_void_p), ("bid_price", C.c_void_p), ("storage_mw", C.c_void_p), ("wind_mw", C.c_double),
+                ("da_offer", C.c_void_p), ("da_prices", C.c_void_p), ("da_curve", C.c_void_p), ("da_count", C.c_void_p),
+                ("rt_dispatch", C.c_void_p), ("rt_curve", C.c_void_p), ("rt_count", C.c_void_p),
+                ("h2_kg", C.c_void_p), ("h2_mul", C.c_double), ("h2_div", C.c_double), ("pem_col", C.c_int32), ("reserved", C.c_int32)]
 
 
 def source_hash(root: Optional[str] = None) -> Optional[str]:
@@ -251,6 +262,8 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_market_prepare.restype = C.c_int
     lib.dsp_loop_market_clear.argtypes = [C.POINTER(DspLoopMarketState), C.POINTER(DspLoopMarketModel), C.POINTER(DspLoopModel), i32, i32, vp, vp, vp, vp]
     lib.dsp_loop_market_clear.restype = C.c_int
+    lib.dsp_loop_param_step.argtypes = [C.POINTER(DspLoopParamState), C.POINTER(DspLoopModel), i32, i32, vp]
+    lib.dsp_loop_param_step.restype = C.c_int
     lib.dsp_last_hip_error.restype = C.c_int
     if path == _LIB_PATH:
         _lib = lib

@@ -20,7 +20,14 @@ n_scenario = 3 on a Backcaster, nuclear_flowsheet_double_loop.ipynb): the semant
 Every plant bids on S backcast scenarios (rows b * S + i of the bidding batches), the S solutions of a period become one bid curve that
 starts at the generator's p_min (400 MW for the nuclear unit, Bidder._assemble_bids), a price-taker market dispatches the plant along it,
 and the tracker follows the cleared dispatch.  `_day_ahead_step_stochastic` / `_hour_step_stochastic` are the executable specification as
-tensor operations; csrc/dsp_market.hip (dsp_loop_market_*) is the same arithmetic in two kernels, bit for bit."""
+tensor operations; csrc/dsp_market.hip (dsp_loop_market_*) is the same arithmetic in two kernels, bit for bit.
+
+Parametrized mode (bidder="parametrized", bid_price, storage_mw; the reference's wind + PEM study run_double_loop_PEM.py bids with a
+PEMParametrizedBidder on a PerfectForecaster, run_double_loop_battery_parametrized.py with a FixedParametrizedBidder): no bidding LP.
+The curve of a (plant, period) is a closed form of the available wind w, the plant's storage size and its bid price - the pairs
+(0, 0), (max(0, w - storage_mw), 0), (p_max, bid_price) through the same curve and clearing rules -, day-ahead on the day-ahead capacity
+factors, hourly on the real-time ones; only the tracking LPs are solved.  `_day_ahead_step_parametrized` / `_hour_step_parametrized`
+are the specification as tensor operations; csrc/dsp_param.hip (dsp_loop_param_step) is the same arithmetic in one kernel per step."""
 from __future__ import annotations
 
 import numpy as np
@@ -28,6 +35,33 @@ import numpy as np
 from . import scenarios
 from .hip_solver import DeviceLP, default_options
 from .rolling import _NoSolver
+
+
+def exact_fma(torch, a, b, c):
+    """round(a * b + c) with ONE rounding, as tensor operations (float64; no overflow / underflow in a * b): the fused multiply-add of
+    the kernels, which torch does not offer.  Boldo & Melquiond, "Emulation of a FMA and correctly rounded sums: proved algorithms using
+    rounding to odd" (IEEE TC 2008), algorithm Fma-emul: a * b = uh + ul exactly (Dekker's product on Veltkamp splits, as
+    bid_curves.cents), (th, tl) = TwoSum(c, ul), (vh, vl) = TwoSum(uh, th), z = tl + vl rounded TO ODD, result = vh + z."""
+    def split(v):
+        t = v * 134217729.0                            # 2^27 + 1
+        hi = t - (t - v)
+        return hi, v - hi
+
+    def two_sum(x, y):
+        s = x + y
+        yy = s - x
+        return s, (x - (s - yy)) + (y - yy)
+    uh = a * b
+    (ah, al), (bh, bl) = split(a), split(b)
+    ul = al * bl - (((uh - ah * bh) - al * bh) - ah * bl)
+    th, tl = two_sum(c, ul)
+    vh, vl = two_sum(uh, th)
+    z, err = two_sum(tl, vl)
+    # to odd: an inexact sum whose last mantissa bit is even moves one ulp towards the lost part (integer step on the bit pattern)
+    bits = z.view(torch.int64)
+    step = torch.where((err > 0) == (z > 0), torch.ones_like(bits), -torch.ones_like(bits))
+    z = torch.where((err != 0) & ((bits & 1) == 0), bits + step, bits).view(torch.float64)
+    return vh + z
 
 
 def _dense_rows(block, family, n, hours):
@@ -38,7 +72,7 @@ def _dense_rows(block, family, n, hours):
 class _Model:
     """One of the three LPs on the device, described without reference to a flowsheet."""
 
-    def __init__(self, model, block_family, B, dev, device_index, power_output, state_init, wind, lp_backend=None):
+    def __init__(self, model, block_family, B, dev, device_index, power_output, state_init, wind, lp_backend=None, solved=True):
         import torch
         self.lp = model.lp
         self.T = len(model.HOUR)
@@ -68,7 +102,7 @@ class _Model:
             self.opts_warm, self.opts_first = DspOptions.from_buffer_copy(self.opts), DspOptions.from_buffer_copy(self.opts)
             if self.T <= 16:                       # hourly LPs: the simplex starts from the previous hour's basis (dsp_options::simplex_warm)
                 self.opts_warm.simplex_warm, self.opts_first.simplex_warm = 1, 2
-            self.dlp = DeviceLP(self.lp, device_index, self.opts)
+            self.dlp = DeviceLP(self.lp, device_index, self.opts) if solved else None      # (parametrized mode never solves its bidding templates)
             m = max(self.lp.m, 1)
             self.out = dict(x=torch.zeros((B, n), dtype=torch.float64, device=dev), y=torch.zeros((B, m), dtype=torch.float64, device=dev),
                             obj=torch.zeros(B, dtype=torch.float64, device=dev), status=torch.zeros(B, dtype=torch.int32, device=dev),
@@ -127,6 +161,7 @@ def _templates(flowsheet, day_ahead_horizon, tracking_horizon):
                     init=lambda blk: [getattr(blk, fam)["soc_init"].index, getattr(blk, fam)["thr_init"].index],
                     real=lambda blk: [getattr(blk, fam)["periods"][0]["state_of_charge"].index, getattr(blk, fam)["periods"][0]["energy_throughput"].index])
         prices = (np.clip(s["da_lmp"], 0.0, cap), np.clip(s["rt_lmp"], 0.0, cap), s["rt_cf"])
+        desc["da_cf"] = s["da_cf"]
     elif flowsheet == "wind_pem":
         series, stride, cap = "rts_gmlc_303.npz", 37, 500.0
         bidder, da = scenarios.wind_pem_batch(1, day_ahead_horizon, _NoSolver(), series=series, stride=stride)
@@ -135,7 +170,7 @@ def _templates(flowsheet, day_ahead_horizon, tracking_horizon):
         tr_obj = mo.__class__(mo.model_data, wind_capacity_factors=list(s["rt_cf"][:tracking_horizon]), wind_pmax_mw=mo._wind_pmax_mw,
                               pem_pmax_mw=mo._pem_pmax_mw)
         fam = "windPEM"
-        desc = dict(family=fam, per_kw=1.0, decimals=[], init=lambda blk: [], real=lambda blk: [])
+        desc = dict(family=fam, per_kw=1.0, decimals=[], init=lambda blk: [], real=lambda blk: [], da_cf=s["da_cf"])
         prices = (np.clip(s["da_lmp"], 0.0, cap), np.clip(s["rt_lmp"], 0.0, cap), s["rt_cf"])
     elif flowsheet == "nuclear":
         stride = 29
@@ -157,7 +192,7 @@ def _templates(flowsheet, day_ahead_horizon, tracking_horizon):
 class BatchedDoubleLoop:
     def __init__(self, flowsheet, n_scenarios, device=0, first_scenario=0, day_ahead_horizon=48, tracking_horizon=4, lp_backend=None,
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
-                 market="stub"):
+                 market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -165,7 +200,12 @@ class BatchedDoubleLoop:
         n_price_scenarios, forecaster, max_historical_days, market: the STOCHASTIC mode, with the meaning and the validation of
         BatchedWindBatteryDoubleLoop (rolling.py): forecaster="backcast" bids on S scenarios out of the D last days of the
         plant's own circular series, market="price_taker" dispatches along the bid curve at the price that occurs ("stub": at its last
-        point).  The curves start at the generator's p_min.  The defaults are the deterministic loop, unchanged."""
+        point).  The curves start at the generator's p_min.  The defaults are the deterministic loop, unchanged.
+        plant_windows: int array [B]; plant b sees the year that starts at hour (stride * (first_scenario + plant_windows[b])) mod N
+        (None: arange(B)), so that several plants - parameter points of a sweep - can share one window.
+        bidder="parametrized" (wind_pem, wind_battery; perfect forecaster, one scenario, tracking_horizon <= 16), bid_price [$/MWh] and
+        storage_mw [MW of PEM / battery the upper tier covers], scalars or arrays [B]: the two-tier closed-form curves of the
+        reference's parametrized bidders instead of bidding LPs (module docstring); market "price_taker" or "stub"."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
@@ -177,16 +217,46 @@ class BatchedDoubleLoop:
             raise ValueError(f"forecaster='backcast' needs 1 <= n_price_scenarios <= min(16, max_historical_days), not {S} (max_historical_days={D})")
         if forecaster == "perfect" and S != 1:
             raise ValueError("forecaster='perfect' knows one price scenario: n_price_scenarios must be 1")
+        if bidder not in ("lp", "parametrized"):
+            raise ValueError(f"bidder is 'lp' or 'parametrized', not {bidder!r}")
+        self.parametrized = bidder == "parametrized"
+        if self.parametrized:
+            if flowsheet not in ("wind_pem", "wind_battery"):
+                raise ValueError(f"bidder='parametrized' is the wind + PEM / wind + battery bidders' rule: not for {flowsheet!r}")
+            if S != 1 or forecaster != "perfect":
+                raise ValueError("bidder='parametrized' bids on a perfect forecast: forecaster='perfect', n_price_scenarios=1")
+            if not 1 <= int(tracking_horizon) <= 16:
+                raise ValueError("bidder='parametrized' takes a tracking_horizon of 1 .. 16 periods")
+
+            def per_plant(v, name):
+                if v is None:
+                    raise ValueError(f"bidder='parametrized' needs {name}")
+                a = np.asarray(v, np.float64)
+                if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != B):
+                    raise ValueError(f"{name} is a scalar or an array of length {B}, not of shape {a.shape}")
+                if not np.isfinite(a).all() or (a < 0).any() or (a >= 2.0e7).any():         # (2e7: the range of the cent arithmetic, bid_curves.cents)
+                    raise ValueError(f"{name} must be finite, >= 0 and below 2e7")
+                return np.broadcast_to(a, (B,)).copy()
+            bid_price, storage_mw = per_plant(bid_price, "bid_price"), per_plant(storage_mw, "storage_mw")
+        elif bid_price is not None or storage_mw is not None:
+            raise ValueError("bid_price and storage_mw belong to bidder='parametrized'")
+        if plant_windows is None:
+            plant_windows = np.arange(B)
+        else:
+            plant_windows = np.asarray(plant_windows)
+            if plant_windows.shape != (B,) or plant_windows.dtype.kind not in "iu":
+                raise ValueError(f"plant_windows is an int array of length {B}")
+            plant_windows = plant_windows.astype(np.int64)
         self.forecaster, self.market = forecaster, market
-        self.stochastic = forecaster != "perfect" or market != "stub"
-        rows = B * S                                                       # rows of the bidding batches (plant b, scenario i: row b * S + i)
+        self.stochastic = forecaster != "perfect" or market != "stub" or self.parametrized
+        rows = 1 if self.parametrized else B * S                           # rows of the bidding batches (plant b, scenario i: row b * S + i; no bidding LP is solved in parametrized mode: one template row)
         self.dev = dev = torch.device("cuda", device) if lp_backend is None else torch.device("cpu")
         bidder, da_model, rt_model, tracker, d = _templates(flowsheet, day_ahead_horizon, tracking_horizon)
         tr_model = tracker.model
         self.bidder, self.tracker_template = bidder, tracker
         da_s, rt_s, cf_s = d["prices"]
         self.N = N = len(rt_s)
-        if self.stochastic and (24 * D > N or tracking_horizon > len(rt_model.HOUR) or not 24 <= len(da_model.HOUR) <= 48):
+        if self.stochastic and not self.parametrized and (24 * D > N or tracking_horizon > len(rt_model.HOUR) or not 24 <= len(da_model.HOUR) <= 48):
             raise ValueError("the stochastic mode needs max_historical_days whole days inside the series, tracking_horizon <= the real-time "
                              "horizon and a day-ahead horizon of 24 .. 48 periods")
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float64), device=dev)
@@ -194,7 +264,7 @@ class BatchedDoubleLoop:
         self.da_series, self.rt_series = t(da_s), t(rt_s)
         self.cf_series = t(cf_s) if cf_s is not None else None
         self.stride = d["stride"]
-        self.start = idx((d["stride"] * (first_scenario + np.arange(B))) % N)
+        self.start = idx((d["stride"] * (first_scenario + plant_windows)) % N)
         power = bidder.bidding_model_object.power_output
         fam = d["family"]
 
@@ -204,8 +274,8 @@ class BatchedDoubleLoop:
             f = getattr(model.block, fam)
             cols = [p["wind"].index for p in f["periods"]]
             return cols, f["wind_kw"], d["per_kw"], f["wind_kw"] * float(np.sum(cf_s[:len(cols)]))
-        mk = lambda model, nb: _Model(model, fam, nb, dev, device, power, d["init"](model.block), wind_of(model), lp_backend)
-        self.da, self.rt, self.tr = mk(da_model, rows), mk(rt_model, rows), mk(tr_model, B)
+        mk = lambda model, nb, solved=True: _Model(model, fam, nb, dev, device, power, d["init"](model.block), wind_of(model), lp_backend, solved)
+        self.da, self.rt, self.tr = mk(da_model, rows, not self.parametrized), mk(rt_model, rows, not self.parametrized), mk(tr_model, B)
         self.da.pda_cols, self.rt.pda_cols = idx(da_model.pda_cols), idx(rt_model.pda_cols)
         self.tr.track_rows = idx([tr_model.block.kept_row_index(r) for r in tr_model.tracking_rows])
         self.tr.state_real = d["real"](tr_model.block)
@@ -224,7 +294,9 @@ class BatchedDoubleLoop:
         self.simplex_warm = bool(simplex_warm) and lp_backend is None
         self._graphs, self._warm = {}, False
         self.use_fused = bool(use_fused) and lp_backend is None and self.rt.T <= 16 and self.tr.T <= 16 and len(self.scale) <= 2
-        if self.stochastic:
+        if self.parametrized:
+            self._parametrized_setup(d, bid_price, storage_mw, tr_model, fam)
+        elif self.stochastic:
             self.p_min_cents = int(round(float(bidder.bidding_model_object.model_data.p_min) * 100.0))     # Bidder._assemble_bids: p_min of the generator
             for m in (self.da, self.rt):
                 cols = m.set_terms(dev)
@@ -239,8 +311,63 @@ class BatchedDoubleLoop:
             self._hundred = torch.full((), 100.0, dtype=torch.float64, device=dev)
         if self.use_fused:
             self._fused_setup()
-            if self.stochastic:
+            if self.parametrized:
+                self._param_setup()
+            elif self.stochastic:
                 self._market_setup()
+
+    def _parametrized_setup(self, d, bid_price, storage_mw, tr_model, fam):
+        import torch
+        from .flowsheets import parameters as prm
+        dev, B, Tc = self.dev, self.B, self.tr.T
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float64), device=dev)
+        self.p_min_cents = 0
+        self.bid_price, self.storage_mw = t(bid_price), t(storage_mw)
+        self.da_cf_series = t(d["da_cf"])
+        if len(d["da_cf"]) != self.N or self.N < 24:
+            raise ValueError("the day-ahead capacity factors must cover the series, and the series a day")
+        self.wind_mw = float(self.bidder.bidding_model_object._wind_pmax_mw)       # the host bidders' wind_mw
+        self.battery = self.flowsheet == "wind_battery"                            # p_max = max(w, storage_mw) (FixedParametrizedBidder)
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        self.da_curve, self.da_count = i32(B, 24, 4, 2), i32(B, 24)                # three pairs: at most 3 points in the S + 1 = 4 slots of plant_curves
+        self.rt_curve, self.rt_count = i32(B, Tc, 4, 2), i32(B, Tc)
+        self.rt_dispatch = z(B, Tc)
+        self.da_energy_mwh, self.offered_mwh = z(B), z(B)
+        self._hundred = torch.full((), 100.0, dtype=torch.float64, device=dev)
+        cols, coef = self.tr.terms()                                               # P_T[0] of the tracker as phase 2 of dsp_loop_update reads it
+        used = cols[0] >= 0
+        self.tr.p0_cols = torch.as_tensor(cols[0][used], dtype=torch.int64, device=dev)
+        self.tr.p0_coef = t(coef[0][used])
+        self.h2_kg = None
+        if self.flowsheet == "wind_pem":                                           # MultiPeriodWindPEM._h2_kg_per_hr of the implemented hour
+            self.h2_kg = z(B)
+            self.pem_col = int(getattr(tr_model.block, fam)["periods"][0]["pem_elec"].index)
+            self._h2_mul = float(prm.pem_electricity_to_mol)
+            self._h2_div = torch.full((), float(prm.h2_mols_per_kg), dtype=torch.float64, device=dev)
+
+    def _param_setup(self):
+        from .hip_solver import DspLoopParamState
+        ps = DspLoopParamState()
+        ps.B, ps.N, ps.price_taker, ps.battery = self.B, self.N, int(self.market == "price_taker"), int(self.battery)
+        for name in ("start", "hour", "da_series", "rt_series", "state", "da_offer", "da_prices"):
+            setattr(ps, name, getattr(self._loop_state, name))
+        ps.da_cf_series, ps.rt_cf_series = self.da_cf_series.data_ptr(), self.cf_series.data_ptr()
+        ps.bid_price, ps.storage_mw, ps.wind_mw = self.bid_price.data_ptr(), self.storage_mw.data_ptr(), self.wind_mw
+        ps.da_curve, ps.da_count = self.da_curve.data_ptr(), self.da_count.data_ptr()
+        ps.rt_dispatch, ps.rt_curve, ps.rt_count = self.rt_dispatch.data_ptr(), self.rt_curve.data_ptr(), self.rt_count.data_ptr()
+        if self.h2_kg is not None:
+            ps.h2_kg, ps.pem_col = self.h2_kg.data_ptr(), self.pem_col
+            ps.h2_mul, ps.h2_div = self._h2_mul, float(self._h2_div.item())
+        self._param_state = ps
+
+    def _param(self, phase, k):
+        import ctypes as C
+        import torch
+        rc = self._lib.dsp_loop_param_step(C.byref(self._param_state), C.byref(self._loop_tr), phase, k,
+                                           C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"dsp_loop_param_step failed ({rc})")
 
     def _fused_setup(self):
         from .hip_solver import DspLoopModel, DspLoopState, load_library
@@ -573,6 +700,89 @@ class BatchedDoubleLoop:
         self.energy_mwh += self.delivered
         self.hour_t += 1
 
+    # -- parametrized mode: two-tier closed-form curves (workflow/parametrized_bidder.py), no bidding LP ---------------------------------
+    def _param_curves(self, cf):
+        """cf [B, Tc] capacity factors -> (U, M [4, B * Tc] int64 cents, count): the pairs (0, 0), (max(0, w - storage), 0), (p_max, bid)
+        as three "scenarios" of plant_curves with p_min = 0"""
+        import torch
+        from .workflow.market import plant_curves
+        w = cf * self.wind_mw
+        storage = self.storage_mw[:, None]
+        lo = torch.clamp(w - storage, min=0.0)
+        hi = torch.maximum(w, storage.expand_as(w)) if self.battery else w
+        zero = torch.zeros_like(w)
+        power = torch.stack([zero, lo, hi]).reshape(3, -1)
+        price = torch.stack([zero, zero, self.bid_price[:, None].expand_as(w)]).reshape(3, -1)
+        return plant_curves(torch, power, price, torch.ones_like(power, dtype=torch.bool), p_min_cents=0)
+
+    def _store_param_curves(self, curve, cnt, U, M, count):
+        import torch
+        B, Tc = cnt.shape
+        curve.copy_(torch.stack([U.t().reshape(B, Tc, 4), M.t().reshape(B, Tc, 4)], dim=3))
+        cnt.copy_(count.reshape(B, Tc))
+
+    def _day_ahead_step_parametrized(self):
+        """one curve per plant-hour from the day-ahead capacity factors, cleared at the realised day-ahead price; no LP"""
+        import torch
+        if self.use_fused:
+            self._param(0, -1)
+        else:
+            U, M, count = self._param_curves(self._window(self.da_cf_series, 24))
+            realised = self._window(self.da_series, 24)
+            self.da_offer.copy_(self._clear(U, M, count, realised))
+            self.da_prices.copy_(realised)
+            self._store_param_curves(self.da_curve, self.da_count, U, M, count)
+        self.da_energy_mwh += self.da_offer.sum(1)
+        last = torch.gather(self.da_curve[:, :, :, 0], 2, (self.da_count.to(torch.int64) - 1)[:, :, None])[:, :, 0]
+        self.offered_mwh += (last.to(torch.float64) / self._hundred).sum(1)
+
+    def _param_dispatch(self, k):
+        """the first half of hour k: curves of the tracked periods, their clearing, and the tracker's LP on the cleared dispatch"""
+        if self.use_fused:
+            self._param(1, k)
+            return
+        tr = self.tr
+        U, M, count = self._param_curves(self._window(self.cf_series, tr.T))
+        self.rt_dispatch.copy_(self._clear(U, M, count, self._window(self.rt_series, tr.T)))
+        self._store_param_curves(self.rt_curve, self.rt_count, U, M, count)
+        self._set_tracker()
+
+    def _param_hydrogen(self, k):
+        """h2_kg += MultiPeriodWindPEM._h2_kg_per_hr(PEM electricity of the implemented hour) (a tensor divisor: cf. clear_curves)"""
+        if self.h2_kg is None:
+            return
+        if self.use_fused:
+            self._param(2, k)
+        else:
+            self.h2_kg += ((self.tr.out["x"][:, self.pem_col] * self._h2_mul) / self._h2_div) * 3600.0
+
+    def _hour_step_parametrized(self, k):
+        """Hour k of the day: one curve per plant and tracked period from the real-time capacity factors, cleared at the real-time price
+        of that period (the perfect forecast IS the realised price; the day-ahead dispatch plays no part, as in the reference); tracking
+        of the cleared dispatch (B LPs); hydrogen of the implemented hour; state hand-off, revenue and clock as _hour_step."""
+        import torch
+        tr, B = self.tr, self.B
+        hour = k if self.simplex_warm else None
+        self._param_dispatch(k)
+        out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
+        self._param_hydrogen(k)
+        if self.use_fused:
+            self._fused(2, k)                         # delivered power, state hand-off, revenue, energy, clock: unchanged (reads the tracker only)
+            return
+        self._check(out)
+        x, rt0 = out["x"], self._window(self.rt_series, 1)[:, 0]
+        # delivered power and revenue in the arithmetic of phase 2 of dsp_loop_update, so that this form and the kernels agree bit for
+        # bit on the sums too: P_T[0] = fma(cb, x[b], fma(ca, x[a], const)), revenue += fma(delivered, rt, da_offer * (da - rt))
+        p = tr.PT_const[0].expand(B)
+        for e in range(tr.p0_cols.shape[0]):
+            p = exact_fma(torch, tr.p0_coef[e].expand(B), x[:, tr.p0_cols[e]], p)
+        self.delivered.copy_(p)
+        for j, col in enumerate(tr.state_real):
+            self.state[:, j] = torch.round(x[:, col] * self.scale[j]) / self._scale_t[j]
+        self.revenue += exact_fma(torch, self.delivered, rt0, self.da_offer[:, k] * (self.da_prices[:, k] - rt0))
+        self.energy_mwh += self.delivered
+        self.hour_t += 1
+
     def _run(self, key, fn):
         import torch
         if not self.use_graphs or not self._warm:
@@ -589,14 +799,21 @@ class BatchedDoubleLoop:
     # -- the loop ----------------------------------------------------------------------------------------------------------------------
     def day_ahead(self):
         self.day_start = self.hour
+        if self.parametrized:
+            self._run("da", self._day_ahead_step_parametrized)
+            return self.da_offer.clone()
         self._run("da", self._day_ahead_step_stochastic if self.stochastic else self._day_ahead_step)
         self.solves += self.B * self.S
         return self.da_offer.clone()
 
     def hour_step(self):
         k = self.hour - self.day_start
-        self._run(k, (lambda: self._hour_step_stochastic(k)) if self.stochastic else (lambda: self._hour_step(k)))
-        self.solves += self.B * self.S + self.B
+        if self.parametrized:
+            self._run(k, lambda: self._hour_step_parametrized(k))
+            self.solves += self.B
+        else:
+            self._run(k, (lambda: self._hour_step_stochastic(k)) if self.stochastic else (lambda: self._hour_step(k)))
+            self.solves += self.B * self.S + self.B
         self.hour += 1
         return self.delivered.clone()
 
@@ -612,10 +829,14 @@ class BatchedDoubleLoop:
         self.bad.zero_()
         if self.stochastic:
             self.da_energy_mwh.zero_(), self.offered_mwh.zero_()
+        if self.parametrized and self.h2_kg is not None:
+            self.h2_kg.zero_()
         self.hour = self.solves = 0
 
     def results(self):
         res = dict(obj=self.revenue, energy_mwh=self.energy_mwh, state=self.state)
         if self.stochastic:                            # what the market left on the table: offered (the curves' last points) against cleared
             res.update(da_energy_mwh=self.da_energy_mwh, offered_mwh=self.offered_mwh)
+        if self.parametrized and self.h2_kg is not None:
+            res["h2_kg"] = self.h2_kg
         return res, not bool(self.bad.item())

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 14
+#define DSP_VERSION 15
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -551,6 +551,46 @@ int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_mark
  * Refusals as dsp_loop_market_prepare, and for a dispatch row of `tr` outside [0, tr->m). */
 int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market_model *m, const dsp_loop_model *tr, int32_t k, int32_t T,
                           double *dispatch, int32_t *curve, int32_t *count, void *hipStream);
+
+/* Parametrized two-tier bidding in the descriptor loop (ABI 15; dispatches_amd/rolling_flowsheets.py: BatchedDoubleLoop with
+ * bidder="parametrized").  The reference's wind + PEM and wind + battery sweeps bid without an LP (PEM_parametrized_bidder.py:50-122,
+ * battery_parametrized_bidder.py:47-123): with w = wind_mw * capacity factor of the period, the pairs of a (plant, period) are
+ *   (0, 0), (max(0, w - storage_mw[b]), 0), (p_max, bid_price[b]),   p_max = w (wind + PEM) or max(w, storage_mw[b]) (battery != 0).
+ * They become a curve by the rules of dsp_loop_market_clear with S = 3 and p_min = 0 (integer cents, the highest price per distinct
+ * power, running maximum: 1 .. 3 points in a slot of 4) and are cleared the same way (price taker: the last point whose price the LMP
+ * covers; stub: the last point).  Three pairs need no sort: the curve is a closed form of the three cent values.
+ * bid_price and storage_mw must be finite and >= 0, the series finite, start[b] in [0, N): device data, not checked by the entry point. */
+typedef struct dsp_loop_param_state {
+  int32_t B, N;                        /* plants (>= 1), length of the series (>= 24)                                             */
+  int32_t price_taker, battery;        /* 0 / 1: market (0 = stub), p_max rule (1 = max(w, storage_mw): wind + battery)           */
+  const int64_t *start;                /* [B] first hour of every plant's year (several plants may share one)                     */
+  const int64_t *hour;                 /* [1] the clock (read only here)                                                          */
+  const double *da_series, *rt_series; /* [N] day-ahead / real-time prices                                                        */
+  const double *da_cf_series, *rt_cf_series;         /* [N] day-ahead / real-time capacity factors                                */
+  const double *state;                 /* [B][n_state] realised state (NULL with n_state = 0)                                     */
+  const double *bid_price, *storage_mw;              /* [B] the two parameters of every plant                                     */
+  double wind_mw;                      /* w = wind_mw * capacity factor                                                           */
+  double *da_offer, *da_prices;        /* [B][24] written by phase 0                                                              */
+  int32_t *da_curve, *da_count;        /* [B][24][4][2] cents (power, price; unused slots 0), [B][24]                             */
+  double *rt_dispatch;                 /* [B][T] written by phase 1                                                               */
+  int32_t *rt_curve, *rt_count;        /* [B][T][4][2], [B][T]                                                                    */
+  double *h2_kg;                       /* [B] or NULL (no electrolyser): += ((x[pem_col] * h2_mul) / h2_div) * 3600 in phase 2    */
+  double h2_mul, h2_div;
+  int32_t pem_col, reserved;           /* column of the tracker holding the first period's PEM electricity                        */
+} dsp_loop_param_state;
+
+/* phase 0 (k = -1), one lane per (plant, hour of 24): day-ahead curves on da_cf_series, cleared at the realised day-ahead price ->
+ *          da_offer, da_prices, da_curve, da_count.  `tr` is not touched (only tr->T is checked).
+ * phase 1 (k = 0 .. 23), one lane per (plant, period t < tr->T): real-time curves on rt_cf_series, cleared at the real-time price of
+ *          period t -> rt_dispatch, rt_curve, rt_count; the tracker's LP of this hour as dsp_loop_market_clear writes it (dispatch
+ *          rows = dispatch - tr->pt_const[t]; by the lane of period 0: state columns, wind upper bounds, c0).
+ * phase 2 (k = 0 .. 23), one lane per plant, after the tracking solve: the hydrogen of the implemented hour -> h2_kg.  Hand-off,
+ *          revenue and clock stay with phase 2 of dsp_loop_update.
+ * DSP_ERR_INVALID, nothing launched and nothing written, for: B < 1; N < 24; tr->T outside 1 .. DSP_LOOP_MAX_T; a NULL series, start,
+ * hour, parameter array or output of the phase; phase 1: a dispatch row outside [0, tr->m), a wind column (when wind_cols[0] >= 0) or a
+ * state column outside [0, tr->n), n_state outside 0 .. 2 or > 0 with a NULL state, NULL rlo / rhi / lb / ub / c0; phase 2: NULL
+ * h2_kg or tr->x, pem_col outside [0, tr->n); a phase outside 0 .. 2 or a k that does not belong to it. */
+int dsp_loop_param_step(const dsp_loop_param_state *st, const dsp_loop_model *tr, int32_t phase, int32_t k, void *hipStream);
 
 /* Introspection */
 int dsp_get_dims(const dsp_handle *h, int32_t *n, int32_t *m, int64_t *nnz);
