@@ -264,9 +264,10 @@ __device__ __forceinline__ void loop_state_and_wind(const dsp_loop_state &s, con
     lb[m.state_init[j]] = v; ub[m.state_init[j]] = v;
   }
   if (m.wind_cols[0] >= 0) {
+    const double kw = m.wind_kw_plant ? m.wind_kw_plant[b] : m.wind_kw;     // per-plant size (ABI 16) at the site of the scalar
     double sum = 0.0;
     for (int t = 0; t < m.T; ++t) {
-      const double avail = m.wind_kw * s.cf_series[(st0 + h + t) % s.N];
+      const double avail = kw * s.cf_series[(st0 + h + t) % s.N];
       ub[m.wind_cols[t]] = avail;
       sum += avail;
     }
@@ -283,7 +284,7 @@ __global__ void __launch_bounds__(256) loop_update_kernel(dsp_loop_state s, dsp_
     const dsp_loop_model &m = rt;
     const int known = min(m.T, 24 - k);
     double *c = m.c + (size_t)b * m.n, *lb = m.lb + (size_t)b * m.n, *ub = m.ub + (size_t)b * m.n;
-    double c0 = m.c0_base;
+    double c0 = m.c0_base_plant ? m.c0_base_plant[b] : m.c0_base;
     for (int t = 0; t < m.T; ++t) {
       const double rtp = win(s.rt_series, t);
       const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : win(s.da_series, t);
@@ -305,7 +306,7 @@ __global__ void __launch_bounds__(256) loop_update_kernel(dsp_loop_state s, dsp_
       rlo[tr.track_rows[t]] = rhs;
       rhi[tr.track_rows[t]] = rhs;
     }
-    loop_state_and_wind(s, tr, b, h, st0, tr.c0_base);
+    loop_state_and_wind(s, tr, b, h, st0, tr.c0_base_plant ? tr.c0_base_plant[b] : tr.c0_base);
   } else {
     loop_check(s, tr, b);
     const double *x = tr.x + (size_t)b * tr.n;
@@ -339,6 +340,10 @@ int dsp_loop_update(const dsp_loop_state *st, const dsp_loop_model *rt, const ds
       tr->T > DSP_LOOP_MAX_T || rt->n_state < 0 || rt->n_state > 2 || tr->n_state != rt->n_state || !rt->c0 || !tr->c0 ||
       ((rt->wind_cols[0] >= 0 || tr->wind_cols[0] >= 0) && !st->cf_series))
     return DSP_ERR_INVALID;
+  // per-plant sizes (ABI 16): both pointers or neither on each model, the two models together, only with wind columns
+  if (!rt->wind_kw_plant != !rt->c0_base_plant || !tr->wind_kw_plant != !tr->c0_base_plant || !rt->wind_kw_plant != !tr->wind_kw_plant ||
+      (rt->wind_kw_plant && (rt->wind_cols[0] < 0 || tr->wind_cols[0] < 0)))
+    return DSP_ERR_INVALID;
   if (st->B == 0) return DSP_OK;
   hipStream_t s = (hipStream_t)hipStream;
   hipLaunchKernelGGL(loop_update_kernel, dim3((st->B + 255) / 256), dim3(256), 0, s, *st, *rt, *tr, (int)phase, (int)k);
@@ -366,6 +371,11 @@ static bool market_state_ok(const dsp_market_state *st) {
   return st->start && st->hour && st->da_series && st->rt_series;
 }
 static bool market_col_ok(int32_t col, int32_t n) { return col >= 0 && col < n; }
+// per-plant sizes (ABI 16): both pointers or neither, and only on a model that has wind columns
+static bool plant_sizes_ok(const double *wind_kw_plant, const double *c0_base_plant, int32_t wind_col0) {
+  if (!wind_kw_plant != !c0_base_plant) return false;
+  return !wind_kw_plant || wind_col0 >= 0;
+}
 
 int dsp_market_prepare(const dsp_market_state *st, const dsp_market_model *m, int32_t k, void *hipStream) {
   if (!market_state_ok(st) || !m || k < -1 || k > 23 || m->n < 1 || m->T < 1 || m->T > DSP_MARKET_MAX_T) return DSP_ERR_INVALID;
@@ -419,6 +429,7 @@ int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_mark
     if (!market_col_ok(m->state_init[j], m->n)) return DSP_ERR_INVALID;
   const bool wind = m->wind_cols[0] >= 0;
   if (wind && !st->cf_series) return DSP_ERR_INVALID;
+  if (!plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return DSP_ERR_INVALID;
   for (int t = 0; t < m->T; ++t) {
     if (!market_col_ok(m->pda_cols[t], m->n) || (wind && !market_col_ok(m->wind_cols[t], m->n))) return DSP_ERR_INVALID;
     for (int e = 0; e < 2; ++e)
@@ -434,6 +445,8 @@ int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market
   if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < -1 || k > 23 || T < 1 || T > m->T) return DSP_ERR_INVALID;
   if (!m->x || !m->status || !dispatch || !curve || !count) return DSP_ERR_INVALID;
   if (k < 0 ? (T > 24 || !st->da_prices || tr) : T > DSP_LOOP_MAX_T) return DSP_ERR_INVALID;
+  if (!plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return DSP_ERR_INVALID;
+  if (tr && (!plant_sizes_ok(tr->wind_kw_plant, tr->c0_base_plant, tr->wind_cols[0]) || !tr->wind_kw_plant != !m->wind_kw_plant)) return DSP_ERR_INVALID;
   for (int t = 0; t < T; ++t) {
     if (k < 0) {
       if (!market_col_ok(m->pda_cols[t], m->n)) return DSP_ERR_INVALID;
@@ -461,6 +474,7 @@ int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market
 int dsp_loop_param_step(const dsp_loop_param_state *st, const dsp_loop_model *tr, int32_t phase, int32_t k, void *hipStream) {
   if (!st || !tr || st->B < 1 || st->N < 24 || tr->T < 1 || tr->T > DSP_LOOP_MAX_T) return DSP_ERR_INVALID;
   if (phase < 0 || phase > 2 || (phase == 0 ? k != -1 : (k < 0 || k > 23))) return DSP_ERR_INVALID;
+  if (tr->wind_kw_plant || tr->c0_base_plant) return DSP_ERR_INVALID;      // the parametrized bidders take one wind size (wind_mw)
   if (!st->start || !st->hour || !st->da_series || !st->rt_series || !st->da_cf_series || !st->rt_cf_series || !st->bid_price ||
       !st->storage_mw)
     return DSP_ERR_INVALID;

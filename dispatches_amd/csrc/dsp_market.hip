@@ -226,6 +226,8 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
   const int hod = k < 0 ? 0 : k;
   const int known = k < 0 ? 0 : min(m.T, 24 - k);
   const bool wind = m.wind_cols[0] >= 0;
+  const double kw = m.wind_kw_plant ? m.wind_kw_plant[b] : m.wind_kw;       // per-plant sizes (ABI 16): row r belongs to plant b = r / S
+  const double c0_base = m.c0_base_plant ? m.c0_base_plant[b] : m.c0_base;
   double *c = m.c + (size_t)r * m.n, *lb = m.lb + (size_t)r * m.n, *ub = m.ub + (size_t)r * m.n;
   double avail_sum = 0.0, price_sum = 0.0;
   for (int t = 0; t < m.T; ++t) {
@@ -242,7 +244,7 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
     const double pc = mk_opaque(__dmul_rn(rtp, m.pt_const[t]));
     price_sum = t ? __dadd_rn(price_sum, pc) : pc;
     if (wind) {
-      const double avail = mk_opaque(__dmul_rn(m.wind_kw, s.cf_series[(st0 + h + t) % s.N]));     // capacity factors: the realised window
+      const double avail = mk_opaque(__dmul_rn(kw, s.cf_series[(st0 + h + t) % s.N]));     // capacity factors: the realised window
       ub[m.wind_cols[t]] = avail;
       avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
     }
@@ -250,7 +252,7 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
     lb[pda] = fix;
     ub[pda] = t < known ? fix : INFINITY;
   }
-  double c0 = mk_opaque(__dsub_rn(m.c0_base, price_sum));
+  double c0 = mk_opaque(__dsub_rn(c0_base, price_sum));
   if (wind) c0 = __dadd_rn(c0, mk_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
   m.c0[r] = c0;
   for (int j = 0; j < m.n_state; ++j) {
@@ -347,11 +349,12 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
   rhi[tr.track_rows[t]] = rhs;
   if (t == 0) {
     double *lb = tr.lb + (size_t)b * tr.n, *ub = tr.ub + (size_t)b * tr.n;
-    double c0 = tr.c0_base;
+    double c0 = tr.c0_base_plant ? tr.c0_base_plant[b] : tr.c0_base;
     if (tr.wind_cols[0] >= 0) {
+      const double kw = tr.wind_kw_plant ? tr.wind_kw_plant[b] : tr.wind_kw;
       double avail_sum = 0.0;
       for (int q = 0; q < tr.T; ++q) {
-        const double avail = mk_opaque(__dmul_rn(tr.wind_kw, s.cf_series[(st0 + h + q) % s.N]));
+        const double avail = mk_opaque(__dmul_rn(kw, s.cf_series[(st0 + h + q) % s.N]));
         ub[tr.wind_cols[q]] = avail;
         avail_sum = q ? __dadd_rn(avail_sum, avail) : avail;
       }

@@ -93,7 +93,7 @@ class DspLoopModel(C.Structure):
                 ("pda_cols", C.c_int32 * 16), ("track_rows", C.c_int32 * 16), ("wind_cols", C.c_int32 * 16),
                 ("state_init", C.c_int32 * 2), ("state_real", C.c_int32 * 2),
                 ("wind_kw", C.c_double), ("c0_base", C.c_double), ("waste_per_kw", C.c_double),
-                ("status", C.c_void_p), ("flags", C.c_void_p)]
+                ("status", C.c_void_p), ("flags", C.c_void_p), ("wind_kw_plant", C.c_void_p), ("c0_base_plant", C.c_void_p)]
 
 
 class DspLoopState(C.Structure):
@@ -111,7 +111,7 @@ EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_
                     "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step")
 
 
-ABI_VERSION = 15         # DSP_VERSION of the include/dsp_hip.h these structures mirror
+ABI_VERSION = 16         # DSP_VERSION of the include/dsp_hip.h these structures mirror
 
 
 BID_MAX_HOURS, BID_MAX_SCENARIOS = 64, 16384
@@ -152,7 +152,8 @@ class DspLoopMarketModel(C.Structure):
                 ("n", C.c_int32), ("T", C.c_int32), ("n_state", C.c_int32), ("reserved", C.c_int32),
                 ("pt_cols", (C.c_int32 * 2) * MARKET_MAX_T), ("pt_coef", (C.c_double * 2) * MARKET_MAX_T), ("pt_const", C.c_double * MARKET_MAX_T),
                 ("pda_cols", C.c_int32 * MARKET_MAX_T), ("wind_cols", C.c_int32 * MARKET_MAX_T), ("state_init", C.c_int32 * 2),
-                ("wind_kw", C.c_double), ("c0_base", C.c_double), ("waste_per_kw", C.c_double)]
+                ("wind_kw", C.c_double), ("c0_base", C.c_double), ("waste_per_kw", C.c_double),
+                ("wind_kw_plant", C.c_void_p), ("c0_base_plant", C.c_void_p)]
 
 
 class DspLoopMarketState(C.Structure):

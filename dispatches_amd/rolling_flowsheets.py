@@ -27,7 +27,14 @@ PEMParametrizedBidder on a PerfectForecaster, run_double_loop_battery_parametriz
 The curve of a (plant, period) is a closed form of the available wind w, the plant's storage size and its bid price - the pairs
 (0, 0), (max(0, w - storage_mw), 0), (p_max, bid_price) through the same curve and clearing rules -, day-ahead on the day-ahead capacity
 factors, hourly on the real-time ones; only the tracking LPs are solved.  `_day_ahead_step_parametrized` / `_hour_step_parametrized`
-are the specification as tensor operations; csrc/dsp_param.hip (dsp_loop_param_step) is the same arithmetic in one kernel per step."""
+are the specification as tensor operations; csrc/dsp_param.hip (dsp_loop_param_step) is the same arithmetic in one kernel per step.
+
+Per-plant sizes (wind_mw, battery_mw, battery_mwh with the LP bidder; the reference's run_double_loop_battery.py takes --wind_pmax,
+--battery_pmax and --battery_energy_capacity and its study runs one job per size point): in these flowsheets a size is never a matrix
+coefficient.  The wind size is the upper bound of the wind columns (wind_kw[b] * capacity factor, every step) and two objective
+constants (curtailment, fixed O&M); the battery's power and energy limits are static column / row bounds written once.  So a batch of
+DIFFERENT plants shares one template - built at the batch's largest sizes, see `_check_template` - and the kernels read two arrays
+[B] where they read two scalars (dsp_loop_model / dsp_loop_market_model: wind_kw_plant, c0_base_plant)."""
 from __future__ import annotations
 
 import numpy as np
@@ -90,6 +97,7 @@ class _Model:
         PT, PT_const = _dense_rows(model.block, power_output, n, model.HOUR)
         self.PT, self.PT_const = t(PT), t(PT_const)                       # [T, n], [T]
         self.state_init = [int(c) for c in state_init]                    # columns fixed to the realised state
+        self.kw_plant = self.c0_plant = None                              # per-plant sizes: wind kW [B, 1], objective constant [B] (set_plant_sizes)
         self.wind = None
         if wind is not None:                                              # (columns, kW, curtailment cost per kW, template availability sum)
             cols, kw, per_kw, template_sum = wind
@@ -113,6 +121,17 @@ class _Model:
 
     def power_output(self, x):
         return x @ self.PT.T + self.PT_const                              # [B, T] MW
+
+    def set_plant_sizes(self, wind_kw, c0_base, dev):
+        """wind_kw, c0_base: float64 arrays [B] per PLANT, computed once on the host - the tensor form and the kernels read these very
+        arrays instead of the scalars wind[1] / base_c0"""
+        import torch
+        self.kw_plant = torch.as_tensor(np.ascontiguousarray(wind_kw, np.float64), device=dev)[:, None]
+        self.c0_plant = torch.as_tensor(np.ascontiguousarray(c0_base, np.float64), device=dev)
+
+    def kw(self):
+        """the wind size as the window's factor: the scalar, or [B, 1] per plant"""
+        return self.wind[1] if self.kw_plant is None else self.kw_plant
 
     def terms(self):
         """P_T[t] = (x[a] ca + x[b] cb) + const_t as index / coefficient arrays [T, 2] (-1 / 0.0: no such term): the stochastic mode's
@@ -146,16 +165,22 @@ class _Model:
         return self.out
 
 
-def _templates(flowsheet, day_ahead_horizon, tracking_horizon):
-    """(bidder, day-ahead model, real-time model, tracker, descriptor) built ONCE through the product's own model objects (B = 1)."""
+_WIND_BATTERY_SIZES = dict(wind_mw=200.0, battery_mw=25.0, battery_mwh=100.0)      # the plant of the reference's wind + battery double loop
+
+
+def _templates(flowsheet, day_ahead_horizon, tracking_horizon, sizes=None):
+    """(bidder, day-ahead model, real-time model, tracker, descriptor) built ONCE through the product's own model objects (B = 1).
+    sizes: dict(wind_mw, battery_mw, battery_mwh) [wind_pem: wind_mw] of the template plant, None = the flowsheet's default plant."""
     from .workflow import Tracker
     if flowsheet == "wind_battery":
         series, stride, cap = "rts_gmlc_309.npz", 17, 500.0
-        bidder, da = scenarios.wind_battery_batch(1, day_ahead_horizon, _NoSolver(), series=series, stride=stride)
+        z = _WIND_BATTERY_SIZES if sizes is None else sizes
+        bidder, da = scenarios.wind_battery_batch(1, day_ahead_horizon, _NoSolver(), series=series, stride=stride, wind_mw=z["wind_mw"],
+                                                  batt_mw=z["battery_mw"], batt_mwh=z["battery_mwh"])
         s = scenarios.load_series(series)
         mo = bidder.bidding_model_object
-        tr_obj = mo.__class__(model_data=mo.model_data, wind_capacity_factors=list(s["rt_cf"][:tracking_horizon]), wind_pmax_mw=200.0,
-                              battery_pmax_mw=25.0, battery_energy_capacity_mwh=100.0)
+        tr_obj = mo.__class__(model_data=mo.model_data, wind_capacity_factors=list(s["rt_cf"][:tracking_horizon]), wind_pmax_mw=z["wind_mw"],
+                              battery_pmax_mw=z["battery_mw"], battery_energy_capacity_mwh=z["battery_mwh"])
         fam = "windBattery"
         desc = dict(family=fam, per_kw=mo.wind_waste_penalty * 1e-3, decimals=[2, 2],
                     init=lambda blk: [getattr(blk, fam)["soc_init"].index, getattr(blk, fam)["thr_init"].index],
@@ -164,7 +189,8 @@ def _templates(flowsheet, day_ahead_horizon, tracking_horizon):
         desc["da_cf"] = s["da_cf"]
     elif flowsheet == "wind_pem":
         series, stride, cap = "rts_gmlc_303.npz", 37, 500.0
-        bidder, da = scenarios.wind_pem_batch(1, day_ahead_horizon, _NoSolver(), series=series, stride=stride)
+        bidder, da = scenarios.wind_pem_batch(1, day_ahead_horizon, _NoSolver(), series=series, stride=stride,
+                                              **({} if sizes is None else dict(wind_mw=sizes["wind_mw"])))
         s = scenarios.load_series(series)
         mo = bidder.bidding_model_object
         tr_obj = mo.__class__(mo.model_data, wind_capacity_factors=list(s["rt_cf"][:tracking_horizon]), wind_pmax_mw=mo._wind_pmax_mw,
@@ -189,10 +215,60 @@ def _templates(flowsheet, day_ahead_horizon, tracking_horizon):
     return bidder, da, bidder.real_time_model, tracker, desc
 
 
+_default_rows_cache = {}
+
+
+def _default_kept_rows(flowsheet, day_ahead_horizon, tracking_horizon):
+    """names of the rows presolve keeps in the three LPs of the DEFAULT plant (built once per shape)"""
+    key = (flowsheet, int(day_ahead_horizon), int(tracking_horizon))
+    if key not in _default_rows_cache:
+        _, da, rt, tracker, _ = _templates(*key)
+        _default_rows_cache[key] = tuple(tuple(m.lp.row_names) for m in (da, rt, tracker.model))
+    return _default_rows_cache[key]
+
+
+def _check_template(flowsheet, day_ahead_horizon, tracking_horizon, models):
+    """Soundness of ONE template for a batch of different plants.  Presolve, the hulls and the implied-range column scaling belong to
+    the handle, not to the plant.  The template is built at the batch's LARGEST sizes: every size-dependent bound of a plant (wind and
+    battery column upper bounds, the right-hand side of state_of_charge_bounds, all with lower side 0 / -inf) lies inside the template's,
+    which presolve takes as the hull - so a row it proved never binding for the template never binds for a smaller plant either.
+    (The argument rests on that ONE-SIDEDNESS: a size-dependent bound whose other side moved with the size - a minimum load, say -
+    would make a smaller plant's box stick out of the template's, and would need a declared hull instead.)
+    What remains to be shown is that it did not KEEP or DROP anything else than for the default plant (whose LP shape the kernels and the
+    tests are validated on): the kept rows must be the default plant's, name by name.  An energy capacity beyond the 1e8 kWh ramp
+    bound, for instance, keeps the 48 energy-ramp rows; a battery of 0 MW lets presolve drop rows a battery needs."""
+    want = _default_kept_rows(flowsheet, day_ahead_horizon, tracking_horizon)
+    for name, m, rows in zip(("day-ahead", "real-time", "tracking"), models, want):
+        got = tuple(m.lp.row_names)
+        if got != rows:
+            diff = sorted(set(got) ^ set(rows))
+            raise ValueError(f"the sizes of this batch leave the range for which one LP template is sound: presolve keeps {len(got)} rows of the "
+                             f"{name} LP at the batch's largest sizes, {len(rows)} for the default plant (kept rows differ in {diff[:4]}"
+                             f"{' ...' if len(diff) > 4 else ''})" +
+                             ("; battery_mwh * 1e3 may be at most the 1e8 kWh energy-ramp bound and the batch's largest battery_mw must be above 0"
+                              if flowsheet == "wind_battery" else ""))
+
+
+def _objective_constant(model_object, horizon, weighted_family, per_kw, cf):
+    """base_c0 of a template built on `model_object`, in the arithmetic that builds it: the constants of tot_cost[t] * weight added in
+    the order of t (Bidder._refresh_cost_objective / Tracker._refresh_objective; the penalty terms carry no constant), less the
+    template's curtailment constant per_kw * (wind_kw * sum cf[:T]) (_Model.__init__).  Bit for bit the template's own value."""
+    from .lp import LinearBlock
+    block = LinearBlock("fs")
+    model_object.populate_model(block, horizon)
+    name, weight = weighted_family
+    const = 0.0
+    for t in range(horizon):
+        const += block.expressions[name][t].const * float(weight)
+    fam = getattr(block, "windBattery", None) or getattr(block, "windPEM")
+    return float(const) - float(per_kw) * float(fam["wind_kw"] * float(np.sum(cf[:horizon])))
+
+
 class BatchedDoubleLoop:
     def __init__(self, flowsheet, n_scenarios, device=0, first_scenario=0, day_ahead_horizon=48, tracking_horizon=4, lp_backend=None,
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
-                 market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None):
+                 market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
+                 battery_mwh=None):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -205,7 +281,16 @@ class BatchedDoubleLoop:
         (None: arange(B)), so that several plants - parameter points of a sweep - can share one window.
         bidder="parametrized" (wind_pem, wind_battery; perfect forecaster, one scenario, tracking_horizon <= 16), bid_price [$/MWh] and
         storage_mw [MW of PEM / battery the upper tier covers], scalars or arrays [B]: the two-tier closed-form curves of the
-        reference's parametrized bidders instead of bidding LPs (module docstring); market "price_taker" or "stub"."""
+        reference's parametrized bidders instead of bidding LPs (module docstring); market "price_taker" or "stub".
+        wind_mw, battery_mw [MW], battery_mwh [MWh], scalars or arrays [B] (bidder="lp"): the SIZE of every plant, so that a design
+        sweep is one batch (sweeps.design_sweep).  "wind_battery" takes all three; what is left None keeps the default plant's 200 MW
+        of wind and 25 MW / 100 MWh of battery, except that battery_mw without battery_mwh means the flowsheet's own default of four
+        hours, 4 * battery_mw.  "wind_pem" takes wind_mw only (default 847 MW): in the reference's LP, and in this one, the PEM capacity
+        is a free column that the bidding LP chooses - it is not a design parameter of the LP bidder (bidder="parametrized" has
+        storage_mw for it).  Refused (ValueError): sizes for "nuclear" or for bidder="parametrized", battery sizes for "wind_pem", a
+        wrong array length, non-finite values, wind_mw <= 0, negative battery sizes, wind_mw + battery_mw >= 2e7 (the cent arithmetic
+        of the curves), and a batch whose largest sizes change what presolve keeps (_check_template).  With all three None the loop is
+        the default one, unchanged: same templates, descriptors with NULL per-plant pointers, same launches."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
@@ -240,6 +325,8 @@ class BatchedDoubleLoop:
             bid_price, storage_mw = per_plant(bid_price, "bid_price"), per_plant(storage_mw, "storage_mw")
         elif bid_price is not None or storage_mw is not None:
             raise ValueError("bid_price and storage_mw belong to bidder='parametrized'")
+        sizes = self._plant_sizes(flowsheet, B, wind_mw, battery_mw, battery_mwh)
+        self.sized = sizes is not None
         if plant_windows is None:
             plant_windows = np.arange(B)
         else:
@@ -251,8 +338,12 @@ class BatchedDoubleLoop:
         self.stochastic = forecaster != "perfect" or market != "stub" or self.parametrized
         rows = 1 if self.parametrized else B * S                           # rows of the bidding batches (plant b, scenario i: row b * S + i; no bidding LP is solved in parametrized mode: one template row)
         self.dev = dev = torch.device("cuda", device) if lp_backend is None else torch.device("cpu")
-        bidder, da_model, rt_model, tracker, d = _templates(flowsheet, day_ahead_horizon, tracking_horizon)
+        # one template for the batch, built at its largest sizes (None: the default plant's, untouched)
+        bidder, da_model, rt_model, tracker, d = _templates(flowsheet, day_ahead_horizon, tracking_horizon,
+                                                            None if sizes is None else {k: float(v.max()) for k, v in sizes.items()})
         tr_model = tracker.model
+        if self.sized:
+            _check_template(flowsheet, day_ahead_horizon, tracking_horizon, (da_model, rt_model, tr_model))
         self.bidder, self.tracker_template = bidder, tracker
         da_s, rt_s, cf_s = d["prices"]
         self.N = N = len(rt_s)
@@ -294,6 +385,8 @@ class BatchedDoubleLoop:
         self.simplex_warm = bool(simplex_warm) and lp_backend is None
         self._graphs, self._warm = {}, False
         self.use_fused = bool(use_fused) and lp_backend is None and self.rt.T <= 16 and self.tr.T <= 16 and len(self.scale) <= 2
+        if self.sized:
+            self._sizes_setup(sizes, d, tracker)
         if self.parametrized:
             self._parametrized_setup(d, bid_price, storage_mw, tr_model, fam)
         elif self.stochastic:
@@ -315,6 +408,77 @@ class BatchedDoubleLoop:
                 self._param_setup()
             elif self.stochastic:
                 self._market_setup()
+
+    def _plant_sizes(self, flowsheet, B, wind_mw, battery_mw, battery_mwh):
+        """validated sizes -> dict of float64 arrays [B] (wind_mw; wind_battery: battery_mw, battery_mwh too), or None without sizes"""
+        given = {k: v for k, v in (("wind_mw", wind_mw), ("battery_mw", battery_mw), ("battery_mwh", battery_mwh)) if v is not None}
+        if not given:
+            return None
+        if flowsheet == "nuclear":
+            raise ValueError(f"{', '.join(given)}: the nuclear flowsheet has no plant sizes in this loop")
+        if self.parametrized:
+            raise ValueError(f"{', '.join(given)}: per-plant sizes belong to bidder='lp' (the parametrized bidders take storage_mw; their wind_mw is the flowsheet's)")
+        if flowsheet == "wind_pem" and (battery_mw is not None or battery_mwh is not None):
+            raise ValueError("wind_pem has no battery: battery_mw / battery_mwh are refused (the PEM capacity is a free column of its LP, not a size)")
+        out = {}
+        for name, v in given.items():
+            a = np.asarray(v, np.float64)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != B):
+                raise ValueError(f"{name} is a scalar or an array of length {B}, not of shape {a.shape}")
+            if not np.isfinite(a).all():
+                raise ValueError(f"{name} must be finite")
+            if (a <= 0).any() if name == "wind_mw" else (a < 0).any():
+                raise ValueError("wind_mw must be > 0" if name == "wind_mw" else f"{name} must be >= 0")
+            out[name] = np.broadcast_to(a, (B,)).copy()
+        if flowsheet == "wind_battery":
+            if "battery_mwh" not in out:                                   # the flowsheet's own default: four hours of the given power
+                out["battery_mwh"] = 4.0 * out["battery_mw"] if "battery_mw" in out else np.full(B, _WIND_BATTERY_SIZES["battery_mwh"])
+            for name in ("wind_mw", "battery_mw"):
+                out.setdefault(name, np.full(B, _WIND_BATTERY_SIZES[name]))
+        total = out["wind_mw"] + out.get("battery_mw", 0.0)
+        if (total >= 2.0e7).any():                                         # (2e7 MW: the range of the cent arithmetic, bid_curves.cents)
+            raise ValueError("wind_mw + battery_mw must stay below 2e7")
+        return out
+
+    def _sizes_setup(self, sizes, d, tracker):
+        """the per-plant operands of a sized batch: wind kW and objective constant [B] of each of the three models (host, float64,
+        once), and the battery's static bounds written into the per-row tensors (rows b * S + i of the bidding models, row b of the
+        tracker) - elec_in / elec_out <= battery kW, state_of_charge_bounds <= battery kWh.  No step ever rewrites those."""
+        import torch
+        B, S, fam = self.B, self.S, d["family"]
+        mo = self.bidder.bidding_model_object
+        cf = d["prices"][2]
+        self.wind_mw, self.battery_mw, self.battery_mwh = sizes["wind_mw"], sizes.get("battery_mw"), sizes.get("battery_mwh")
+        wind_kw = self.wind_mw * 1e3
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float64), device=self.dev)
+
+        def model_object(w):
+            if self.flowsheet == "wind_battery":
+                return mo.__class__(model_data=mo.model_data, wind_capacity_factors=list(cf[:max(self.da.T, self.rt.T, self.tr.T)]), wind_pmax_mw=w,
+                                    battery_pmax_mw=mo._battery_pmax_mw, battery_energy_capacity_mwh=mo._battery_energy_capacity_mwh)
+            return mo.__class__(mo.model_data, wind_capacity_factors=list(cf[:max(self.da.T, self.rt.T, self.tr.T)]), wind_pmax_mw=w,
+                                pem_pmax_mw=mo._pem_pmax_mw)
+        distinct, inverse = np.unique(self.wind_mw, return_inverse=True)
+        for m, family in ((self.da, mo.total_cost), (self.rt, mo.total_cost), (self.tr, tracker.tracking_model_object.total_cost)):
+            c0 = np.array([_objective_constant(model_object(float(w)), m.T, family, m.wind[2], cf) for w in distinct])
+            at = int(np.argmax(distinct))                                  # the template IS the largest wind size: the same number, bit for bit
+            if c0[at] != m.base_c0 or float(distinct[at]) * 1e3 != m.wind[1]:
+                raise RuntimeError(f"the objective constant recomputed for the template's wind size ({c0[at]!r}) is not the template's ({m.base_c0!r})")
+            m.set_plant_sizes(wind_kw, c0[inverse], self.dev)
+        cols, coef = self.tr.terms()                                       # P_T[0] of the tracker as phase 2 of dsp_loop_update reads it (_hand_off_exact)
+        used = cols[0] >= 0
+        self.tr.p0_cols = torch.as_tensor(cols[0][used], dtype=torch.int64, device=self.dev)
+        self.tr.p0_coef = t(coef[0][used])
+        if self.flowsheet != "wind_battery":
+            return
+        batt_kw, batt_kwh = self.battery_mw * 1e3, self.battery_mwh * 1e3
+        for m, model, per in ((self.da, self.bidder.day_ahead_model, S), (self.rt, self.bidder.real_time_model, S), (self.tr, tracker.model, 1)):
+            periods = getattr(model.block, fam)["periods"]
+            cols = [p[key].index for p in periods for key in ("elec_in", "elec_out")]
+            rows = [model.lp.row_names.index(f"battery.state_of_charge_bounds[{k}]") for k in range(len(periods))]
+            m.batt_cols, m.soc_rows = cols, rows
+            m.ub[:, cols] = t(np.repeat(batt_kw, per))[:, None]
+            m.rhi[:, rows] = t(np.repeat(batt_kwh, per))[:, None]
 
     def _parametrized_setup(self, d, bid_price, storage_mw, tr_model, fam):
         import torch
@@ -398,6 +562,8 @@ class BatchedDoubleLoop:
             w.waste_per_kw = m.wind[2] if m.wind is not None else 0.0
             w.c0_base = m.base_c0
             w.status, w.flags = m.out["status"].data_ptr(), m.out["flags"].data_ptr()
+            if m.kw_plant is not None:                                     # (None: the pointers stay NULL, the kernels read the scalars)
+                w.wind_kw_plant, w.c0_base_plant = m.kw_plant.data_ptr(), m.c0_plant.data_ptr()
             return w
         st = DspLoopState()
         st.B, st.N = self.B, self.N
@@ -444,6 +610,8 @@ class BatchedDoubleLoop:
             w.wind_kw = m.wind[1] if m.wind is not None else 0.0
             w.waste_per_kw = m.wind[2] if m.wind is not None else 0.0
             w.c0_base = m.base_c0
+            if m.kw_plant is not None:
+                w.wind_kw_plant, w.c0_base_plant = m.kw_plant.data_ptr(), m.c0_plant.data_ptr()
             return w
         self._mk_state, self._mk_da, self._mk_rt = mk, struct(self.da), struct(self.rt)
 
@@ -479,12 +647,15 @@ class BatchedDoubleLoop:
         for k, col in enumerate(m.state_init):
             m.lb[:, col] = self.state[:, k]
             m.ub[:, col] = self.state[:, k]
-        m.c0.fill_(m.base_c0)
+        if m.c0_plant is None:
+            m.c0.fill_(m.base_c0)
+        else:
+            m.c0.copy_(m.c0_plant)
         if price_c0 is not None:
             m.c0 += price_c0
         if m.wind is not None:
-            cols, kw, per_kw = m.wind
-            avail = kw * self._window(self.cf_series, m.T)
+            cols, _, per_kw = m.wind
+            avail = m.kw() * self._window(self.cf_series, m.T)
             m.ub[:, cols] = avail
             m.c0 += per_kw * avail.sum(1)
 
@@ -562,8 +733,8 @@ class BatchedDoubleLoop:
 
     def _avail(self, m):
         """wind availability of the window [B, T] and its sum accumulated in the order of t (the kernels' order: bit-identical constants)"""
-        cols, kw, per_kw = m.wind
-        avail = kw * self._window(self.cf_series, m.T)
+        cols, _, per_kw = m.wind
+        avail = m.kw() * self._window(self.cf_series, m.T)
         total = avail[:, 0]
         for t in range(1, m.T):
             total = total + avail[:, t]
@@ -578,9 +749,9 @@ class BatchedDoubleLoop:
             psum = rt[:, 0] * m.PT_const[0]
             for t in range(1, m.T):
                 psum = psum + rt[:, t] * m.PT_const[t]
-            c0 = m.base_c0_t - psum
+            c0 = (m.base_c0_t if m.c0_plant is None else self._rows(m.c0_plant)) - psum
         else:
-            c0 = m.base_c0_t.expand(rt.shape[0])
+            c0 = m.base_c0_t.expand(rt.shape[0]) if m.c0_plant is None else self._rows(m.c0_plant)
         for j, col in enumerate(m.state_init):
             v = self._rows(self.state[:, j])
             m.lb[:, col] = v
@@ -603,7 +774,7 @@ class BatchedDoubleLoop:
         if tr.wind is not None:
             cols, avail, waste = self._avail(tr)
             tr.ub[:, cols] = avail
-            tr.c0.copy_(tr.base_c0 + waste)
+            tr.c0.copy_((tr.base_c0 if tr.c0_plant is None else tr.c0_plant) + waste)
         else:
             tr.c0.fill_(tr.base_c0)
 
@@ -693,10 +864,29 @@ class BatchedDoubleLoop:
         out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
         self._check(out)
         x, rt0 = out["x"], rt0[:, 0]
+        if self.sized:                                # a sized batch states phase 2 of dsp_loop_update exactly, sums included (as the parametrized mode)
+            self._hand_off_exact(x, rt0, k)
+            return
         self.delivered.copy_(tr.power_output(x)[:, 0])
         for j, col in enumerate(tr.state_real):
             self.state[:, j] = torch.round(x[:, col] * self.scale[j]) / self._scale_t[j]
         self.revenue += self.delivered * rt0 + self.da_offer[:, k] * (self.da_prices[:, k] - rt0)
+        self.energy_mwh += self.delivered
+        self.hour_t += 1
+
+    def _hand_off_exact(self, x, rt0, k):
+        """delivered power, state, revenue, energy and clock in the arithmetic of phase 2 of dsp_loop_update, so that the tensor form and
+        the kernels agree bit for bit on the sums too: P_T[0] = fma(cb, x[b], fma(ca, x[a], const)), revenue += fma(delivered, rt,
+        da_offer * (da - rt))   (the statement of _hour_step_parametrized)"""
+        import torch
+        tr = self.tr
+        p = tr.PT_const[0].expand(self.B)
+        for e in range(tr.p0_cols.shape[0]):
+            p = exact_fma(torch, tr.p0_coef[e].expand(self.B), x[:, tr.p0_cols[e]], p)
+        self.delivered.copy_(p)
+        for j, col in enumerate(tr.state_real):
+            self.state[:, j] = torch.round(x[:, col] * self.scale[j]) / self._scale_t[j]
+        self.revenue += exact_fma(torch, self.delivered, rt0, self.da_offer[:, k] * (self.da_prices[:, k] - rt0))
         self.energy_mwh += self.delivered
         self.hour_t += 1
 

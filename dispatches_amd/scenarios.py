@@ -79,7 +79,7 @@ def _apply_cf_windows(model, wind_cols, wind_kw, cf_windows, cf_template, waste_
 
 
 def wind_battery_batch(B, T, solver, series="rts_gmlc_309.npz", stride=17, wind_mw=200.0, batt_mw=25.0,
-                       price_cap=500.0, ramp_cost=0.0, throughput_nodes=0):
+                       price_cap=500.0, ramp_cost=0.0, throughput_nodes=0, batt_mwh=None):
     """LP #1 (wind + battery) day-ahead bidding, B scenarios x T hours (BASELINE metric workload: T=24, B=4096;
     config 4 shape: T=48, bus 309, start hours (17 k) mod (N - T))."""
     s = load_series(series)
@@ -88,7 +88,8 @@ def wind_battery_batch(B, T, solver, series="rts_gmlc_309.npz", stride=17, wind_
     fc = WindowForecaster(s["da_lmp"], s["rt_lmp"], starts, clip=(0.0, price_cap))
     mp = MultiPeriodWindBattery(_thermal_data("309_WIND_1", "Carter", wind_mw, batt_mw),
                                 wind_capacity_factors=list(s["rt_cf"]), wind_pmax_mw=wind_mw,
-                                battery_pmax_mw=batt_mw, battery_energy_capacity_mwh=4 * batt_mw, throughput_nodes=throughput_nodes)
+                                battery_pmax_mw=batt_mw, battery_energy_capacity_mwh=4 * batt_mw if batt_mwh is None else batt_mwh,
+                                throughput_nodes=throughput_nodes)
     bidder = Bidder(mp, day_ahead_horizon=T, real_time_horizon=4, n_scenario=B, solver=solver, forecaster=fc,
                     ramp_cost=ramp_cost)
     model = bidder.day_ahead_model

@@ -3,7 +3,11 @@
 The reference runs its wind + PEM study (run_double_loop_PEM.py, `sweep_design_*`) as one Prescient job per (--pem_bid, --pem_pmax)
 point.  In the device double loop (rolling_flowsheets.py::BatchedDoubleLoop with bidder="parametrized") a whole
 (bid price x storage size x price window) grid is one batch of plants: every window carries the full grid through `plant_windows`,
-bidding is arithmetic, and only the tracking LPs are solved."""
+bidding is arithmetic, and only the tracking LPs are solved.
+
+The wind + battery study (run_double_loop_battery.py: --wind_pmax, --battery_pmax, --battery_energy_capacity, one Prescient job per size
+point of new_wind_battery_ratio_duration_sweep_sb) bids with the stochastic LP Bidder: `design_sweep` runs a (wind size x battery power
+x duration x price window) grid as one batch of DIFFERENT plants through BatchedDoubleLoop's wind_mw / battery_mw / battery_mwh."""
 from __future__ import annotations
 
 import numpy as np
@@ -33,5 +37,45 @@ def parametrized_sweep(flowsheet, bid_prices, storage_mws, n_windows, n_days, de
     out = {name: res[key].cpu().numpy().reshape(shape).copy()
            for name, key in (("revenue", "obj"), ("energy_mwh", "energy_mwh"), ("da_energy_mwh", "da_energy_mwh"), ("offered_mwh", "offered_mwh"),
                              ("h2_kg", "h2_kg")) if key in res}
+    out["all_optimal"] = bool(ok)
+    return out
+
+
+def design_layout(wind_mws, battery_mws, durations_h, n_windows):
+    """-> (wind_mw [B], battery_mw [B], battery_mwh [B], plant_windows [B]) of the grid flattened in C order with the window axis last
+    (the rule of grid_layout): plant (i, j, d, w) -> ((i * J + j) * D + d) * W + w;  battery_mwh = battery_mw * duration_h"""
+    axes = [np.asarray(a, np.float64).ravel() for a in (wind_mws, battery_mws, durations_h)]
+    if min(len(a) for a in axes) < 1 or int(n_windows) < 1:
+        raise ValueError("a sweep needs at least one wind size, one battery size, one duration and one window")
+    wind, batt, dur, win = np.meshgrid(*axes, np.arange(int(n_windows)), indexing="ij")
+    return wind.ravel(), batt.ravel(), (batt * dur).ravel(), win.ravel().astype(np.int64)
+
+
+def design_sweep(flowsheet, wind_mws, battery_mws, durations_h, n_windows, n_days, n_price_scenarios=1, forecaster="perfect",
+                 market="price_taker", device=0, lp_backend=None, **loop_kw):
+    """Runs `n_days` simulated days of the (wind MW x battery MW x duration h x window) grid of `flowsheet` with the LP bidder, every grid
+    point a plant of its own size.  "wind_battery": all axes; "wind_pem": the wind axis only - battery_mws and durations_h must have
+    length 1 and are not used (pass [0.0], [0.0]).  -> dict of numpy arrays shaped [len(wind_mws), len(battery_mws), len(durations_h),
+    n_windows]: revenue, energy_mwh (delivered), da_energy_mwh and offered_mwh (where the mode has them: not the deterministic loop,
+    forecaster="perfect" with market="stub"), throughput_kwh (wind_battery: the final accumulated battery throughput); and all_optimal."""
+    from .rolling_flowsheets import BatchedDoubleLoop
+    wind, batt, mwh, win = design_layout(wind_mws, battery_mws, durations_h, n_windows)
+    shape = tuple(len(np.ravel(a)) for a in (wind_mws, battery_mws, durations_h)) + (int(n_windows),)
+    if flowsheet == "wind_pem":
+        if shape[1] != 1 or shape[2] != 1:
+            raise ValueError("wind_pem has no battery: the battery and duration axes of its sweep must have length 1")
+        sizes = dict(wind_mw=wind)
+    else:
+        sizes = dict(wind_mw=wind, battery_mw=batt, battery_mwh=mwh)
+    loop = BatchedDoubleLoop(flowsheet, len(wind), device=device, lp_backend=lp_backend, n_price_scenarios=n_price_scenarios, forecaster=forecaster,
+                             market=market, plant_windows=win, **sizes, **loop_kw)
+    for _ in range(int(n_days)):
+        loop.run_day()
+    res, ok = loop.results()
+    out = {name: res[key].cpu().numpy().reshape(shape).copy()
+           for name, key in (("revenue", "obj"), ("energy_mwh", "energy_mwh"), ("da_energy_mwh", "da_energy_mwh"), ("offered_mwh", "offered_mwh"))
+           if key in res}
+    if flowsheet == "wind_battery":
+        out["throughput_kwh"] = res["state"][:, 1].cpu().numpy().reshape(shape).copy()
     out["all_optimal"] = bool(ok)
     return out

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 15
+#define DSP_VERSION 16
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -389,6 +389,9 @@ typedef struct dsp_loop_model {
   int32_t state_init[2], state_real[2];/* columns fixed to the realised state / holding it after the first period                */
   double  wind_kw, c0_base, waste_per_kw;
   const int32_t *status, *flags;       /* [B] outputs of its last solve or NULL (as dsp_wb_model)                                 */
+  const double *wind_kw_plant, *c0_base_plant;       /* [B] per PLANT, both or neither (ABI 16): plant b's wind capacity and its
+                                          objective constant instead of the scalars wind_kw / c0_base; NULL = the scalars.  Only
+                                          with wind columns; `rt` and `tr` of one call carry them together                        */
 } dsp_loop_model;
 
 typedef struct dsp_loop_state {
@@ -404,7 +407,8 @@ typedef struct dsp_loop_state {
   int64_t *uncertified;
 } dsp_loop_state;
 
-/* phases as dsp_wb_rolling_update: 0 before the real-time bidding solve of hour-of-day k, 1 between the solves, 2 after the tracking solve */
+/* phases as dsp_wb_rolling_update: 0 before the real-time bidding solve of hour-of-day k, 1 between the solves, 2 after the tracking solve.
+ * Per-plant pointers (ABI 16): refusals as stated at dsp_loop_market_clear. */
 int dsp_loop_update(const dsp_loop_state *st, const dsp_loop_model *rt, const dsp_loop_model *tr, int32_t phase, int32_t k, void *hipStream);
 
 /* The scenario half of the Bidder's bid assembly ON THE DEVICE (reference: idaes Bidder._assemble_bids as DISPATCHES drives it -
@@ -520,6 +524,8 @@ typedef struct dsp_loop_market_model {
   int32_t wind_cols[DSP_MARKET_MAX_T]; /* wind production column of every period; wind_cols[0] = -1: the flowsheet has no wind    */
   int32_t state_init[2];               /* columns fixed to the realised state                                                     */
   double wind_kw, c0_base, waste_per_kw;
+  const double *wind_kw_plant, *c0_base_plant;       /* [B] per PLANT (not per row: row r reads plant r / S), both or neither
+                                          (ABI 16, as dsp_loop_model): NULL = the scalars wind_kw / c0_base                       */
 } dsp_loop_market_model;
 
 typedef struct dsp_loop_market_state {
@@ -548,7 +554,13 @@ int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_mark
  * k = 0 .. 23 (T <= DSP_LOOP_MAX_T): real-time pairs, cleared at the realised price (t = 0) / scenario 0's forecast (t >= 1).  With `tr`
  * (the tracking model of B rows, tr->T == T) the lanes also write the tracker's LP of this hour: dispatch rows = dispatch[t] -
  * tr->pt_const[t], state columns, wind availability and c0 = c0_base + waste_per_kw * sum_t availability (as phase 1 of dsp_loop_update).
- * Refusals as dsp_loop_market_prepare, and for a dispatch row of `tr` outside [0, tr->m). */
+ * Refusals as dsp_loop_market_prepare, and for a dispatch row of `tr` outside [0, tr->m).
+ * Per-plant sizes (ABI 16; BatchedDoubleLoop(wind_mw=, battery_mw=, battery_mwh=)): with wind_kw_plant / c0_base_plant the lanes read
+ * plant b's wind capacity and objective constant at the very sites that read the scalars - same intrinsics, same order, so that kernel
+ * = tensor form = graph replay stays bit for bit.  A size is never a matrix coefficient of these flowsheets: the battery's power and
+ * energy limits are static column / row bounds that the caller writes once into lb / ub / rhi.  DSP_ERR_INVALID, nothing launched, for
+ * one of the two pointers without the other, for per-plant pointers on a model without wind columns, and for `m` and `tr`
+ * (dsp_loop_update: `rt` and `tr`) that do not carry them together. */
 int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market_model *m, const dsp_loop_model *tr, int32_t k, int32_t T,
                           double *dispatch, int32_t *curve, int32_t *count, void *hipStream);
 
