@@ -5,6 +5,9 @@ wave, all LPs of the batch advanced in lock step here (numpy batch axis = the GP
 
     min c.x   s.t.  rlo <= A x <= rhi,  lb <= x <= ub        (scaled by the handle's D_r, D_c)
     z = (x, s),  s = A x  in [rlo, rhi];  start: all slacks basic, structurals at the finite bound nearest to 0
+             (lb = -inf, ub finite: at ub, marked "at upper"; free columns: at 0, on neither side)
+    free columns (lb = -inf, ub = +inf): eligible when |d| > dtol, moving up for d < 0 and down for d > 0, whatever side
+             they are marked on; once basic they never block, so they never leave
     phase 1: minimise the sum of bound violations of the basic variables (costs -1 / +1 on violated basics),
              an infeasible basic blocks when it reaches the bound it violates
     phase 2: Dantzig pricing on reduced costs recomputed from the tableau every pivot (no drift), two-pass ratio test
@@ -36,7 +39,10 @@ def simplex_batch(A, c, lb, ub, rlo, rhi, max_pivots=None, tol_p=1e-9, tol_d=1e-
     # nonbasic structurals at the finite bound nearest to zero (all dispatch columns have lb = 0)
     val = np.where(np.isfinite(lo) & (np.abs(lo) <= np.abs(np.where(np.isfinite(hi), hi, BIG))), lo,
                    np.where(np.isfinite(hi), hi, np.where(np.isfinite(lo), lo, 0.0)))
-    at_upper = np.isfinite(hi) & (val == hi) & ~(val == lo)
+    only_upper = ~np.isfinite(lo) & np.isfinite(hi)                      # lb = -inf, ub finite: starts at ub, on its upper side
+    val = np.where(only_upper, hi, val)
+    at_upper = (np.isfinite(hi) & (val == hi) & ~(val == lo)) | only_upper
+    free = ~np.isfinite(lo) & ~np.isfinite(hi)                           # priced on |d|, direction from the sign of d
     basis = np.tile(np.arange(n, N)[None], (B, 1))                       # [B, m] variable index of each row's basic
     is_basic = np.zeros((B, N), bool); is_basic[:, n:] = True
     beta = val[:, :n] @ A.T                                              # s = A x_N
@@ -58,7 +64,7 @@ def simplex_batch(A, c, lb, ub, rlo, rhi, max_pivots=None, tol_p=1e-9, tol_d=1e-
         cN = np.where(phase1[:, None], 0.0, cost)
         d = cN - np.einsum("bi,bij->bj", cB, T)                           # reduced costs of every column
         dtol = np.where(phase1, 1e-9, ctol)[:, None]
-        elig = ~is_basic & ~fixed & (((~at_upper) & (d < -dtol)) | (at_upper & (d > dtol)))
+        elig = ~is_basic & ~fixed & np.where(free, np.abs(d) > dtol, ((~at_upper) & (d < -dtol)) | (at_upper & (d > dtol)))
         score = np.where(elig, np.abs(d), -1.0)
         j = score.argmax(1)
         none = score[rows, j] < 0
@@ -69,7 +75,8 @@ def simplex_batch(A, c, lb, ub, rlo, rhi, max_pivots=None, tol_p=1e-9, tol_d=1e-
         if it == max_pivots:
             status = np.where(run, 1, status)
             break
-        sgn = np.where(at_upper[rows, j], -1.0, 1.0)                      # entering moves up from its lower / down from its upper bound
+        # entering moves up from its lower / down from its upper bound; a free column moves against the sign of its reduced cost
+        sgn = np.where(np.where(free[rows, j], d[rows, j] > 0.0, at_upper[rows, j]), -1.0, 1.0)
         alpha = T[rows, :, j]                                             # [B, m]
         delta = -sgn[:, None] * alpha                                     # d beta / d t
         amax = np.abs(alpha).max(1, keepdims=True)
