@@ -414,6 +414,7 @@ int dsp_market_clear(const dsp_market_state *st, const dsp_market_model *m, cons
 static bool loop_market_state_ok(const dsp_loop_market_state *st) {
   if (!st || st->B < 0 || st->N < 1 || st->S < 1 || st->S > DSP_MARKET_MAX_S || st->p_min_cents < 0 || st->p_min_cents > 2000000000ll) return false;
   if (st->backcast ? (st->D < 1 || st->S > st->D || 24ll * st->D > st->N) : st->S != 1) return false;
+  if (st->rt_history_lag_days < 0 || (st->backcast && 24ll * ((long long)st->D + st->rt_history_lag_days) > st->N)) return false;      // (ABI 17)
   return st->start && st->hour && st->da_series && st->rt_series;
 }
 static bool loop_market_model_ok(const dsp_loop_market_model *m) {
@@ -493,6 +494,36 @@ int dsp_loop_param_step(const dsp_loop_param_state *st, const dsp_loop_model *tr
     if (!st->h2_kg || !tr->x || tr->n < 1 || !market_col_ok(st->pem_col, tr->n)) return DSP_ERR_INVALID;
   }
   HIP_TRY(launch_loop_param_step(*st, *tr, (int)phase, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
+// the projection tracker of the descriptor loop (dsp_project.hip): every index and pointer a lane would use is checked here
+int dsp_loop_project(const dsp_loop_project_state *st, const dsp_loop_model *pj, int32_t phase, int32_t j, void *hipStream) {
+  if (!st || st->B < 1 || st->N < 1 || st->ruc_hour < 1 || st->ruc_hour > 23 || phase < 0 || phase > 2) return DSP_ERR_INVALID;
+  if (j < 0 || j >= (phase == 2 ? 1 : 24 - st->ruc_hour)) return DSP_ERR_INVALID;
+  if (phase == 2) {
+    if (!st->da_offer || !st->da_prices || !st->pend_offer || !st->pend_prices || st->slots < 0 || st->slots > DSP_MARKET_MAX_S + 1) return DSP_ERR_INVALID;
+    if (st->slots > 0 && (!st->da_curve || !st->da_count || !st->pend_curve || !st->pend_count)) return DSP_ERR_INVALID;
+    HIP_TRY(launch_loop_project(*st, pj ? *pj : dsp_loop_model{}, 2, 0, (hipStream_t)hipStream));
+    return DSP_OK;
+  }
+  if (!pj || pj->T < 1 || pj->T > DSP_LOOP_MAX_T || pj->n < 1 || pj->m < 1 || pj->n_state < 0 || pj->n_state > 2) return DSP_ERR_INVALID;
+  if (!st->start || !st->hour || (pj->n_state > 0 && (!st->state || !st->proj_state))) return DSP_ERR_INVALID;      // (no state: empty traces may be NULL)
+  if (!plant_sizes_ok(pj->wind_kw_plant, pj->c0_base_plant, pj->wind_cols[0])) return DSP_ERR_INVALID;
+  if (phase == 0) {
+    if (!st->da_offer || !pj->lb || !pj->ub || !pj->rlo || !pj->rhi || !pj->c0) return DSP_ERR_INVALID;
+    const bool wind = pj->wind_cols[0] >= 0;
+    if (wind && !st->cf_series) return DSP_ERR_INVALID;
+    for (int e = 0; e < pj->n_state; ++e)
+      if (!market_col_ok(pj->state_init[e], pj->n)) return DSP_ERR_INVALID;
+    for (int t = 0; t < pj->T; ++t)
+      if (!market_col_ok(pj->track_rows[t], pj->m) || (wind && !market_col_ok(pj->wind_cols[t], pj->n))) return DSP_ERR_INVALID;
+  } else {
+    if (!pj->x || !pj->status || !pj->c0 || !st->obj || (pj->n_state > 0 && !st->proj_real) || !st->proj_obj) return DSP_ERR_INVALID;
+    for (int e = 0; e < pj->n_state; ++e)
+      if (!market_col_ok(pj->state_real[e], pj->n) || !(st->state_scale[e] > 0.0)) return DSP_ERR_INVALID;
+  }
+  HIP_TRY(launch_loop_project(*st, *pj, (int)phase, (int)j, (hipStream_t)hipStream));
   return DSP_OK;
 }
 

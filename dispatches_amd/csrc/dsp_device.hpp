@@ -180,6 +180,8 @@ hipError_t launch_loop_market_clear(const dsp_loop_market_state &st, const dsp_l
                                     double *dispatch, int32_t *curve, int32_t *count, hipStream_t stream);
 // parametrized two-tier bidding of the descriptor loop (dsp_param.hip): phase 0 day-ahead, 1 real time + tracker, 2 hydrogen
 hipError_t launch_loop_param_step(const dsp_loop_param_state &st, const dsp_loop_model &tr, int phase, hipStream_t stream);
+// projection tracker of the descriptor loop (dsp_project.hip): phase 0 write, 1 hand-off, 2 activate the pending bid
+hipError_t launch_loop_project(const dsp_loop_project_state &st, const dsp_loop_model &pj, int phase, int j, hipStream_t stream);
 hipError_t launch_spmv(int cpl, int rpl, const SpmvArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t st);
 
 #endif

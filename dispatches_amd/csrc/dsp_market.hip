@@ -217,6 +217,13 @@ __device__ __forceinline__ long long lmk_index(const dsp_loop_market_state &s, l
   long long v = (st0 + 24 * (d - D) + pos) % s.N;
   return v < 0 ? v + s.N : v;
 }
+// the same hour of the REAL-TIME series: with the backcast forecaster its history ends rt_history_lag_days earlier (ABI 17; a bid made
+// at the RUC hour: today is not a whole day of real-time prices yet).  lag 0: `at` itself.  24 * lag < N is checked on the host.
+__device__ __forceinline__ long long lmk_rt(const dsp_loop_market_state &s, long long at) {
+  if (!s.backcast || s.rt_history_lag_days == 0) return at;
+  const long long v = at - 24ll * s.rt_history_lag_days;
+  return v < 0 ? v + s.N : v;
+}
 
 __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m, int k) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -232,7 +239,7 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
   double avail_sum = 0.0, price_sum = 0.0;
   for (int t = 0; t < m.T; ++t) {
     const long long at = lmk_index(s, st0, h, i, hod, t);
-    const double rtp = s.rt_series[at];
+    const double rtp = s.rt_series[lmk_rt(s, at)];
     const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : s.da_series[at];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
@@ -292,7 +299,8 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
           if (cb >= 0) p = mk_opaque(__dadd_rn(p, mk_opaque(__dmul_rn(x[cb], fb))));
           power = __dadd_rn(p, fc);
         }
-        const double price = series[lmk_index(s, st0, h, i, hod, t)];
+        const long long at = lmk_index(s, st0, h, i, hod, t);
+        const double price = series[k < 0 ? at : lmk_rt(s, at)];
         const long long pc = bid_cents(power), cc = bid_cents(price);
         if (pc >= pmin && fabs(power) < INFINITY && fabs(price) < INFINITY) key = bid_key(pc, cc);
       } else {
@@ -306,7 +314,7 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
   if (any_bad && s.bad) *s.bad = 1;
   mk_sort<SP>(keys);
   // ---- the price that occurs: realised for the day-ahead market and for the hour at hand, scenario 0's for the look-ahead hours ----
-  const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[lmk_index(s, st0, h, 0, hod, t)];
+  const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[lmk_rt(s, lmk_index(s, st0, h, 0, hod, t))];
   // ---- lowest price among the distinct points (the inserted p_min point takes it) ----
   const bool has_min = keys[0] != kBidDrop && bid_key_power(keys[0]) == pmin;      // powers are >= p_min and ascending
   long long lowest = 0x7fffffffffffffffll;

@@ -108,10 +108,10 @@ class DspLoopState(C.Structure):
 EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_step", "dsp_get_dims",
                     "dsp_get_scaling", "dsp_destroy", "dsp_strerror", "dsp_last_hip_error", "dsp_version",
                     "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
-                    "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step")
+                    "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step", "dsp_loop_project")
 
 
-ABI_VERSION = 16         # DSP_VERSION of the include/dsp_hip.h these structures mirror
+ABI_VERSION = 17         # DSP_VERSION of the include/dsp_hip.h these structures mirror
 
 
 BID_MAX_HOURS, BID_MAX_SCENARIOS = 64, 16384
@@ -162,7 +162,8 @@ class DspLoopMarketState(C.Structure):
                 ("start", C.c_void_p), ("hour", C.c_void_p),
                 ("da_series", C.c_void_p), ("rt_series", C.c_void_p), ("cf_series", C.c_void_p),
                 ("state", C.c_void_p), ("da_offer", C.c_void_p), ("da_prices", C.c_void_p),
-                ("bad", C.c_void_p), ("uncertified", C.c_void_p), ("p_min_cents", C.c_int64)]
+                ("bad", C.c_void_p), ("uncertified", C.c_void_p), ("p_min_cents", C.c_int64),
+                ("rt_history_lag_days", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DspLoopParamState(C.Structure):
@@ -174,6 +175,17 @@ class DspLoopParamState(C.Structure):
                 ("da_offer", C.c_void_p), ("da_prices", C.c_void_p), ("da_curve", C.c_void_p), ("da_count", C.c_void_p),
                 ("rt_dispatch", C.c_void_p), ("rt_curve", C.c_void_p), ("rt_count", C.c_void_p),
                 ("h2_kg", C.c_void_p), ("h2_mul", C.c_double), ("h2_div", C.c_double), ("pem_col", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DspLoopProjectState(C.Structure):
+    """include/dsp_hip.h: dsp_loop_project_state (ABI 17) - the projection tracker of the descriptor loop's ruc_hour mode"""
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("ruc_hour", C.c_int32), ("slots", C.c_int32),
+                ("start", C.c_void_p), ("hour", C.c_void_p), ("cf_series", C.c_void_p), ("state", C.c_void_p),
+                ("state_scale", C.c_double * 2), ("obj", C.c_void_p),
+                ("proj_state", C.c_void_p), ("proj_real", C.c_void_p), ("proj_obj", C.c_void_p),
+                ("bad", C.c_void_p), ("uncertified", C.c_void_p),
+                ("da_offer", C.c_void_p), ("da_prices", C.c_void_p), ("pend_offer", C.c_void_p), ("pend_prices", C.c_void_p),
+                ("da_curve", C.c_void_p), ("da_count", C.c_void_p), ("pend_curve", C.c_void_p), ("pend_count", C.c_void_p)]
 
 
 def source_hash(root: Optional[str] = None) -> Optional[str]:
@@ -265,6 +277,8 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_market_clear.restype = C.c_int
     lib.dsp_loop_param_step.argtypes = [C.POINTER(DspLoopParamState), C.POINTER(DspLoopModel), i32, i32, vp]
     lib.dsp_loop_param_step.restype = C.c_int
+    lib.dsp_loop_project.argtypes = [C.POINTER(DspLoopProjectState), C.POINTER(DspLoopModel), i32, i32, vp]
+    lib.dsp_loop_project.restype = C.c_int
     lib.dsp_last_hip_error.restype = C.c_int
     if path == _LIB_PATH:
         _lib = lib

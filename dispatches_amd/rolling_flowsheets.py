@@ -34,7 +34,20 @@ Per-plant sizes (wind_mw, battery_mw, battery_mwh with the LP bidder; the refere
 coefficient.  The wind size is the upper bound of the wind columns (wind_kw[b] * capacity factor, every step) and two objective
 constants (curtailment, fixed O&M); the battery's power and energy limits are static column / row bounds written once.  So a batch of
 DIFFERENT plants shares one template - built at the batch's largest sizes, see `_check_template` - and the kernels read two arrays
-[B] where they read two scalars (dsp_loop_model / dsp_loop_market_model: wind_kw_plant, c0_base_plant)."""
+[B] where they read two scalars (dsp_loop_model / dsp_loop_market_model: wind_kw_plant, c0_base_plant).
+
+Bidding at the RUC hour (ruc_hour=H with the LP bidder; the reference's DoubleLoopCoordinator.bid_into_DAM, run_double_loop_battery.py:255-294
+builds its two trackers; our host restatement is workflow/coordinator.py::_project_tracking_trajectory): the day-ahead market of day d + 1
+runs at hour H of day d.  Day 0 bids at hour 0 from the initial state, as above.  At hour-of-day H of every day, before that hour's
+real-time step, the PROJECTION tracker - a _Model of its own on the tracker's template - starts from the realised state and solves 24 - H
+chained tracking LPs: step j tracks da_offer[H + j + t] on the periods with H + j + t < 24, its rows past midnight are free on both sides
+(Tracker._pass_market_dispatch on a short dispatch list), its wind window starts at hour 24 d + H + j, and its rounded first-period state
+is step j + 1's.  The day-ahead step then runs on the projected state with every window at 24 (d + 1) - backcast day-ahead scenario i is
+day d - i, real-time scenario i day d - 1 - i (day d is not a whole day of real-time prices when the RUC runs) - into PENDING buffers; at
+the start of day d + 1 day_ahead() solves nothing and makes them current (activate_pending_DA_bids).  The hourly steps are unchanged,
+including what their backcast knows - OURS: a Prescient-fed Backcaster would hold tomorrow's day-ahead prices after the RUC.
+`_project_write` / `_project_hand_off` / `_activate` are the specification as tensor operations; csrc/dsp_project.hip (dsp_loop_project)
+is the same arithmetic in one kernel per step.  proj_state / proj_real / proj_obj keep the last chain."""
 from __future__ import annotations
 
 import numpy as np
@@ -268,7 +281,7 @@ class BatchedDoubleLoop:
     def __init__(self, flowsheet, n_scenarios, device=0, first_scenario=0, day_ahead_horizon=48, tracking_horizon=4, lp_backend=None,
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
                  market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
-                 battery_mwh=None):
+                 battery_mwh=None, ruc_hour=None):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -290,7 +303,12 @@ class BatchedDoubleLoop:
         storage_mw for it).  Refused (ValueError): sizes for "nuclear" or for bidder="parametrized", battery sizes for "wind_pem", a
         wrong array length, non-finite values, wind_mw <= 0, negative battery sizes, wind_mw + battery_mw >= 2e7 (the cent arithmetic
         of the curves), and a batch whose largest sizes change what presolve keeps (_check_template).  With all three None the loop is
-        the default one, unchanged: same templates, descriptors with NULL per-plant pointers, same launches."""
+        the default one, unchanged: same templates, descriptors with NULL per-plant pointers, same launches.
+        ruc_hour: None (the loop above: the day-ahead bid of day d is made at hour 0 of day d, same launches, same bits) or an integer
+        H, 1 <= H <= 23: the reference's timeline (module docstring, "Bidding at the RUC hour").  Explicit, no default of ours: the
+        reference's drivers leave Prescient's ruc_execution_hour at Prescient's own default, 16.  Refused (ValueError): a value that
+        is not an integer of 1 .. 23, bidder="parametrized" (no bidding LP and no state in the bid: nothing to project), and
+        forecaster="backcast" with 24 (max_historical_days + 1) hours more than the series holds."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
@@ -325,6 +343,13 @@ class BatchedDoubleLoop:
             bid_price, storage_mw = per_plant(bid_price, "bid_price"), per_plant(storage_mw, "storage_mw")
         elif bid_price is not None or storage_mw is not None:
             raise ValueError("bid_price and storage_mw belong to bidder='parametrized'")
+        if ruc_hour is not None:
+            if isinstance(ruc_hour, bool) or not isinstance(ruc_hour, (int, np.integer)) or not 1 <= int(ruc_hour) <= 23:
+                raise ValueError(f"ruc_hour is None or an integer hour of the day 1 .. 23, not {ruc_hour!r}")
+            if self.parametrized:
+                raise ValueError("ruc_hour belongs to bidder='lp': a parametrized bid has no bidding LP and no state, nothing to project")
+            ruc_hour = int(ruc_hour)
+        self.ruc_hour = ruc_hour
         sizes = self._plant_sizes(flowsheet, B, wind_mw, battery_mw, battery_mwh)
         self.sized = sizes is not None
         if plant_windows is None:
@@ -350,6 +375,9 @@ class BatchedDoubleLoop:
         if self.stochastic and not self.parametrized and (24 * D > N or tracking_horizon > len(rt_model.HOUR) or not 24 <= len(da_model.HOUR) <= 48):
             raise ValueError("the stochastic mode needs max_historical_days whole days inside the series, tracking_horizon <= the real-time "
                              "horizon and a day-ahead horizon of 24 .. 48 periods")
+        if ruc_hour is not None and forecaster == "backcast" and 24 * (D + 1) > N:
+            raise ValueError("ruc_hour with forecaster='backcast' needs max_historical_days + 1 whole days inside the series: the real-time "
+                             "history of a bid made at the RUC hour ends one day earlier")
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float64), device=dev)
         idx = lambda cols: torch.as_tensor(np.asarray(cols, np.int64), device=dev)
         self.da_series, self.rt_series = t(da_s), t(rt_s)
@@ -379,6 +407,7 @@ class BatchedDoubleLoop:
         self.bad = torch.zeros((), dtype=torch.bool, device=dev)
         self.uncertified = torch.zeros((), dtype=torch.int64, device=dev)
         self.hour_t = torch.zeros((), dtype=torch.int64, device=dev)     # the clock on the device (graphs replay across days)
+        self._clk, self._st = self.hour_t, self.state                     # what a bidding step reads as clock and state (ruc_hour: the bid's)
         self._scale_t = [torch.full((), s, dtype=torch.float64, device=dev) for s in self.scale]
         self.hour = self.solves = 0
         self.use_graphs = bool(use_graphs) and lp_backend is None
@@ -402,6 +431,8 @@ class BatchedDoubleLoop:
             self.rt_dispatch = z(B, self.tr.T)
             self.da_energy_mwh, self.offered_mwh = z(B), z(B)
             self._hundred = torch.full((), 100.0, dtype=torch.float64, device=dev)
+        if self.ruc_hour is not None:
+            self._ruc_setup(mk(tr_model, B))
         if self.use_fused:
             self._fused_setup()
             if self.parametrized:
@@ -579,6 +610,23 @@ class BatchedDoubleLoop:
         self._loop_state = st
         self._loop_rt = struct(self.rt, pda=self.rt.pda_cols.cpu().tolist())
         self._loop_tr = struct(self.tr, track=self.tr.track_rows.cpu().tolist(), real=self.tr.state_real)
+        if self.ruc_hour is not None:
+            from .hip_solver import DspLoopProjectState
+            self._loop_pj = struct(self.pj, track=self.pj.track_rows.cpu().tolist(), real=self.pj.state_real)
+            ps = DspLoopProjectState()
+            ps.B, ps.N, ps.ruc_hour = self.B, self.N, self.ruc_hour
+            ps.slots = self.da_curve.shape[2] if self.stochastic else 0
+            for name in ("start", "hour", "cf_series", "state", "bad", "uncertified", "da_offer", "da_prices"):
+                setattr(ps, name, getattr(st, name))
+            for j in range(2):
+                ps.state_scale[j] = st.state_scale[j]
+            ps.obj = self.pj.out["obj"].data_ptr()
+            ps.proj_state, ps.proj_real, ps.proj_obj = self.proj_state.data_ptr(), self.proj_real.data_ptr(), self.proj_obj.data_ptr()
+            ps.pend_offer, ps.pend_prices = self.pend_offer.data_ptr(), self.pend_prices.data_ptr()
+            if self.stochastic:
+                ps.da_curve, ps.da_count = self.da_curve.data_ptr(), self.da_count.data_ptr()
+                ps.pend_curve, ps.pend_count = self.pend_curve.data_ptr(), self.pend_count.data_ptr()
+            self._proj_state_c = ps
 
     def _market_setup(self):
         from .hip_solver import DspLoopMarketModel, DspLoopMarketState
@@ -614,11 +662,17 @@ class BatchedDoubleLoop:
                 w.wind_kw_plant, w.c0_base_plant = m.kw_plant.data_ptr(), m.c0_plant.data_ptr()
             return w
         self._mk_state, self._mk_da, self._mk_rt = mk, struct(self.da), struct(self.rt)
+        if self.ruc_hour is not None:                  # the bid made at the RUC hour: its own clock, the projected state, the pending buffers
+            bid = DspLoopMarketState.from_buffer_copy(mk)
+            bid.hour, bid.state = self.bid_hour_t.data_ptr(), self.proj_state[-1].data_ptr() if len(self.scale) else None
+            bid.da_offer, bid.da_prices = self.pend_offer.data_ptr(), self.pend_prices.data_ptr()
+            bid.rt_history_lag_days = 1
+            self._mk_bid = bid
 
-    def _market(self, fn, *args):
+    def _market(self, fn, *args, bid=False):
         import ctypes as C
         import torch
-        rc = fn(C.byref(self._mk_state), *args, C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+        rc = fn(C.byref(self._mk_bid if bid else self._mk_state), *args, C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
         if rc != 0:
             raise RuntimeError(f"{fn.__name__} failed ({rc})")
 
@@ -631,9 +685,10 @@ class BatchedDoubleLoop:
             raise RuntimeError(f"dsp_loop_update failed ({rc})")
 
     # -- pieces of a step (all capturable: persistent tensors, the clock read on the device) ---------------------------------------
-    def _window(self, series, T):
+    def _window(self, series, T, offset=0):
         import torch
-        return series[(self.start[:, None] + self.hour_t + torch.arange(T, device=self.dev)[None, :]) % self.N]
+        clock = self._clk + offset if offset else self._clk
+        return series[(self.start[:, None] + clock + torch.arange(T, device=self.dev)[None, :]) % self.N]
 
     def _set_prices(self, m, da, rt):
         """c = base - RT . dP_T/dx - (DA - RT) on day_ahead_power ; c0 = base - RT . PT_const (Bidder._pass_price_forecasts)"""
@@ -645,8 +700,8 @@ class BatchedDoubleLoop:
         """what update_model writes: the state columns fixed to the realised values, wind availability of the window; and the objective
         constant of every plant (dsp_batch::obj_offset: the scale of the solver's objective-accuracy test, cf. rolling.py)"""
         for k, col in enumerate(m.state_init):
-            m.lb[:, col] = self.state[:, k]
-            m.ub[:, col] = self.state[:, k]
+            m.lb[:, col] = self._st[:, k]
+            m.ub[:, col] = self._st[:, k]
         if m.c0_plant is None:
             m.c0.fill_(m.base_c0)
         else:
@@ -664,7 +719,8 @@ class BatchedDoubleLoop:
         if out.get("flags") is not None:
             self.uncertified += ((out["flags"] & 1) != 0).sum()
 
-    def _day_ahead_step(self):
+    def _day_ahead_step(self, bid=False):
+        """bid: the bid made at the RUC hour for the next day (clock and state are the bid's, self._clk / self._st; the pending buffers)"""
         m = self.da
         da, rt = self._window(self.da_series, m.T), self._window(self.rt_series, m.T)
         self._set_state(m, self._set_prices(m, da, rt))
@@ -672,8 +728,8 @@ class BatchedDoubleLoop:
         m.ub.index_fill_(1, m.pda_cols, float("inf"))
         out = m.solve(self.B)
         self._check(out)
-        self.da_offer.copy_(out["x"][:, m.pda_cols][:, :24])
-        self.da_prices.copy_(da[:, :24])
+        (self.pend_offer if bid else self.da_offer).copy_(out["x"][:, m.pda_cols][:, :24])
+        (self.pend_prices if bid else self.da_prices).copy_(da[:, :24])
 
     def _hour_step(self, k):
         import torch
@@ -715,14 +771,17 @@ class BatchedDoubleLoop:
         self.hour_t += 1
 
     # -- stochastic mode: backcast scenarios, bid curves from p_min, market clearing (semantics: rolling.py, generalised over the descriptor) --
-    def _forecast(self, series, T, hod):
+    def _forecast(self, series, T, hod, lag_days=0):
         """[B, S, T] price scenarios asked at hour-of-day `hod` of the current day: Backcaster._forecast over the D whole days before
-        the current day of every plant's own circular series (rolling.py::_forecast)"""
+        the current day of every plant's own circular series (rolling.py::_forecast).  lag_days: the history ends that many days
+        earlier (the real-time prices of a bid made at the RUC hour)"""
         import torch
         if self.forecaster == "perfect":
             return self._window(series, T)[:, None, :]
         D = self.D
-        d = torch.div(self.hour_t, 24, rounding_mode="floor")
+        d = torch.div(self._clk, 24, rounding_mode="floor")
+        if lag_days:
+            d = d - lag_days
         i, t = torch.arange(self.S, device=self.dev)[:, None], torch.arange(T, device=self.dev)[None, :]
         pos = (24 * (D - 1 - i) + hod + t) % (24 * D)
         return series[(self.start[:, None, None] + 24 * (d - D) + pos[None]) % self.N]
@@ -731,10 +790,10 @@ class BatchedDoubleLoop:
         """per-plant values [B, ...] -> per-row [B * S, ...] (a plant's S rows are adjacent)"""
         return v if self.S == 1 else v.repeat_interleave(self.S, dim=0)
 
-    def _avail(self, m):
+    def _avail(self, m, offset=0):
         """wind availability of the window [B, T] and its sum accumulated in the order of t (the kernels' order: bit-identical constants)"""
         cols, _, per_kw = m.wind
-        avail = m.kw() * self._window(self.cf_series, m.T)
+        avail = m.kw() * self._window(self.cf_series, m.T, offset)
         total = avail[:, 0]
         for t in range(1, m.T):
             total = total + avail[:, t]
@@ -753,7 +812,7 @@ class BatchedDoubleLoop:
         else:
             c0 = m.base_c0_t.expand(rt.shape[0]) if m.c0_plant is None else self._rows(m.c0_plant)
         for j, col in enumerate(m.state_init):
-            v = self._rows(self.state[:, j])
+            v = self._rows(self._st[:, j])
             m.lb[:, col] = v
             m.ub[:, col] = v
         if m.wind is not None:
@@ -797,31 +856,42 @@ class BatchedDoubleLoop:
         curve.copy_(torch.stack([U.t().reshape(B, Tc, self.S + 1), M.t().reshape(B, Tc, self.S + 1)], dim=3))
         cnt.copy_(count.reshape(B, Tc))
 
-    def _day_ahead_step_stochastic(self):
+    def _day_ahead_step_stochastic(self, bid=False):
         """B * S day-ahead LPs (row b * S + i on scenario i's prices, plant b's state and wind, day_ahead_power free), one curve per
-        plant-hour from the S day_ahead_power values and day-ahead forecasts, cleared at the realised day-ahead price"""
+        plant-hour from the S day_ahead_power values and day-ahead forecasts, cleared at the realised day-ahead price.
+        bid: the bid made at the RUC hour for the next day - clock and state are the bid's (self._clk / self._st), the real-time
+        history is one day older, and offers, prices, curves and counts go to the pending buffers; the day's sums wait for midnight"""
         import ctypes as C
         import torch
         m, B, S = self.da, self.B, self.S
+        offer, prices = (self.pend_offer, self.pend_prices) if bid else (self.da_offer, self.da_prices)
+        curve, count_ = (self.pend_curve, self.pend_count) if bid else (self.da_curve, self.da_count)
         if self.use_fused:
-            self._market(self._lib.dsp_loop_market_prepare, C.byref(self._mk_da), -1)
+            self._market(self._lib.dsp_loop_market_prepare, C.byref(self._mk_da), -1, bid=bid)
         else:
-            da, rt = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T), self._forecast(self.rt_series, m.T, 0).expand(B, S, m.T)
+            da = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T)
+            rt = self._forecast(self.rt_series, m.T, 0, lag_days=int(bid)).expand(B, S, m.T)
             self._set_rows(m, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
             m.lb.index_fill_(1, m.pda_cols, 0.0)
             m.ub.index_fill_(1, m.pda_cols, float("inf"))
         out = m.solve(B * S)
         if self.use_fused:                            # (status / flags of the solve: folded into bad / uncertified by the kernel)
-            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_da), None, -1, 24, C.c_void_p(self.da_offer.data_ptr()),
-                         C.c_void_p(self.da_curve.data_ptr()), C.c_void_p(self.da_count.data_ptr()))
+            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_da), None, -1, 24, C.c_void_p(offer.data_ptr()),
+                         C.c_void_p(curve.data_ptr()), C.c_void_p(count_.data_ptr()), bid=bid)
         else:
             self._check(out)
             power = out["x"][:, m.pda_cols[:24]].reshape(B, S, 24)
             U, M, count = self._curves(power, self._forecast(self.da_series, 24, 0), out["status"])
             realised = self._window(self.da_series, 24)
-            self.da_offer.copy_(self._clear(U, M, count, realised))
-            self.da_prices.copy_(realised)
-            self._store_curves(self.da_curve, self.da_count, U, M, count)
+            offer.copy_(self._clear(U, M, count, realised))
+            prices.copy_(realised)
+            self._store_curves(curve, count_, U, M, count)
+        if not bid:
+            self._account_day_ahead()
+
+    def _account_day_ahead(self):
+        """the day's sums of the bid that is current: cleared and offered day-ahead energy (ruc_hour: when the bid BECOMES current)"""
+        import torch
         self.da_energy_mwh += self.da_offer.sum(1)
         last = torch.gather(self.da_curve[:, :, :, 0], 2, (self.da_count.to(torch.int64) - 1)[:, :, None])[:, :, 0]
         self.offered_mwh += (last.to(torch.float64) / self._hundred).sum(1)
@@ -987,8 +1057,112 @@ class BatchedDoubleLoop:
         g.replay()
 
     # -- the loop ----------------------------------------------------------------------------------------------------------------------
+    # -- bidding at the RUC hour (ruc_hour=H): projection tracker, pending bid, activation at midnight ----------------------------------
+    def _ruc_setup(self, pj):
+        """the projection tracker (a _Model of its own on the tracker's template: own buffers, own handle, own simplex basis - the
+        reference keeps a separate Tracker object for the same reason), the trace of its last chain, the pending bid, the bid clock"""
+        import torch
+        B, dev, L, ns = self.B, self.dev, 24 - self.ruc_hour, len(self.scale)
+        self.pj = pj
+        pj.track_rows, pj.state_real = self.tr.track_rows, self.tr.state_real
+        pj.kw_plant, pj.c0_plant = self.tr.kw_plant, self.tr.c0_plant      # per-plant sizes: the tracker's arrays (read only)
+        for name in ("lb", "ub", "rlo", "rhi"):                            # ... and its static battery bounds
+            getattr(pj, name).copy_(getattr(self.tr, name))
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        self.proj_state, self.proj_real, self.proj_obj = z(L + 1, B, ns), z(L, B, ns), z(L, B)
+        self.pend_offer, self.pend_prices = z(B, 24), z(B, 24)
+        self.bid_hour_t = torch.zeros((), dtype=torch.int64, device=dev)   # the bid clock: hour 0 of the day the pending bid is for
+        if self.stochastic:
+            self.pend_curve, self.pend_count = torch.zeros_like(self.da_curve), torch.zeros_like(self.da_count)
+        self._pending = False
+
+    def _project(self, phase, j):
+        import ctypes as C
+        import torch
+        rc = self._lib.dsp_loop_project(C.byref(self._proj_state_c), C.byref(self._loop_pj), phase, j,
+                                        C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"dsp_loop_project failed ({rc})")
+
+    def _project_write(self, j):
+        """the projection tracker's LP of chain step j (the window that starts at clock + j): dispatch rows inside the day on the
+        current day-ahead dispatch, rows past midnight free on both sides (Tracker._pass_market_dispatch on a short list), state
+        columns fixed to proj_state[j], wind and c0 as _set_tracker"""
+        if self.use_fused:
+            self._project(0, j)
+            return
+        pj, H = self.pj, self.ruc_hour
+        if j == 0:
+            self.proj_state[0].copy_(self.state)
+        known = min(pj.T, 24 - H - j)
+        rhs = self.da_offer[:, H + j:H + j + known] - pj.PT_const[:known]
+        pj.rlo[:, pj.track_rows[:known]] = rhs
+        pj.rhi[:, pj.track_rows[:known]] = rhs
+        if known < pj.T:
+            pj.rlo[:, pj.track_rows[known:]] = float("-inf")
+            pj.rhi[:, pj.track_rows[known:]] = float("inf")
+        for e, col in enumerate(pj.state_init):
+            pj.lb[:, col] = self.proj_state[j, :, e]
+            pj.ub[:, col] = self.proj_state[j, :, e]
+        if pj.wind is not None:
+            cols, avail, waste = self._avail(pj, offset=j)
+            pj.ub[:, cols] = avail
+            pj.c0.copy_((pj.base_c0 if pj.c0_plant is None else pj.c0_plant) + waste)
+        else:
+            pj.c0.fill_(pj.base_c0)
+
+    def _project_hand_off(self, j, out):
+        import torch
+        if self.use_fused:
+            self._project(1, j)
+            return
+        self._check(out)
+        for e, col in enumerate(self.pj.state_real):
+            real = out["x"][:, col]
+            self.proj_real[j, :, e] = real
+            self.proj_state[j + 1, :, e] = torch.round(real * self.scale[e]) / self._scale_t[e]
+        self.proj_obj[j].copy_(out["obj"] + self.pj.c0)
+
+    def _ruc_step(self):
+        """hour H of day d, before that hour's real-time step: the projection chain to midnight (flowsheets with state), then the
+        day-ahead bid of day d + 1 on the projected state, into the pending buffers"""
+        import torch
+        pj, B, H = self.pj, self.B, self.ruc_hour
+        if len(self.scale):
+            for j in range(24 - H):
+                self._project_write(j)
+                hour = (0 if j == 0 else 1) if self.simplex_warm else None         # step 0 from the slack basis, then from the step before
+                out = pj.solve(B, hour=hour) if pj.opts is not None else pj.solve(B)
+                self._project_hand_off(j, out)
+        torch.add(self.hour_t, 24 - H, out=self.bid_hour_t)
+        self._clk, self._st = self.bid_hour_t, self.proj_state[-1]
+        try:
+            if self.stochastic:
+                self._day_ahead_step_stochastic(bid=True)
+            else:
+                self._day_ahead_step(bid=True)
+        finally:
+            self._clk, self._st = self.hour_t, self.state
+
+    def _activate(self):
+        """midnight: the pending bid becomes the current one (DoubleLoopCoordinator.activate_pending_DA_bids)"""
+        if self.use_fused:
+            self._project(2, 0)
+        else:
+            self.da_offer.copy_(self.pend_offer)
+            self.da_prices.copy_(self.pend_prices)
+            if self.stochastic:
+                self.da_curve.copy_(self.pend_curve)
+                self.da_count.copy_(self.pend_count)
+        if self.stochastic:
+            self._account_day_ahead()
+
     def day_ahead(self):
         self.day_start = self.hour
+        if self.ruc_hour is not None and self._pending:                    # day d >= 1: nothing to solve, yesterday's bid takes over
+            self._run("activate", self._activate)
+            self._pending = False
+            return self.da_offer.clone()
         if self.parametrized:
             self._run("da", self._day_ahead_step_parametrized)
             return self.da_offer.clone()
@@ -1002,7 +1176,13 @@ class BatchedDoubleLoop:
             self._run(k, lambda: self._hour_step_parametrized(k))
             self.solves += self.B
         else:
-            self._run(k, (lambda: self._hour_step_stochastic(k)) if self.stochastic else (lambda: self._hour_step(k)))
+            step = (lambda: self._hour_step_stochastic(k)) if self.stochastic else (lambda: self._hour_step(k))
+            if k == self.ruc_hour:
+                self._run(k, lambda: (self._ruc_step(), step()))
+                self.solves += self.B * self.S + (self.B * (24 - k) if len(self.scale) else 0)
+                self._pending = True
+            else:
+                self._run(k, step)
             self.solves += self.B * self.S + self.B
         self.hour += 1
         return self.delivered.clone()
@@ -1021,6 +1201,12 @@ class BatchedDoubleLoop:
             self.da_energy_mwh.zero_(), self.offered_mwh.zero_()
         if self.parametrized and self.h2_kg is not None:
             self.h2_kg.zero_()
+        if self.ruc_hour is not None:
+            for t in (self.proj_state, self.proj_real, self.proj_obj, self.pend_offer, self.pend_prices, self.bid_hour_t):
+                t.zero_()
+            if self.stochastic:
+                self.pend_curve.zero_(), self.pend_count.zero_()
+            self._pending = False
         self.hour = self.solves = 0
 
     def results(self):

@@ -18,6 +18,12 @@
  * (dsp_solve).  Plain C, opaque handle, caller-owned buffers, int return codes, stream-ordered.
  * All per-scenario pointers in dsp_batch / dsp_spmv_step are DEVICE pointers (e.g. torch.Tensor.data_ptr());
  * everything in dsp_lp_desc is a HOST pointer that is copied during dsp_create.
+ *
+ * The rolling double loops on top of it (dsp_wb_rolling_update, dsp_loop_update, dsp_loop_market_*, dsp_loop_param_step) write the LPs
+ * of a simulated hour from device-resident series and state.  ABI 17 adds the reference's day-ahead timeline to the descriptor loop:
+ * dsp_loop_project runs the coordinator's projection tracker (bid_into_DAM: the rest of today's cleared day-ahead dispatch tracked to
+ * midnight, free dispatch rows past it) and makes the bid computed at the RUC hour current at midnight;
+ * dsp_loop_market_state::rt_history_lag_days ages the real-time backcast of that bid by the day that is not complete yet.
  */
 #ifndef DSP_HIP_H
 #define DSP_HIP_H
@@ -30,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 16
+#define DSP_VERSION 17
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -540,6 +546,10 @@ typedef struct dsp_loop_market_state {
   uint8_t *bad;                        /* [1] or NULL                                                                             */
   int64_t *uncertified;                /* [1] or NULL                                                                             */
   int64_t p_min_cents;                 /* minimum power of the generator in integer cents (>= 0)                                  */
+  int32_t rt_history_lag_days;         /* (ABI 17) backcast only: the REAL-TIME scenarios come from a history that ends this many
+                                          days earlier (0: as before, bit for bit; 1: a bid made at the RUC hour for the next day,
+                                          when today is not a whole day of real-time prices yet).  >= 0, 24 (D + lag) <= N          */
+  int32_t reserved;
 } dsp_loop_market_state;
 
 /* Scenario fan-out of bidding model `m` (B * S rows), one lane per row.  k = -1: the day-ahead LP (day_ahead_power free in every period);
@@ -603,6 +613,47 @@ typedef struct dsp_loop_param_state {
  * state column outside [0, tr->n), n_state outside 0 .. 2 or > 0 with a NULL state, NULL rlo / rhi / lb / ub / c0; phase 2: NULL
  * h2_kg or tr->x, pem_col outside [0, tr->n); a phase outside 0 .. 2 or a k that does not belong to it. */
 int dsp_loop_param_step(const dsp_loop_param_state *st, const dsp_loop_model *tr, int32_t phase, int32_t k, void *hipStream);
+
+/* Day-ahead bidding at the RUC hour on a PROJECTED state (ABI 17; dispatches_amd/rolling_flowsheets.py: BatchedDoubleLoop with
+ * ruc_hour=H, 1 <= H <= 23).  In the reference the day-ahead market of day d + 1 runs at hour H of day d: the coordinator clones the
+ * tracker into a projection tracker, tracks the not yet delivered part of today's cleared day-ahead dispatch to midnight and hands the
+ * projected state to the day-ahead bidder (DoubleLoopCoordinator.bid_into_DAM; workflow/coordinator.py::_project_tracking_trajectory).
+ * `pj` is that projection tracker: a dsp_loop_model of its own (own buffers, own solver handle) on the tracker's template.
+ * Chain step j = 0 .. 24 - H - 1, at loop clock *hour = 24 d + H:
+ *   phase 0 (write, before the solve), one lane per (plant, period t < pj->T):
+ *            dispatch row t = da_offer[b][H + j + t] - pj->pt_const[t] where H + j + t < 24, free on both sides (-inf, +inf) past
+ *            midnight; by the lane of period 0: state columns = state[b] (j = 0, also copied to proj_state[0]) or proj_state[j][b],
+ *            wind upper bounds of the window that starts at clock + j, c0 = c0_base + waste_per_kw * sum_t availability (the tracker
+ *            half of dsp_loop_market_clear, per-plant sizes included).
+ *   phase 1 (hand-off, after the solve), one lane per plant: status / flags -> bad / uncertified; proj_real[j][b] = x[state_real];
+ *            proj_state[j + 1][b] = rint(x[state_real] * state_scale) / state_scale; proj_obj[j][b] = obj[b] + c0[b].
+ *   phase 2 (activate, midnight; j = 0; pj is not touched and may be NULL), one lane per (plant, hour of 24): pend_offer ->
+ *            da_offer, pend_prices -> da_prices and, with slots > 0, pend_curve / pend_count -> da_curve / da_count.
+ * DSP_ERR_INVALID, nothing launched and nothing written, for: B < 1; N < 1; ruc_hour outside 1 .. 23; a phase outside 0 .. 2; j outside
+ * 0 .. 24 - ruc_hour - 1 (phase 2: j != 0); a NULL pointer the phase uses; phases 0 / 1: pj->T outside 1 .. DSP_LOOP_MAX_T, n_state
+ * outside 0 .. 2, a dispatch row outside [0, pj->m), a wind, state_init or state_real column outside [0, pj->n), wind columns with a
+ * NULL cf_series, one per-plant pointer without the other or without wind columns; phase 2: slots < 0 or > DSP_MARKET_MAX_S + 1. */
+typedef struct dsp_loop_project_state {
+  int32_t B, N;
+  int32_t ruc_hour;                    /* H: hour of the day at which the chain starts                                            */
+  int32_t slots;                       /* points per stored curve (S + 1); 0 = the loop keeps no curves (deterministic mode)      */
+  const int64_t *start;                /* [B]                                                                                     */
+  const int64_t *hour;                 /* [1] the loop's clock (read only here)                                                   */
+  const double *cf_series;             /* [N] or NULL without wind                                                                */
+  const double *state;                 /* [B][n_state] realised state (NULL with n_state = 0)                                     */
+  double state_scale[2];
+  const double *obj;                   /* [B] objective of pj's last solve, without its constant                                  */
+  double *proj_state;                  /* [24 - H + 1][B][n_state] the trace: entry 0 realised, the last one what the bid uses    */
+  double *proj_real;                   /* [24 - H][B][n_state] unrounded                                                          */
+  double *proj_obj;                    /* [24 - H][B] objective including c0                                                      */
+  uint8_t *bad;                        /* as dsp_loop_state                                                                       */
+  int64_t *uncertified;
+  double *da_offer, *da_prices;        /* [B][24] current day: da_offer read by phase 0, both written by phase 2                  */
+  const double *pend_offer, *pend_prices;            /* [B][24] the bid made at the RUC hour for the next day                     */
+  int32_t *da_curve, *da_count;        /* [B][24][slots][2], [B][24] (slots > 0)                                                  */
+  const int32_t *pend_curve, *pend_count;
+} dsp_loop_project_state;
+int dsp_loop_project(const dsp_loop_project_state *st, const dsp_loop_model *pj, int32_t phase, int32_t j, void *hipStream);
 
 /* Introspection */
 int dsp_get_dims(const dsp_handle *h, int32_t *n, int32_t *m, int64_t *nnz);
