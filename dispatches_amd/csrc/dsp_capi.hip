@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "dsp_device.hpp"
+#include "dsp_loop_device.hpp"
 #include "dsp_prepare.hpp"
 #include "dsp_rtc.hpp"
 #include "dsp_stream.hpp"
@@ -168,8 +169,8 @@ static int solve_geometry(dsp_handle *h, int requested, int B, Geometry *g, int 
 }
 
 // ---- rolling-horizon hand-off of the wind + battery double loop: one thread per plant ------------------------------------------
-// Every product is made opaque to the optimiser before it is added (no FMA contraction: the _rn intrinsics are plain
-// operators to the compiler and `#pragma clang fp contract(off)` did not keep it from fusing them): the results are
+// Every product is made opaque to the optimiser before it is added (loop_opaque, dsp_loop_device.hpp: no FMA contraction - the _rn
+// intrinsics are plain operators to the compiler and `#pragma clang fp contract(off)` did not keep it from fusing them): the results are
 // bit-identical to the element-wise tensor operations this kernel replaces (dispatches_amd/rolling.py, use_fused=False),
 // which is how it is tested.
 // outcome of the solve that has just finished, folded into the loop's device-side flags (what six tensor launches per solve did)
@@ -179,7 +180,6 @@ __device__ __forceinline__ void loop_check(const S &s, const M &m, int b) {
   if (m.flags && s.uncertified && (m.flags[b] & DSP_FLAG_OBJ_WAIVED)) atomicAdd(reinterpret_cast<unsigned long long *>(s.uncertified), 1ull);
 }
 
-__device__ __forceinline__ double wb_opaque(double v) { asm volatile("" : "+v"(v)); return v; }
 __global__ void __launch_bounds__(256) wb_rolling_kernel(dsp_wb_state s, dsp_wb_model rt, dsp_wb_model tr, int phase, int k) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= s.B) return;
@@ -193,10 +193,10 @@ __global__ void __launch_bounds__(256) wb_rolling_kernel(dsp_wb_state s, dsp_wb_
     for (int t = 0; t < m.T; ++t) {
       const double rtp = win(s.rt_series, t);
       const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : win(s.da_series, t);
-      const double r3 = wb_opaque(__dmul_rn(1e-3, rtp));
+      const double r3 = loop_opaque(__dmul_rn(1e-3, rtp));
       c[m.pt_cols[t][0]] = __dsub_rn(m.base_c[m.pt_cols[t][0]], r3);
       c[m.pt_cols[t][1]] = __dsub_rn(m.base_c[m.pt_cols[t][1]], r3);
-      c[m.pda_cols[t]] = __dsub_rn(m.base_c[m.pda_cols[t]], wb_opaque(__dsub_rn(dap, rtp)));
+      c[m.pda_cols[t]] = __dsub_rn(m.base_c[m.pda_cols[t]], loop_opaque(__dsub_rn(dap, rtp)));
       const double avail = __dmul_rn(m.wind_kw, win(s.cf_series, t));
       ub[m.wind_cols[t]] = avail;
       avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
@@ -204,7 +204,7 @@ __global__ void __launch_bounds__(256) wb_rolling_kernel(dsp_wb_state s, dsp_wb_
       lb[m.pda_cols[t]] = fix;
       ub[m.pda_cols[t]] = t < known ? fix : INFINITY;
     }
-    if (m.c0) m.c0[b] = __dadd_rn(m.c0_base, wb_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
+    if (m.c0) m.c0[b] = __dadd_rn(m.c0_base, loop_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
     lb[m.soc_init] = s.soc[b]; ub[m.soc_init] = s.soc[b];
     lb[m.thr_init] = s.thr[b]; ub[m.thr_init] = s.thr[b];
   } else if (phase == 1) {
@@ -214,27 +214,27 @@ __global__ void __launch_bounds__(256) wb_rolling_kernel(dsp_wb_state s, dsp_wb_
     double *rlo = tr.rlo + (size_t)b * tr.m, *rhi = tr.rhi + (size_t)b * tr.m;
     double avail_sum = 0.0;
     for (int t = 0; t < tr.T; ++t) {
-      const double offer = __dmul_rn(1e-3, wb_opaque(__dadd_rn(xr[rt.pt_cols[t][0]], xr[rt.pt_cols[t][1]])));
+      const double offer = __dmul_rn(1e-3, loop_opaque(__dadd_rn(xr[rt.pt_cols[t][0]], xr[rt.pt_cols[t][1]])));
       rlo[tr.track_rows[t]] = offer;
       rhi[tr.track_rows[t]] = offer;
       const double avail = __dmul_rn(tr.wind_kw, win(s.cf_series, t));
       ub[tr.wind_cols[t]] = avail;
       avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
     }
-    if (tr.c0) tr.c0[b] = __dadd_rn(tr.c0_base, wb_opaque(__dmul_rn(tr.waste_per_kw, avail_sum)));
+    if (tr.c0) tr.c0[b] = __dadd_rn(tr.c0_base, loop_opaque(__dmul_rn(tr.waste_per_kw, avail_sum)));
     lb[tr.soc_init] = s.soc[b]; ub[tr.soc_init] = s.soc[b];
     lb[tr.thr_init] = s.thr[b]; ub[tr.thr_init] = s.thr[b];
   } else {
     loop_check(s, tr, b);
     const double *x = tr.x + (size_t)b * tr.n;
-    const double delivered = wb_opaque(__dmul_rn(1e-3, wb_opaque(__dadd_rn(x[tr.pt_cols[0][0]], x[tr.pt_cols[0][1]]))));
+    const double delivered = loop_opaque(__dmul_rn(1e-3, loop_opaque(__dadd_rn(x[tr.pt_cols[0][0]], x[tr.pt_cols[0][1]]))));
     const double rt0 = win(s.rt_series, 0);
     s.delivered[b] = delivered;
-    s.soc[b] = __ddiv_rn(rint(wb_opaque(__dmul_rn(x[tr.soc0], 100.0))), 100.0);
-    s.thr[b] = __ddiv_rn(rint(wb_opaque(__dmul_rn(x[tr.thr0], 100.0))), 100.0);
+    s.soc[b] = __ddiv_rn(rint(loop_opaque(__dmul_rn(x[tr.soc0], 100.0))), 100.0);
+    s.thr[b] = __ddiv_rn(rint(loop_opaque(__dmul_rn(x[tr.thr0], 100.0))), 100.0);
     const double dao = s.da_offer[(size_t)b * 24 + k], dap = s.da_prices[(size_t)b * 24 + k];
-    const double t1 = wb_opaque(__dmul_rn(delivered, rt0)), t2 = wb_opaque(__dmul_rn(dao, wb_opaque(__dsub_rn(dap, rt0))));
-    s.revenue[b] = __dadd_rn(s.revenue[b], wb_opaque(__dadd_rn(t1, t2)));
+    const double t1 = loop_opaque(__dmul_rn(delivered, rt0)), t2 = loop_opaque(__dmul_rn(dao, loop_opaque(__dsub_rn(dap, rt0))));
+    s.revenue[b] = __dadd_rn(s.revenue[b], loop_opaque(__dadd_rn(t1, t2)));
     s.energy_mwh[b] = __dadd_rn(s.energy_mwh[b], delivered);
   }
 }
@@ -335,14 +335,55 @@ int dsp_wb_rolling_update(const dsp_wb_state *st, const dsp_wb_model *rt, const 
   return DSP_OK;
 }
 
+// ---- descriptors checked on the host: every index a lane would use lies inside its buffer, nothing is launched otherwise ----
+static bool market_col_ok(int32_t col, int32_t n) { return col >= 0 && col < n; }
+static bool loop_cols_ok(const int32_t *cols, int count, int32_t n) {
+  for (int i = 0; i < count; ++i)
+    if (!market_col_ok(cols[i], n)) return false;
+  return true;
+}
+// the <= 2 terms of the power output of T periods: a column of the LP, or -1 for "no such term"
+static bool loop_terms_ok(const int32_t (*pt_cols)[2], int T, int32_t n) {
+  for (int t = 0; t < T; ++t)
+    for (int e = 0; e < 2; ++e)
+      if (pt_cols[t][e] != -1 && !market_col_ok(pt_cols[t][e], n)) return false;
+  return true;
+}
+// wind columns of T periods (none: wind_cols[0] < 0) need the capacity factors
+static bool loop_wind_ok(const int32_t *wind_cols, int T, int32_t n, const void *cf_series) {
+  return wind_cols[0] < 0 || (cf_series && loop_cols_ok(wind_cols, T, n));
+}
+// per-plant sizes (ABI 16): both pointers or neither, and only on a model that has wind columns
+static bool plant_sizes_ok(const double *wind_kw_plant, const double *c0_base_plant, int32_t wind_col0) {
+  if (!wind_kw_plant != !c0_base_plant) return false;
+  return !wind_kw_plant || wind_col0 >= 0;
+}
+// the indices of a tracker of horizon T whose dispatch rows and plant half (loop_tracker_plant) a kernel writes
+static bool loop_tracker_cols_ok(const dsp_loop_model *tr, int T, const void *state, const void *cf_series) {
+  if (tr->n_state < 0 || tr->n_state > 2 || (tr->n_state > 0 && !state)) return false;
+  return loop_cols_ok(tr->state_init, tr->n_state, tr->n) && loop_cols_ok(tr->track_rows, T, tr->m) && loop_wind_ok(tr->wind_cols, T, tr->n, cf_series) &&
+         plant_sizes_ok(tr->wind_kw_plant, tr->c0_base_plant, tr->wind_cols[0]);
+}
+// ... and its buffers: safe to launch a kernel that writes the tracker's LP
+static bool loop_tracker_ok(const dsp_loop_model *tr, int T, const void *state, const void *cf_series) {
+  if (!tr || T < 1 || T > DSP_LOOP_MAX_T || tr->T != T || tr->n < 1 || tr->m < 1) return false;
+  if (!tr->lb || !tr->ub || !tr->rlo || !tr->rhi || !tr->c0) return false;
+  return loop_tracker_cols_ok(tr, T, state, cf_series);
+}
+
 int dsp_loop_update(const dsp_loop_state *st, const dsp_loop_model *rt, const dsp_loop_model *tr, int32_t phase, int32_t k, void *hipStream) {
   if (!st || !rt || !tr || st->B < 0 || phase < 0 || phase > 2 || k < 0 || k > 23 || rt->T < 1 || rt->T > DSP_LOOP_MAX_T || tr->T < 1 ||
-      tr->T > DSP_LOOP_MAX_T || rt->n_state < 0 || rt->n_state > 2 || tr->n_state != rt->n_state || !rt->c0 || !tr->c0 ||
-      ((rt->wind_cols[0] >= 0 || tr->wind_cols[0] >= 0) && !st->cf_series))
+      tr->T > DSP_LOOP_MAX_T || rt->n_state < 0 || rt->n_state > 2 || tr->n_state != rt->n_state || !rt->c0 || !tr->c0)
     return DSP_ERR_INVALID;
   // per-plant sizes (ABI 16): both pointers or neither on each model, the two models together, only with wind columns
-  if (!rt->wind_kw_plant != !rt->c0_base_plant || !tr->wind_kw_plant != !tr->c0_base_plant || !rt->wind_kw_plant != !tr->wind_kw_plant ||
-      (rt->wind_kw_plant && (rt->wind_cols[0] < 0 || tr->wind_cols[0] < 0)))
+  if (!plant_sizes_ok(rt->wind_kw_plant, rt->c0_base_plant, rt->wind_cols[0]) || !rt->wind_kw_plant != !tr->wind_kw_plant) return DSP_ERR_INVALID;
+  // every index of the three phases.  The tracker follows the first tr->T periods of the real-time offer (phase 2 reads the tracker
+  // alone: the parametrized mode, which has no real-time LP, calls it with tracking horizons beyond the real-time one)
+  if ((phase < 2 && tr->T > rt->T) || !loop_tracker_cols_ok(tr, tr->T, st->state, st->cf_series) || !loop_cols_ok(tr->state_real, tr->n_state, tr->n) ||
+      !loop_terms_ok(tr->pt_cols, tr->T, tr->n))
+    return DSP_ERR_INVALID;
+  if (!loop_cols_ok(rt->pda_cols, rt->T, rt->n) || !loop_terms_ok(rt->pt_cols, rt->T, rt->n) || !loop_cols_ok(rt->state_init, rt->n_state, rt->n) ||
+      !loop_wind_ok(rt->wind_cols, rt->T, rt->n, st->cf_series))
     return DSP_ERR_INVALID;
   if (st->B == 0) return DSP_OK;
   hipStream_t s = (hipStream_t)hipStream;
@@ -370,13 +411,6 @@ static bool market_state_ok(const dsp_market_state *st) {
   if (st->backcast ? (st->D < 1 || st->S > st->D || 24ll * st->D > st->N) : st->S != 1) return false;
   return st->start && st->hour && st->da_series && st->rt_series;
 }
-static bool market_col_ok(int32_t col, int32_t n) { return col >= 0 && col < n; }
-// per-plant sizes (ABI 16): both pointers or neither, and only on a model that has wind columns
-static bool plant_sizes_ok(const double *wind_kw_plant, const double *c0_base_plant, int32_t wind_col0) {
-  if (!wind_kw_plant != !c0_base_plant) return false;
-  return !wind_kw_plant || wind_col0 >= 0;
-}
-
 int dsp_market_prepare(const dsp_market_state *st, const dsp_market_model *m, int32_t k, void *hipStream) {
   if (!market_state_ok(st) || !m || k < -1 || k > 23 || m->n < 1 || m->T < 1 || m->T > DSP_MARKET_MAX_T) return DSP_ERR_INVALID;
   if (!st->cf_series || !st->soc || !st->thr || !m->c || !m->lb || !m->ub || !m->base_c) return DSP_ERR_INVALID;
@@ -425,17 +459,9 @@ int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_mark
   if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < -1 || k > 23) return DSP_ERR_INVALID;
   if (!m->c || !m->lb || !m->ub || !m->base_c || !m->c0) return DSP_ERR_INVALID;
   if (k >= 0 && (!st->da_offer || !st->da_prices)) return DSP_ERR_INVALID;
-  if (m->n_state > 0 && !st->state) return DSP_ERR_INVALID;
-  for (int j = 0; j < m->n_state; ++j)
-    if (!market_col_ok(m->state_init[j], m->n)) return DSP_ERR_INVALID;
-  const bool wind = m->wind_cols[0] >= 0;
-  if (wind && !st->cf_series) return DSP_ERR_INVALID;
-  if (!plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return DSP_ERR_INVALID;
-  for (int t = 0; t < m->T; ++t) {
-    if (!market_col_ok(m->pda_cols[t], m->n) || (wind && !market_col_ok(m->wind_cols[t], m->n))) return DSP_ERR_INVALID;
-    for (int e = 0; e < 2; ++e)
-      if (m->pt_cols[t][e] != -1 && !market_col_ok(m->pt_cols[t][e], m->n)) return DSP_ERR_INVALID;
-  }
+  if ((m->n_state > 0 && !st->state) || !loop_cols_ok(m->state_init, m->n_state, m->n)) return DSP_ERR_INVALID;
+  if (!loop_wind_ok(m->wind_cols, m->T, m->n, st->cf_series) || !plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return DSP_ERR_INVALID;
+  if (!loop_cols_ok(m->pda_cols, m->T, m->n) || !loop_terms_ok(m->pt_cols, m->T, m->n)) return DSP_ERR_INVALID;
   if (st->B == 0) return DSP_OK;
   HIP_TRY(launch_loop_market_prepare(*st, *m, (int)k, (hipStream_t)hipStream));
   return DSP_OK;
@@ -447,25 +473,8 @@ int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market
   if (!m->x || !m->status || !dispatch || !curve || !count) return DSP_ERR_INVALID;
   if (k < 0 ? (T > 24 || !st->da_prices || tr) : T > DSP_LOOP_MAX_T) return DSP_ERR_INVALID;
   if (!plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return DSP_ERR_INVALID;
-  if (tr && (!plant_sizes_ok(tr->wind_kw_plant, tr->c0_base_plant, tr->wind_cols[0]) || !tr->wind_kw_plant != !m->wind_kw_plant)) return DSP_ERR_INVALID;
-  for (int t = 0; t < T; ++t) {
-    if (k < 0) {
-      if (!market_col_ok(m->pda_cols[t], m->n)) return DSP_ERR_INVALID;
-    } else {
-      for (int e = 0; e < 2; ++e)
-        if (m->pt_cols[t][e] != -1 && !market_col_ok(m->pt_cols[t][e], m->n)) return DSP_ERR_INVALID;
-    }
-  }
-  if (tr) {
-    if (tr->T != T || tr->n < 1 || tr->m < 1 || tr->n_state != m->n_state || !tr->lb || !tr->ub || !tr->rlo || !tr->rhi || !tr->c0) return DSP_ERR_INVALID;
-    if (tr->n_state > 0 && !st->state) return DSP_ERR_INVALID;
-    for (int j = 0; j < tr->n_state; ++j)
-      if (!market_col_ok(tr->state_init[j], tr->n)) return DSP_ERR_INVALID;
-    const bool wind = tr->wind_cols[0] >= 0;
-    if (wind && !st->cf_series) return DSP_ERR_INVALID;
-    for (int t = 0; t < T; ++t)
-      if (!market_col_ok(tr->track_rows[t], tr->m) || (wind && !market_col_ok(tr->wind_cols[t], tr->n))) return DSP_ERR_INVALID;
-  }
+  if (k < 0 ? !loop_cols_ok(m->pda_cols, T, m->n) : !loop_terms_ok(m->pt_cols, T, m->n)) return DSP_ERR_INVALID;
+  if (tr && (!loop_tracker_ok(tr, T, st->state, st->cf_series) || tr->n_state != m->n_state || !tr->wind_kw_plant != !m->wind_kw_plant)) return DSP_ERR_INVALID;
   if (st->B == 0) return DSP_OK;
   HIP_TRY(launch_loop_market_clear(*st, *m, tr, (int)k, (int)T, dispatch, curve, count, (hipStream_t)hipStream));
   return DSP_OK;
@@ -483,13 +492,7 @@ int dsp_loop_param_step(const dsp_loop_param_state *st, const dsp_loop_model *tr
     if (!st->da_offer || !st->da_prices || !st->da_curve || !st->da_count) return DSP_ERR_INVALID;
   } else if (phase == 1) {
     if (!st->rt_dispatch || !st->rt_curve || !st->rt_count) return DSP_ERR_INVALID;
-    if (tr->n < 1 || tr->m < 1 || tr->n_state < 0 || tr->n_state > 2 || !tr->lb || !tr->ub || !tr->rlo || !tr->rhi || !tr->c0) return DSP_ERR_INVALID;
-    if (tr->n_state > 0 && !st->state) return DSP_ERR_INVALID;
-    for (int j = 0; j < tr->n_state; ++j)
-      if (!market_col_ok(tr->state_init[j], tr->n)) return DSP_ERR_INVALID;
-    const bool wind = tr->wind_cols[0] >= 0;
-    for (int t = 0; t < tr->T; ++t)
-      if (!market_col_ok(tr->track_rows[t], tr->m) || (wind && !market_col_ok(tr->wind_cols[t], tr->n))) return DSP_ERR_INVALID;
+    if (!loop_tracker_ok(tr, tr->T, st->state, st->rt_cf_series)) return DSP_ERR_INVALID;
   } else {
     if (!st->h2_kg || !tr->x || tr->n < 1 || !market_col_ok(st->pem_col, tr->n)) return DSP_ERR_INVALID;
   }
@@ -511,13 +514,7 @@ int dsp_loop_project(const dsp_loop_project_state *st, const dsp_loop_model *pj,
   if (!st->start || !st->hour || (pj->n_state > 0 && (!st->state || !st->proj_state))) return DSP_ERR_INVALID;      // (no state: empty traces may be NULL)
   if (!plant_sizes_ok(pj->wind_kw_plant, pj->c0_base_plant, pj->wind_cols[0])) return DSP_ERR_INVALID;
   if (phase == 0) {
-    if (!st->da_offer || !pj->lb || !pj->ub || !pj->rlo || !pj->rhi || !pj->c0) return DSP_ERR_INVALID;
-    const bool wind = pj->wind_cols[0] >= 0;
-    if (wind && !st->cf_series) return DSP_ERR_INVALID;
-    for (int e = 0; e < pj->n_state; ++e)
-      if (!market_col_ok(pj->state_init[e], pj->n)) return DSP_ERR_INVALID;
-    for (int t = 0; t < pj->T; ++t)
-      if (!market_col_ok(pj->track_rows[t], pj->m) || (wind && !market_col_ok(pj->wind_cols[t], pj->n))) return DSP_ERR_INVALID;
+    if (!st->da_offer || !loop_tracker_ok(pj, pj->T, st->state, st->cf_series)) return DSP_ERR_INVALID;
   } else {
     if (!pj->x || !pj->status || !pj->c0 || !st->obj || (pj->n_state > 0 && !st->proj_real) || !st->proj_obj) return DSP_ERR_INVALID;
     for (int e = 0; e < pj->n_state; ++e)

@@ -17,30 +17,22 @@
 //   loop_market_prepare_kernel / loop_market_clear_kernel   the same two for ANY flowsheet, by descriptor (dsp_loop_market_*; rolling_flowsheets.py):
 //                           power P_T = (x[a] ca + x[b] cb) + const, curves that start at the generator's p_min, <= 2 state columns,
 //                           optional wind; the clearing lanes also write the tracker's LP (a dsp_loop_model).  VGPRs / scratch of every
-//                           instantiation: profiles/loop_market_kernel_resources.txt.
+//                           instantiation: profiles/loop_device_kernel_resources.txt.
 //
-// Every product is made opaque before it is added (as in wb_rolling_kernel, dsp_capi.hip): the results are bit-identical to the
-// tensor operations of dispatches_amd/rolling.py (use_fused=False), which is how the kernels are tested.
+// What the clearing kernels share with each other and with dsp_param.hip / dsp_project.hip lives in dsp_loop_device.hpp: the register
+// barrier, the scenario index, sorted keys -> curve and cleared dispatch (loop_curve_and_clear, the wind + battery curve with
+// p_min = 0), the wind window with its objective constant, and the plant half of the descriptor tracker's LP (loop_tracker_plant).
+// Every product is made opaque before it is added: the results are bit-identical to the tensor operations of
+// dispatches_amd/rolling.py / rolling_flowsheets.py (use_fused=False), which is how the kernels are tested.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/dsp_hip.h"
-#include "dsp_bid_cents.hpp"
 #include "dsp_device.hpp"
+#include "dsp_loop_device.hpp"
 
 namespace dsp {
-
-__device__ __forceinline__ double mk_opaque(double v) { asm volatile("" : "+v"(v)); return v; }
-
-// index into the circular series of the price scenario i of plant (start st0) asked at hour-of-day hod for period t (clock h)
-__device__ __forceinline__ long long mk_index(const dsp_market_state &s, long long st0, long long h, int i, int hod, int t) {
-  if (!s.backcast) return (st0 + h + t) % s.N;
-  const long long D = s.D, d = h / 24;
-  const long long pos = (24 * (D - 1 - i) + hod + t) % (24 * D);
-  long long v = (st0 + 24 * (d - D) + pos) % s.N;
-  return v < 0 ? v + s.N : v;
-}
 
 __global__ void __launch_bounds__(256) market_prepare_kernel(dsp_market_state s, dsp_market_model m, int k) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -52,20 +44,20 @@ __global__ void __launch_bounds__(256) market_prepare_kernel(dsp_market_state s,
   double *c = m.c + (size_t)r * m.n, *lb = m.lb + (size_t)r * m.n, *ub = m.ub + (size_t)r * m.n;
   double avail_sum = 0.0;
   for (int t = 0; t < m.T; ++t) {
-    const double rtp = s.rt_series[mk_index(s, st0, h, i, hod, t)];
-    const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : s.da_series[mk_index(s, st0, h, i, hod, t)];
-    const double r3 = mk_opaque(__dmul_rn(1e-3, rtp));
+    const double rtp = s.rt_series[loop_scenario_index(s, st0, h, i, hod, t)];
+    const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : s.da_series[loop_scenario_index(s, st0, h, i, hod, t)];
+    const double r3 = loop_opaque(__dmul_rn(1e-3, rtp));
     c[m.pt_cols[t][0]] = __dsub_rn(m.base_c[m.pt_cols[t][0]], r3);
     c[m.pt_cols[t][1]] = __dsub_rn(m.base_c[m.pt_cols[t][1]], r3);
-    c[m.pda_cols[t]] = __dsub_rn(m.base_c[m.pda_cols[t]], mk_opaque(__dsub_rn(dap, rtp)));
-    const double avail = mk_opaque(__dmul_rn(m.wind_kw, s.cf_series[(st0 + h + t) % s.N]));      // capacity factors: the realised window
+    c[m.pda_cols[t]] = __dsub_rn(m.base_c[m.pda_cols[t]], loop_opaque(__dsub_rn(dap, rtp)));
+    const double avail = loop_opaque(__dmul_rn(m.wind_kw, s.cf_series[(st0 + h + t) % s.N]));      // capacity factors: the realised window
     ub[m.wind_cols[t]] = avail;
     avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
     const double fix = t < known ? s.da_offer[(size_t)b * 24 + k + t] : 0.0;
     lb[m.pda_cols[t]] = fix;
     ub[m.pda_cols[t]] = t < known ? fix : INFINITY;
   }
-  if (m.c0) m.c0[r] = __dadd_rn(m.c0_base, mk_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
+  if (m.c0) m.c0[r] = __dadd_rn(m.c0_base, loop_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
   const double soc = s.soc[b], thr = s.thr[b];
   lb[m.soc_init] = soc; ub[m.soc_init] = soc;
   lb[m.thr_init] = thr; ub[m.thr_init] = thr;
@@ -113,8 +105,8 @@ __global__ void __launch_bounds__(256) market_clear_kernel(dsp_market_state s, d
       const size_t row = (size_t)b * S + i;
       if (m.status[row] == 0) {
         const double *x = m.x + row * m.n;
-        const double power = k < 0 ? x[ca] : __dmul_rn(1e-3, mk_opaque(__dadd_rn(x[ca], x[cb])));
-        const double price = series[mk_index(s, st0, h, i, hod, t)];
+        const double power = k < 0 ? x[ca] : __dmul_rn(1e-3, loop_opaque(__dadd_rn(x[ca], x[cb])));
+        const double price = series[loop_scenario_index(s, st0, h, i, hod, t)];
         const long long pc = bid_cents(power), cc = bid_cents(price);
         if (pc >= 0 && fabs(power) < INFINITY && fabs(price) < INFINITY) key = bid_key(pc, cc);
       } else {
@@ -128,55 +120,23 @@ __global__ void __launch_bounds__(256) market_clear_kernel(dsp_market_state s, d
   if (any_bad && s.bad) *s.bad = 1;
   mk_sort<SP>(keys);
   // ---- the price that occurs: realised for the day-ahead market and for the hour at hand, scenario 0's for the look-ahead hours ----
-  const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[mk_index(s, st0, h, 0, hod, t)];
-  // ---- lowest price among the distinct points (the inserted zero-power point takes it) ----
-  const bool has0 = keys[0] != kBidDrop && bid_key_power(keys[0]) == 0;      // powers are >= 0 and ascending
-  long long lowest = 0x7fffffffffffffffll;
-  int n = 0;
-#pragma unroll
-  for (int i = 0; i < SP; ++i) {
-    const bool first = keys[i] != kBidDrop && (i == 0 || bid_key_power(keys[i]) != bid_key_power(keys[i ? i - 1 : 0]));
-    if (first) { lowest = min(lowest, bid_key_price(keys[i])); ++n; }
-  }
-  // ---- distinct points in order with the running maximum, cleared on the way ----
-  int32_t *out = curve + (size_t)g * (S + 1) * 2;
-  int pos = 0;
-  long long run = 0, cleared = 0;
-  auto emit = [&](long long U, long long M) {
-    run = pos == 0 ? M : max(run, M);
-    out[2 * pos] = (int32_t)U;
-    out[2 * pos + 1] = (int32_t)run;
-    if (pos == 0 || !s.price_taker || __ddiv_rn((double)run, 100.0) <= lmp) cleared = U;
-    ++pos;
-  };
-  if (!has0) emit(0, n == 0 ? 0 : lowest);
-#pragma unroll
-  for (int i = 0; i < SP; ++i) {
-    const bool first = keys[i] != kBidDrop && (i == 0 || bid_key_power(keys[i]) != bid_key_power(keys[i ? i - 1 : 0]));
-    if (first) emit(bid_key_power(keys[i]), bid_key_price(keys[i]));
-  }
-  count[g] = pos;
-  for (int q = pos; q <= S; ++q) { out[2 * q] = 0; out[2 * q + 1] = 0; }
-  const double disp = __ddiv_rn((double)cleared, 100.0);
+  const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[loop_scenario_index(s, st0, h, 0, hod, t)];
+  // ---- the curve from the zero-power point on, cleared at that price ----
+  const double disp = loop_curve_and_clear<SP>(keys, S, 0, s.price_taker != 0, lmp, curve + (size_t)g * (S + 1) * 2, count + g);
   dispatch[g] = disp;
   if (k < 0) {
     s.da_prices[(size_t)b * 24 + t] = lmp;
     return;
   }
   if (!has_tr) return;
-  // ---- the tracker's LP of this hour (what phase 1 of dsp_wb_rolling_update writes, with the cleared dispatch) ----
+  // ---- the tracker's LP of this hour on the cleared dispatch ----
   double *rlo = tr.rlo + (size_t)b * tr.m, *rhi = tr.rhi + (size_t)b * tr.m;
   rlo[tr.track_rows[t]] = disp;
   rhi[tr.track_rows[t]] = disp;
   if (t == 0) {
     double *lb = tr.lb + (size_t)b * tr.n, *ub = tr.ub + (size_t)b * tr.n;
-    double avail_sum = 0.0;
-    for (int q = 0; q < tr.T; ++q) {
-      const double avail = mk_opaque(__dmul_rn(tr.wind_kw, s.cf_series[(st0 + h + q) % s.N]));
-      ub[tr.wind_cols[q]] = avail;
-      avail_sum = q ? __dadd_rn(avail_sum, avail) : avail;
-    }
-    if (tr.c0) tr.c0[b] = __dadd_rn(tr.c0_base, mk_opaque(__dmul_rn(tr.waste_per_kw, avail_sum)));
+    const double avail_sum = loop_wind_window(ub, tr.wind_cols, tr.T, tr.wind_kw, s.cf_series, st0 + h, s.N);
+    if (tr.c0) tr.c0[b] = loop_c0(tr.c0_base, tr.waste_per_kw, avail_sum);
     const double soc = s.soc[b], thr = s.thr[b];
     lb[tr.soc_init] = soc; ub[tr.soc_init] = soc;
     lb[tr.thr_init] = thr; ub[tr.thr_init] = thr;
@@ -210,13 +170,6 @@ hipError_t launch_market_clear(const dsp_market_state &st, const dsp_market_mode
 static_assert(sizeof(dsp_loop_market_state) + sizeof(dsp_loop_market_model) + sizeof(dsp_loop_model) + 64 <= 4096,
               "the descriptors travel as by-value kernel arguments: HIP's limit is 4 KB");
 
-__device__ __forceinline__ long long lmk_index(const dsp_loop_market_state &s, long long st0, long long h, int i, int hod, int t) {
-  if (!s.backcast) return (st0 + h + t) % s.N;
-  const long long D = s.D, d = h / 24;
-  const long long pos = (24 * (D - 1 - i) + hod + t) % (24 * D);
-  long long v = (st0 + 24 * (d - D) + pos) % s.N;
-  return v < 0 ? v + s.N : v;
-}
 // the same hour of the REAL-TIME series: with the backcast forecaster its history ends rt_history_lag_days earlier (ABI 17; a bid made
 // at the RUC hour: today is not a whole day of real-time prices yet).  lag 0: `at` itself.  24 * lag < N is checked on the host.
 __device__ __forceinline__ long long lmk_rt(const dsp_loop_market_state &s, long long at) {
@@ -238,20 +191,20 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
   double *c = m.c + (size_t)r * m.n, *lb = m.lb + (size_t)r * m.n, *ub = m.ub + (size_t)r * m.n;
   double avail_sum = 0.0, price_sum = 0.0;
   for (int t = 0; t < m.T; ++t) {
-    const long long at = lmk_index(s, st0, h, i, hod, t);
+    const long long at = loop_scenario_index(s, st0, h, i, hod, t);
     const double rtp = s.rt_series[lmk_rt(s, at)];
     const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : s.da_series[at];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const int col = m.pt_cols[t][e];
-      if (col >= 0) c[col] = __dsub_rn(m.base_c[col], mk_opaque(__dmul_rn(m.pt_coef[t][e], rtp)));
+      if (col >= 0) c[col] = __dsub_rn(m.base_c[col], loop_opaque(__dmul_rn(m.pt_coef[t][e], rtp)));
     }
     const int pda = m.pda_cols[t];
-    c[pda] = __dsub_rn(m.base_c[pda], mk_opaque(__dsub_rn(dap, rtp)));
-    const double pc = mk_opaque(__dmul_rn(rtp, m.pt_const[t]));
+    c[pda] = __dsub_rn(m.base_c[pda], loop_opaque(__dsub_rn(dap, rtp)));
+    const double pc = loop_opaque(__dmul_rn(rtp, m.pt_const[t]));
     price_sum = t ? __dadd_rn(price_sum, pc) : pc;
     if (wind) {
-      const double avail = mk_opaque(__dmul_rn(kw, s.cf_series[(st0 + h + t) % s.N]));     // capacity factors: the realised window
+      const double avail = loop_opaque(__dmul_rn(kw, s.cf_series[(st0 + h + t) % s.N]));     // capacity factors: the realised window
       ub[m.wind_cols[t]] = avail;
       avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
     }
@@ -259,8 +212,8 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
     lb[pda] = fix;
     ub[pda] = t < known ? fix : INFINITY;
   }
-  double c0 = mk_opaque(__dsub_rn(c0_base, price_sum));
-  if (wind) c0 = __dadd_rn(c0, mk_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
+  double c0 = loop_opaque(__dsub_rn(c0_base, price_sum));
+  if (wind) c0 = __dadd_rn(c0, loop_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
   m.c0[r] = c0;
   for (int j = 0; j < m.n_state; ++j) {
     const double v = s.state[(size_t)b * m.n_state + j];
@@ -295,11 +248,11 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
         if (k < 0) {
           power = x[ca];
         } else {
-          double p = ca >= 0 ? mk_opaque(__dmul_rn(x[ca], fa)) : 0.0;
-          if (cb >= 0) p = mk_opaque(__dadd_rn(p, mk_opaque(__dmul_rn(x[cb], fb))));
+          double p = ca >= 0 ? loop_opaque(__dmul_rn(x[ca], fa)) : 0.0;
+          if (cb >= 0) p = loop_opaque(__dadd_rn(p, loop_opaque(__dmul_rn(x[cb], fb))));
           power = __dadd_rn(p, fc);
         }
-        const long long at = lmk_index(s, st0, h, i, hod, t);
+        const long long at = loop_scenario_index(s, st0, h, i, hod, t);
         const double price = series[k < 0 ? at : lmk_rt(s, at)];
         const long long pc = bid_cents(power), cc = bid_cents(price);
         if (pc >= pmin && fabs(power) < INFINITY && fabs(price) < INFINITY) key = bid_key(pc, cc);
@@ -314,66 +267,21 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
   if (any_bad && s.bad) *s.bad = 1;
   mk_sort<SP>(keys);
   // ---- the price that occurs: realised for the day-ahead market and for the hour at hand, scenario 0's for the look-ahead hours ----
-  const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[lmk_rt(s, lmk_index(s, st0, h, 0, hod, t))];
-  // ---- lowest price among the distinct points (the inserted p_min point takes it) ----
-  const bool has_min = keys[0] != kBidDrop && bid_key_power(keys[0]) == pmin;      // powers are >= p_min and ascending
-  long long lowest = 0x7fffffffffffffffll;
-  int n = 0;
-#pragma unroll
-  for (int i = 0; i < SP; ++i) {
-    const bool first = keys[i] != kBidDrop && (i == 0 || bid_key_power(keys[i]) != bid_key_power(keys[i ? i - 1 : 0]));
-    if (first) { lowest = min(lowest, bid_key_price(keys[i])); ++n; }
-  }
-  // ---- distinct points in order with the running maximum, cleared on the way ----
-  int32_t *out = curve + (size_t)g * (S + 1) * 2;
-  int pos = 0;
-  long long run = 0, cleared = 0;
-  auto emit = [&](long long U, long long M) {
-    run = pos == 0 ? M : max(run, M);
-    out[2 * pos] = (int32_t)U;
-    out[2 * pos + 1] = (int32_t)run;
-    if (pos == 0 || !s.price_taker || __ddiv_rn((double)run, 100.0) <= lmp) cleared = U;
-    ++pos;
-  };
-  if (!has_min) emit(pmin, n == 0 ? 0 : lowest);
-#pragma unroll
-  for (int i = 0; i < SP; ++i) {
-    const bool first = keys[i] != kBidDrop && (i == 0 || bid_key_power(keys[i]) != bid_key_power(keys[i ? i - 1 : 0]));
-    if (first) emit(bid_key_power(keys[i]), bid_key_price(keys[i]));
-  }
-  count[g] = pos;
-  for (int q = pos; q <= S; ++q) { out[2 * q] = 0; out[2 * q + 1] = 0; }
-  const double disp = __ddiv_rn((double)cleared, 100.0);
+  const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[lmk_rt(s, loop_scenario_index(s, st0, h, 0, hod, t))];
+  // ---- the curve from the p_min point on, cleared at that price ----
+  const double disp = loop_curve_and_clear<SP>(keys, S, pmin, s.price_taker != 0, lmp, curve + (size_t)g * (S + 1) * 2, count + g);
   dispatch[g] = disp;
   if (k < 0) {
     s.da_prices[(size_t)b * 24 + t] = lmp;
     return;
   }
   if (!has_tr) return;
-  // ---- the tracker's LP of this hour (what phase 1 of dsp_loop_update writes, with the cleared dispatch) ----
+  // ---- the tracker's LP of this hour on the cleared dispatch ----
   double *rlo = tr.rlo + (size_t)b * tr.m, *rhi = tr.rhi + (size_t)b * tr.m;
   const double rhs = __dsub_rn(disp, tr.pt_const[t]);
   rlo[tr.track_rows[t]] = rhs;
   rhi[tr.track_rows[t]] = rhs;
-  if (t == 0) {
-    double *lb = tr.lb + (size_t)b * tr.n, *ub = tr.ub + (size_t)b * tr.n;
-    double c0 = tr.c0_base_plant ? tr.c0_base_plant[b] : tr.c0_base;
-    if (tr.wind_cols[0] >= 0) {
-      const double kw = tr.wind_kw_plant ? tr.wind_kw_plant[b] : tr.wind_kw;
-      double avail_sum = 0.0;
-      for (int q = 0; q < tr.T; ++q) {
-        const double avail = mk_opaque(__dmul_rn(kw, s.cf_series[(st0 + h + q) % s.N]));
-        ub[tr.wind_cols[q]] = avail;
-        avail_sum = q ? __dadd_rn(avail_sum, avail) : avail;
-      }
-      c0 = __dadd_rn(c0, mk_opaque(__dmul_rn(tr.waste_per_kw, avail_sum)));
-    }
-    tr.c0[b] = c0;
-    for (int j = 0; j < tr.n_state; ++j) {
-      const double v = s.state[(size_t)b * tr.n_state + j];
-      lb[tr.state_init[j]] = v; ub[tr.state_init[j]] = v;
-    }
-  }
+  if (t == 0) loop_tracker_plant(tr, b, s.cf_series, st0 + h, s.N, s.state + (size_t)b * tr.n_state);
 }
 
 hipError_t launch_loop_market_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, int k, hipStream_t stream) {

@@ -7,24 +7,25 @@
 //
 //   param_curve_kernel<DA>   one lane per (plant, period): window index, the three pairs in integer cents (dsp_bid_cents.hpp), the
 //                            curve, the clearing.  The pairs are ordered by construction (0 <= max(0, w - s) <= p_max, prices 0, 0,
-//                            bid >= 0), so the sort network of loop_market_clear_kernel reduces to two compares of cent values:
+//                            bid >= 0), so the sort network of the LP bidder's clearing kernel reduces to two compares of cent values:
 //                            "is the middle power above 0" and "is the last power above the middle one".  A pair that repeats a
 //                            power keeps the higher price, which is the later pair's.  DA = true: 24 hours on the day-ahead capacity
 //                            factors and prices; DA = false: the tracker's periods on the real-time ones, and the tracker's LP of
-//                            the hour exactly as loop_market_clear_kernel writes it.
+//                            the hour on the cleared dispatch.
 //   param_h2_kernel          one lane per plant, after the tracking solve: hydrogen of the implemented hour.
 //
 // Every product is rounded on its own (__dmul_rn / __dadd_rn / __dsub_rn, and an opaque register between a product and the sum that
 // takes it - the intrinsics alone do not stop the compiler from contracting the two into one fma): bit-identical to
 // the tensor operations of BatchedDoubleLoop (use_fused=False), which go through workflow/market.py::plant_curves / clear_curves.
-// Vector stores only, no atomics, no LDS; VGPRs / scratch: profiles/param_kernel_resources.txt.
+// The points of a curve (loop_emit_point, loop_curve_close) and the plant half of the tracker's LP (loop_tracker_plant) are the shared
+// ones of dsp_loop_device.hpp.  Vector stores only, no atomics, no LDS; VGPRs / scratch: profiles/loop_device_kernel_resources.txt.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/dsp_hip.h"
-#include "dsp_bid_cents.hpp"
 #include "dsp_device.hpp"
+#include "dsp_loop_device.hpp"
 
 #pragma clang fp contract(off)
 
@@ -32,8 +33,6 @@ namespace dsp {
 
 static_assert(sizeof(dsp_loop_param_state) + sizeof(dsp_loop_model) + 64 <= 4096,
               "the descriptors travel as by-value kernel arguments: HIP's limit is 4 KB");
-
-__device__ __forceinline__ double pm_opaque(double v) { asm volatile("" : "+v"(v)); return v; }
 
 template <bool DA>
 __global__ void __launch_bounds__(256) param_curve_kernel(dsp_loop_param_state s, dsp_loop_model tr, int T) {
@@ -45,7 +44,7 @@ __global__ void __launch_bounds__(256) param_curve_kernel(dsp_loop_param_state s
   const double lmp = (DA ? s.da_series : s.rt_series)[at];
   const double bid = s.bid_price[b], storage = s.storage_mw[b];
   // ---- the three pairs: (0, 0), (lo, 0), (hi, bid) ----
-  const double w = pm_opaque(__dmul_rn((DA ? s.da_cf_series : s.rt_cf_series)[at], s.wind_mw));      // opaque: w - storage must not become one fma
+  const double w = loop_opaque(__dmul_rn((DA ? s.da_cf_series : s.rt_cf_series)[at], s.wind_mw));      // opaque: w - storage must not become one fma
   const double lo = fmax(__dsub_rn(w, storage), 0.0);
   const double hi = s.battery ? fmax(w, storage) : w;
   const long long lo_c = bid_cents(lo), hi_c = bid_cents(hi), bid_c = bid_cents(bid);
@@ -55,13 +54,8 @@ __global__ void __launch_bounds__(256) param_curve_kernel(dsp_loop_param_state s
   int32_t *out = (DA ? s.da_curve : s.rt_curve) + (size_t)g * 8;
   int pos = 0;
   long long run = 0, cleared = 0;
-  auto emit = [&](long long U, long long M) {
-    run = pos == 0 ? M : max(run, M);
-    out[2 * pos] = (int32_t)U;
-    out[2 * pos + 1] = (int32_t)run;
-    if (pos == 0 || !s.price_taker || __ddiv_rn((double)run, 100.0) <= lmp) cleared = U;
-    ++pos;
-  };
+  const bool price_taker = s.price_taker != 0;
+  auto emit = [&](long long U, long long M) { loop_emit_point(out, pos, run, cleared, U, M, price_taker, lmp); };
   const bool lo_new = has_lo && lo_c > 0;                            // compare 1: the middle pair is a point of its own
   const long long below = lo_new ? lo_c : 0;                         // the largest power in front of the last pair
   const bool hi_new = has_hi && hi_c > below;                        // compare 2: the last pair is a point of its own
@@ -70,45 +64,27 @@ __global__ void __launch_bounds__(256) param_curve_kernel(dsp_loop_param_state s
   if (lo_new) emit(lo_c, hi_joins ? max(0ll, bid_c) : 0ll);
   if (hi_new) emit(hi_c, bid_c);
   (DA ? s.da_count : s.rt_count)[g] = pos;
-  for (int q = pos; q < 4; ++q) { out[2 * q] = 0; out[2 * q + 1] = 0; }
-  const double disp = __ddiv_rn((double)cleared, 100.0);
+  const double disp = loop_curve_close(out, pos, 4, cleared);
   if (DA) {
     s.da_offer[g] = disp;
     s.da_prices[g] = lmp;
     return;
   }
   s.rt_dispatch[g] = disp;
-  // ---- the tracker's LP of this hour (as loop_market_clear_kernel) ----
+  // ---- the tracker's LP of this hour on the cleared dispatch (one wind size: the host refuses per-plant pointers here) ----
   double *rlo = tr.rlo + (size_t)b * tr.m, *rhi = tr.rhi + (size_t)b * tr.m;
   const double rhs = __dsub_rn(disp, tr.pt_const[t]);
   rlo[tr.track_rows[t]] = rhs;
   rhi[tr.track_rows[t]] = rhs;
-  if (t == 0) {
-    double *lb = tr.lb + (size_t)b * tr.n, *ub = tr.ub + (size_t)b * tr.n;
-    double c0 = tr.c0_base;
-    if (tr.wind_cols[0] >= 0) {
-      double avail_sum = 0.0;
-      for (int q = 0; q < tr.T; ++q) {
-        const double avail = pm_opaque(__dmul_rn(tr.wind_kw, s.rt_cf_series[(st0 + h + q) % s.N]));
-        ub[tr.wind_cols[q]] = avail;
-        avail_sum = q ? __dadd_rn(avail_sum, avail) : avail;
-      }
-      c0 = __dadd_rn(c0, pm_opaque(__dmul_rn(tr.waste_per_kw, avail_sum)));
-    }
-    tr.c0[b] = c0;
-    for (int j = 0; j < tr.n_state; ++j) {
-      const double v = s.state[(size_t)b * tr.n_state + j];
-      lb[tr.state_init[j]] = v; ub[tr.state_init[j]] = v;
-    }
-  }
+  if (t == 0) loop_tracker_plant(tr, b, s.rt_cf_series, st0 + h, s.N, s.state + (size_t)b * tr.n_state);
 }
 
 __global__ void __launch_bounds__(256) param_h2_kernel(dsp_loop_param_state s, dsp_loop_model tr) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= s.B) return;
   const double kw = tr.x[(size_t)b * tr.n + s.pem_col];
-  const double kg = __dmul_rn(__ddiv_rn(pm_opaque(__dmul_rn(kw, s.h2_mul)), s.h2_div), 3600.0);
-  s.h2_kg[b] = __dadd_rn(s.h2_kg[b], pm_opaque(kg));
+  const double kg = __dmul_rn(__ddiv_rn(loop_opaque(__dmul_rn(kw, s.h2_mul)), s.h2_div), 3600.0);
+  s.h2_kg[b] = __dadd_rn(s.h2_kg[b], loop_opaque(kg));
 }
 
 hipError_t launch_loop_param_step(const dsp_loop_param_state &st, const dsp_loop_model &tr, int phase, hipStream_t stream) {

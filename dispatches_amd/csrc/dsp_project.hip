@@ -10,22 +10,23 @@
 //   project_write_kernel     one lane per (plant, period) of chain step j: dispatch row t = da_offer[H + j + t] - pt_const[t] inside the
 //                            day, FREE ON BOTH SIDES (-inf, +inf) past midnight (Tracker._pass_market_dispatch on a short dispatch
 //                            list); by the lane of period 0 the state columns (step 0: the realised state, which becomes entry 0 of the
-//                            trace; step j: entry j), the wind bounds of the window at clock + j and c0 - what the tracker half of
-//                            loop_market_clear_kernel writes.
+//                            trace; step j: entry j), the wind bounds of the window at clock + j and c0 (loop_tracker_plant,
+//                            dsp_loop_device.hpp: the plant half of every descriptor tracker's LP).
 //   project_hand_off_kernel  one lane per plant after the solve: status / flags -> bad / uncertified, the unrounded state -> proj_real[j],
 //                            rounded as update_model rounds it -> proj_state[j + 1], objective with its constant -> proj_obj[j].
 //   project_activate_kernel  midnight, one lane per (plant, hour of 24): the pending bid (offers, realised day-ahead prices, curves,
 //                            counts) becomes the current one.
 //
-// Arithmetic as dsp_market.hip / dsp_param.hip: every product rounded on its own and opaque before a sum takes it, sums in the order of
+// Arithmetic of dsp_loop_device.hpp: every product rounded on its own and opaque before a sum takes it, sums in the order of
 // t - bit-identical to the tensor operations of BatchedDoubleLoop (use_fused=False).  Vector stores only, no LDS, no atomics beyond the
-// `uncertified` counter of the other loop kernels; VGPRs / scratch: profiles/ruc_project_kernel_resources.txt.
+// `uncertified` counter of the other loop kernels; VGPRs / scratch: profiles/loop_device_kernel_resources.txt.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/dsp_hip.h"
 #include "dsp_device.hpp"
+#include "dsp_loop_device.hpp"
 
 #pragma clang fp contract(off)
 
@@ -33,8 +34,6 @@ namespace dsp {
 
 static_assert(sizeof(dsp_loop_project_state) + sizeof(dsp_loop_model) + 64 <= 4096,
               "the descriptors travel as by-value kernel arguments: HIP's limit is 4 KB");
-
-__device__ __forceinline__ double pj_opaque(double v) { asm volatile("" : "+v"(v)); return v; }
 
 __global__ void __launch_bounds__(256) project_write_kernel(dsp_loop_project_state s, dsp_loop_model pj, int j) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -51,32 +50,12 @@ __global__ void __launch_bounds__(256) project_write_kernel(dsp_loop_project_sta
     rhi[pj.track_rows[t]] = INFINITY;
   }
   if (t != 0) return;
-  const long long h = *s.hour + j, st0 = s.start[b];
-  double *lb = pj.lb + (size_t)b * pj.n, *ub = pj.ub + (size_t)b * pj.n;
-  double c0 = pj.c0_base_plant ? pj.c0_base_plant[b] : pj.c0_base;
-  if (pj.wind_cols[0] >= 0) {
-    const double kw = pj.wind_kw_plant ? pj.wind_kw_plant[b] : pj.wind_kw;
-    double avail_sum = 0.0;
-    for (int q = 0; q < pj.T; ++q) {
-      const double avail = pj_opaque(__dmul_rn(kw, s.cf_series[(st0 + h + q) % s.N]));
-      ub[pj.wind_cols[q]] = avail;
-      avail_sum = q ? __dadd_rn(avail_sum, avail) : avail;
-    }
-    c0 = __dadd_rn(c0, pj_opaque(__dmul_rn(pj.waste_per_kw, avail_sum)));
+  const double *state = s.proj_state + ((size_t)j * s.B + b) * pj.n_state;     // entry j of the trace
+  if (j == 0) {                                                      // entry 0: the realised state at the bid hour
+    state = s.state + (size_t)b * pj.n_state;
+    for (int e = 0; e < pj.n_state; ++e) s.proj_state[(size_t)b * pj.n_state + e] = state[e];
   }
-  pj.c0[b] = c0;
-  const size_t plane = (size_t)s.B * pj.n_state;
-  for (int e = 0; e < pj.n_state; ++e) {
-    const size_t at_state = (size_t)b * pj.n_state + e;
-    double v;
-    if (j == 0) {
-      v = s.state[at_state];
-      s.proj_state[at_state] = v;                                    // entry 0 of the trace: the realised state at the bid hour
-    } else {
-      v = s.proj_state[(size_t)j * plane + at_state];
-    }
-    lb[pj.state_init[e]] = v; ub[pj.state_init[e]] = v;
-  }
+  loop_tracker_plant(pj, b, s.cf_series, s.start[b] + *s.hour + j, s.N, state);
 }
 
 __global__ void __launch_bounds__(256) project_hand_off_kernel(dsp_loop_project_state s, dsp_loop_model pj, int j) {
@@ -90,7 +69,7 @@ __global__ void __launch_bounds__(256) project_hand_off_kernel(dsp_loop_project_
     const size_t at_state = (size_t)b * pj.n_state + e;
     const double real = x[pj.state_real[e]];
     s.proj_real[(size_t)j * plane + at_state] = real;
-    s.proj_state[(size_t)(j + 1) * plane + at_state] = __ddiv_rn(rint(pj_opaque(__dmul_rn(real, s.state_scale[e]))), s.state_scale[e]);
+    s.proj_state[(size_t)(j + 1) * plane + at_state] = __ddiv_rn(rint(loop_opaque(__dmul_rn(real, s.state_scale[e]))), s.state_scale[e]);
   }
   s.proj_obj[(size_t)j * s.B + b] = __dadd_rn(s.obj[b], pj.c0[b]);
 }

@@ -110,6 +110,7 @@ class _Model:
         PT, PT_const = _dense_rows(model.block, power_output, n, model.HOUR)
         self.PT, self.PT_const = t(PT), t(PT_const)                       # [T, n], [T]
         self.state_init = [int(c) for c in state_init]                    # columns fixed to the realised state
+        self.pda_cols = self.track_rows = self.state_real = None          # day-ahead power columns (bidding models); dispatch rows, state after period 0 (trackers)
         self.kw_plant = self.c0_plant = None                              # per-plant sizes: wind kW [B, 1], objective constant [B] (set_plant_sizes)
         self.wind = None
         if wind is not None:                                              # (columns, kW, curtailment cost per kW, template availability sum)
@@ -147,16 +148,24 @@ class _Model:
         return self.wind[1] if self.kw_plant is None else self.kw_plant
 
     def terms(self):
-        """P_T[t] = (x[a] ca + x[b] cb) + const_t as index / coefficient arrays [T, 2] (-1 / 0.0: no such term): the stochastic mode's
-        elementwise form of the power output, the one its kernels compute"""
+        """P_T[t] = (x[a] ca + x[b] cb) + const_t as index / coefficient arrays [T, 2] (-1 / 0.0: no such term): the
+        elementwise form of the power output, the one the kernels compute and the descriptors carry"""
         PT = self.PT.cpu().numpy()
         cols, coef = np.full((self.T, 2), -1, np.int64), np.zeros((self.T, 2))
         for t in range(self.T):
             nz = np.nonzero(PT[t])[0]
             if len(nz) > 2:
-                raise ValueError("the stochastic mode takes power outputs of at most two columns per period")
+                raise ValueError("the kernels take power outputs of at most two columns per period")
             cols[t, :len(nz)], coef[t, :len(nz)] = nz, PT[t, nz]
         return cols, coef
+
+    def set_first_period_terms(self, dev):
+        """P_T[0] as phase 2 of dsp_loop_update reads it, for the exact form of the hand-off (BatchedDoubleLoop._hand_off)"""
+        import torch
+        cols, coef = self.terms()
+        used = cols[0] >= 0
+        self.p0_cols = torch.as_tensor(cols[0][used], dtype=torch.int64, device=dev)
+        self.p0_coef = torch.as_tensor(coef[0][used], dtype=torch.float64, device=dev)
 
     def set_terms(self, dev):
         import torch
@@ -176,6 +185,44 @@ class _Model:
         self.out = self.dlp.solve(B, self.c, self.lb, self.ub, self.rlo if self.lp.m else None, self.rhi if self.lp.m else None,
                                   options=opts, out=self.out, sync_stats=False, obj_offset=self.c0)
         return self.out
+
+
+def _per_plant(v, name, B, positive=False, below=None):
+    """a scalar or an array [B], finite, >= 0 (positive: > 0) and, if given, below `below` -> float64 array [B]"""
+    a = np.asarray(v, np.float64)
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != B):
+        raise ValueError(f"{name} is a scalar or an array of length {B}, not of shape {a.shape}")
+    if not np.isfinite(a).all() or ((a <= 0).any() if positive else (a < 0).any()) or (below is not None and (a >= below).any()):
+        raise ValueError(f"{name} must be finite, {'> 0' if positive else '>= 0'}" + ("" if below is None else f" and below {below:.0e}".replace("e+0", "e")))
+    return np.broadcast_to(a, (B,)).copy()
+
+
+def _fill_descriptor(w, m, n_state):
+    """the fields that DspLoopModel and DspLoopMarketModel (hip_solver.py) share, from a _Model: buffers, sizes, the two-term power output
+    (_Model.terms), day-ahead power / wind / state columns, the wind size and the objective constants, per plant where the model
+    carries them (None: the pointers stay NULL, the kernels read the scalars).  Entries past the horizon are -1 / 0."""
+    w.c, w.lb, w.ub, w.base_c, w.x, w.c0 = (t.data_ptr() for t in (m.c, m.lb, m.ub, m.base_c, m.out["x"], m.c0))
+    w.status, w.flags = m.out["status"].data_ptr(), m.out["flags"].data_ptr()
+    w.n, w.T, w.n_state = m.lp.n, m.T, n_state
+    cols, coef = m.terms()
+    PTc = m.PT_const.cpu().numpy()
+    pda = m.pda_cols.cpu().tolist() if m.pda_cols is not None else []
+    wind = m.wind[0].cpu().tolist() if m.wind is not None else []
+    for t in range(len(w.pda_cols)):
+        live = t < m.T
+        for e in range(2):
+            w.pt_cols[t][e] = int(cols[t, e]) if live else -1
+            w.pt_coef[t][e] = float(coef[t, e]) if live else 0.0
+        w.pt_const[t] = float(PTc[t]) if live else 0.0
+        w.pda_cols[t] = int(pda[t]) if t < len(pda) else -1
+        w.wind_cols[t] = int(wind[t]) if t < len(wind) else -1
+    for j in range(len(w.state_init)):
+        w.state_init[j] = m.state_init[j] if j < len(m.state_init) else 0
+    w.wind_kw, w.waste_per_kw = (m.wind[1], m.wind[2]) if m.wind is not None else (0.0, 0.0)
+    w.c0_base = m.base_c0
+    if m.kw_plant is not None:
+        w.wind_kw_plant, w.c0_base_plant = m.kw_plant.data_ptr(), m.c0_plant.data_ptr()
+    return w
 
 
 _WIND_BATTERY_SIZES = dict(wind_mw=200.0, battery_mw=25.0, battery_mwh=100.0)      # the plant of the reference's wind + battery double loop
@@ -330,17 +377,10 @@ class BatchedDoubleLoop:
                 raise ValueError("bidder='parametrized' bids on a perfect forecast: forecaster='perfect', n_price_scenarios=1")
             if not 1 <= int(tracking_horizon) <= 16:
                 raise ValueError("bidder='parametrized' takes a tracking_horizon of 1 .. 16 periods")
-
-            def per_plant(v, name):
+            for name, v in (("bid_price", bid_price), ("storage_mw", storage_mw)):
                 if v is None:
                     raise ValueError(f"bidder='parametrized' needs {name}")
-                a = np.asarray(v, np.float64)
-                if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != B):
-                    raise ValueError(f"{name} is a scalar or an array of length {B}, not of shape {a.shape}")
-                if not np.isfinite(a).all() or (a < 0).any() or (a >= 2.0e7).any():         # (2e7: the range of the cent arithmetic, bid_curves.cents)
-                    raise ValueError(f"{name} must be finite, >= 0 and below 2e7")
-                return np.broadcast_to(a, (B,)).copy()
-            bid_price, storage_mw = per_plant(bid_price, "bid_price"), per_plant(storage_mw, "storage_mw")
+            bid_price, storage_mw = (_per_plant(v, name, B, below=2.0e7) for v, name in ((bid_price, "bid_price"), (storage_mw, "storage_mw")))      # (2e7: the range of the cent arithmetic, bid_curves.cents)
         elif bid_price is not None or storage_mw is not None:
             raise ValueError("bid_price and storage_mw belong to bidder='parametrized'")
         if ruc_hour is not None:
@@ -372,9 +412,10 @@ class BatchedDoubleLoop:
         self.bidder, self.tracker_template = bidder, tracker
         da_s, rt_s, cf_s = d["prices"]
         self.N = N = len(rt_s)
-        if self.stochastic and not self.parametrized and (24 * D > N or tracking_horizon > len(rt_model.HOUR) or not 24 <= len(da_model.HOUR) <= 48):
-            raise ValueError("the stochastic mode needs max_historical_days whole days inside the series, tracking_horizon <= the real-time "
-                             "horizon and a day-ahead horizon of 24 .. 48 periods")
+        if not self.parametrized and tracking_horizon > len(rt_model.HOUR):       # (the parametrized mode has no real-time LP)
+            raise ValueError(f"tracking_horizon must be <= the real-time horizon ({len(rt_model.HOUR)}): the tracker follows the first periods of the real-time offer")
+        if self.stochastic and not self.parametrized and (24 * D > N or not 24 <= len(da_model.HOUR) <= 48):
+            raise ValueError("the stochastic mode needs max_historical_days whole days inside the series and a day-ahead horizon of 24 .. 48 periods")
         if ruc_hour is not None and forecaster == "backcast" and 24 * (D + 1) > N:
             raise ValueError("ruc_hour with forecaster='backcast' needs max_historical_days + 1 whole days inside the series: the real-time "
                              "history of a bid made at the RUC hour ends one day earlier")
@@ -414,6 +455,9 @@ class BatchedDoubleLoop:
         self.simplex_warm = bool(simplex_warm) and lp_backend is None
         self._graphs, self._warm = {}, False
         self.use_fused = bool(use_fused) and lp_backend is None and self.rt.T <= 16 and self.tr.T <= 16 and len(self.scale) <= 2
+        self.exact = self.sized or self.parametrized    # these state phase 2 of dsp_loop_update exactly, sums included (_hand_off)
+        if self.exact:
+            self.tr.set_first_period_terms(dev)
         if self.sized:
             self._sizes_setup(sizes, d, tracker)
         if self.parametrized:
@@ -451,16 +495,7 @@ class BatchedDoubleLoop:
             raise ValueError(f"{', '.join(given)}: per-plant sizes belong to bidder='lp' (the parametrized bidders take storage_mw; their wind_mw is the flowsheet's)")
         if flowsheet == "wind_pem" and (battery_mw is not None or battery_mwh is not None):
             raise ValueError("wind_pem has no battery: battery_mw / battery_mwh are refused (the PEM capacity is a free column of its LP, not a size)")
-        out = {}
-        for name, v in given.items():
-            a = np.asarray(v, np.float64)
-            if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != B):
-                raise ValueError(f"{name} is a scalar or an array of length {B}, not of shape {a.shape}")
-            if not np.isfinite(a).all():
-                raise ValueError(f"{name} must be finite")
-            if (a <= 0).any() if name == "wind_mw" else (a < 0).any():
-                raise ValueError("wind_mw must be > 0" if name == "wind_mw" else f"{name} must be >= 0")
-            out[name] = np.broadcast_to(a, (B,)).copy()
+        out = {name: _per_plant(v, name, B, positive=name == "wind_mw") for name, v in given.items()}
         if flowsheet == "wind_battery":
             if "battery_mwh" not in out:                                   # the flowsheet's own default: four hours of the given power
                 out["battery_mwh"] = 4.0 * out["battery_mw"] if "battery_mw" in out else np.full(B, _WIND_BATTERY_SIZES["battery_mwh"])
@@ -496,10 +531,6 @@ class BatchedDoubleLoop:
             if c0[at] != m.base_c0 or float(distinct[at]) * 1e3 != m.wind[1]:
                 raise RuntimeError(f"the objective constant recomputed for the template's wind size ({c0[at]!r}) is not the template's ({m.base_c0!r})")
             m.set_plant_sizes(wind_kw, c0[inverse], self.dev)
-        cols, coef = self.tr.terms()                                       # P_T[0] of the tracker as phase 2 of dsp_loop_update reads it (_hand_off_exact)
-        used = cols[0] >= 0
-        self.tr.p0_cols = torch.as_tensor(cols[0][used], dtype=torch.int64, device=self.dev)
-        self.tr.p0_coef = t(coef[0][used])
         if self.flowsheet != "wind_battery":
             return
         batt_kw, batt_kwh = self.battery_mw * 1e3, self.battery_mwh * 1e3
@@ -530,10 +561,6 @@ class BatchedDoubleLoop:
         self.rt_dispatch = z(B, Tc)
         self.da_energy_mwh, self.offered_mwh = z(B), z(B)
         self._hundred = torch.full((), 100.0, dtype=torch.float64, device=dev)
-        cols, coef = self.tr.terms()                                               # P_T[0] of the tracker as phase 2 of dsp_loop_update reads it
-        used = cols[0] >= 0
-        self.tr.p0_cols = torch.as_tensor(cols[0][used], dtype=torch.int64, device=dev)
-        self.tr.p0_coef = t(coef[0][used])
         self.h2_kg = None
         if self.flowsheet == "wind_pem":                                           # MultiPeriodWindPEM._h2_kg_per_hr of the implemented hour
             self.h2_kg = z(B)
@@ -568,33 +595,14 @@ class BatchedDoubleLoop:
         from .hip_solver import DspLoopModel, DspLoopState, load_library
         self._lib = load_library()
 
-        def struct(m, pda=None, track=None, real=None):
-            w = DspLoopModel()
-            w.c, w.lb, w.ub, w.rlo, w.rhi = (t.data_ptr() for t in (m.c, m.lb, m.ub, m.rlo, m.rhi))
-            w.base_c, w.x, w.c0 = m.base_c.data_ptr(), m.out["x"].data_ptr(), m.c0.data_ptr()
-            w.n, w.m, w.T, w.n_state = m.lp.n, m.lp.m, m.T, len(self.scale)
-            PT, PTc = m.PT.cpu().numpy(), m.PT_const.cpu().numpy()
-            wind = m.wind[0].cpu().tolist() if m.wind is not None else []
-            for t in range(16):
-                nz = np.nonzero(PT[t])[0] if t < m.T else []
-                if len(nz) > 2:
-                    raise ValueError("the fused update kernel takes power outputs of at most two columns per period")
-                for e in range(2):
-                    w.pt_cols[t][e] = int(nz[e]) if e < len(nz) else -1
-                    w.pt_coef[t][e] = float(PT[t, nz[e]]) if e < len(nz) else 0.0
-                w.pt_const[t] = float(PTc[t]) if t < m.T else 0.0
-                w.pda_cols[t] = int(pda[t]) if pda is not None and t < len(pda) else -1
-                w.track_rows[t] = int(track[t]) if track is not None and t < len(track) else -1
-                w.wind_cols[t] = int(wind[t]) if t < len(wind) else -1
-            for j in range(2):
-                w.state_init[j] = m.state_init[j] if j < len(m.state_init) else 0
-                w.state_real[j] = real[j] if real is not None and j < len(real) else 0
-            w.wind_kw = m.wind[1] if m.wind is not None else 0.0
-            w.waste_per_kw = m.wind[2] if m.wind is not None else 0.0
-            w.c0_base = m.base_c0
-            w.status, w.flags = m.out["status"].data_ptr(), m.out["flags"].data_ptr()
-            if m.kw_plant is not None:                                     # (None: the pointers stay NULL, the kernels read the scalars)
-                w.wind_kw_plant, w.c0_base_plant = m.kw_plant.data_ptr(), m.c0_plant.data_ptr()
+        def loop_model(m):                             # + what only a dsp_loop_model has: rows, dispatch rows, the state after period 0
+            w = _fill_descriptor(DspLoopModel(), m, len(self.scale))
+            w.rlo, w.rhi, w.m = m.rlo.data_ptr(), m.rhi.data_ptr(), m.lp.m
+            track = m.track_rows.cpu().tolist() if m.track_rows is not None else []
+            for t in range(len(w.track_rows)):
+                w.track_rows[t] = int(track[t]) if t < len(track) else -1
+            for j in range(len(w.state_real)):
+                w.state_real[j] = m.state_real[j] if m.state_real is not None and j < len(m.state_real) else 0
             return w
         st = DspLoopState()
         st.B, st.N = self.B, self.N
@@ -608,11 +616,10 @@ class BatchedDoubleLoop:
         st.delivered, st.revenue, st.energy_mwh = self.delivered.data_ptr(), self.revenue.data_ptr(), self.energy_mwh.data_ptr()
         st.bad, st.uncertified = self.bad.data_ptr(), self.uncertified.data_ptr()
         self._loop_state = st
-        self._loop_rt = struct(self.rt, pda=self.rt.pda_cols.cpu().tolist())
-        self._loop_tr = struct(self.tr, track=self.tr.track_rows.cpu().tolist(), real=self.tr.state_real)
+        self._loop_rt, self._loop_tr = loop_model(self.rt), loop_model(self.tr)
         if self.ruc_hour is not None:
             from .hip_solver import DspLoopProjectState
-            self._loop_pj = struct(self.pj, track=self.pj.track_rows.cpu().tolist(), real=self.pj.state_real)
+            self._loop_pj = loop_model(self.pj)
             ps = DspLoopProjectState()
             ps.B, ps.N, ps.ruc_hour = self.B, self.N, self.ruc_hour
             ps.slots = self.da_curve.shape[2] if self.stochastic else 0
@@ -636,32 +643,8 @@ class BatchedDoubleLoop:
         for name in ("start", "hour", "da_series", "rt_series", "cf_series", "state", "da_offer", "da_prices", "bad", "uncertified"):
             setattr(mk, name, getattr(self._loop_state, name))
         mk.p_min_cents = self.p_min_cents
-
-        def struct(m):
-            w = DspLoopMarketModel()
-            w.c, w.lb, w.ub, w.base_c, w.x, w.c0 = (t.data_ptr() for t in (m.c, m.lb, m.ub, m.base_c, m.out["x"], m.c0))
-            w.status, w.flags = m.out["status"].data_ptr(), m.out["flags"].data_ptr()
-            w.n, w.T, w.n_state = m.lp.n, m.T, len(self.scale)
-            cols, coef = m.terms()
-            PTc, pda = m.PT_const.cpu().numpy(), m.pda_cols.cpu().tolist()
-            wind = m.wind[0].cpu().tolist() if m.wind is not None else []
-            for t in range(len(w.pda_cols)):
-                live = t < m.T
-                for e in range(2):
-                    w.pt_cols[t][e] = int(cols[t, e]) if live else -1
-                    w.pt_coef[t][e] = float(coef[t, e]) if live else 0.0
-                w.pt_const[t] = float(PTc[t]) if live else 0.0
-                w.pda_cols[t] = int(pda[t]) if live else -1
-                w.wind_cols[t] = int(wind[t]) if t < len(wind) else -1
-            for j in range(2):
-                w.state_init[j] = m.state_init[j] if j < len(m.state_init) else 0
-            w.wind_kw = m.wind[1] if m.wind is not None else 0.0
-            w.waste_per_kw = m.wind[2] if m.wind is not None else 0.0
-            w.c0_base = m.base_c0
-            if m.kw_plant is not None:
-                w.wind_kw_plant, w.c0_base_plant = m.kw_plant.data_ptr(), m.c0_plant.data_ptr()
-            return w
-        self._mk_state, self._mk_da, self._mk_rt = mk, struct(self.da), struct(self.rt)
+        self._mk_state = mk
+        self._mk_da, self._mk_rt = (_fill_descriptor(DspLoopMarketModel(), m, len(self.scale)) for m in (self.da, self.rt))
         if self.ruc_hour is not None:                  # the bid made at the RUC hour: its own clock, the projected state, the pending buffers
             bid = DspLoopMarketState.from_buffer_copy(mk)
             bid.hour, bid.state = self.bid_hour_t.data_ptr(), self.proj_state[-1].data_ptr() if len(self.scale) else None
@@ -732,7 +715,6 @@ class BatchedDoubleLoop:
         (self.pend_prices if bid else self.da_prices).copy_(da[:, :24])
 
     def _hour_step(self, k):
-        import torch
         if self.use_fused:
             hour = k if self.simplex_warm else None
             self._fused(0, k)
@@ -762,11 +744,26 @@ class BatchedDoubleLoop:
         tr.rhi[:, tr.track_rows] = rhs
         out = tr.solve(self.B, hour=hour) if tr.opts is not None else tr.solve(self.B)
         self._check(out)
-        x = out["x"]
-        self.delivered.copy_(tr.power_output(x)[:, 0])
-        for j, col in enumerate(tr.state_real):                           # implemented profile -> next hour's state, rounded as update_model does
+        self._hand_off(out["x"], rt[:, 0], k, exact=False)
+
+    def _hand_off(self, x, rt0, k, exact):
+        """the end of hour k on the tracker's solution x: delivered power, the implemented profile -> next hour's state rounded as
+        update_model does, revenue, energy, clock.  exact: delivered power and revenue in the arithmetic of phase 2 of dsp_loop_update,
+        so that the tensor form and the kernels agree bit for bit on the sums too - P_T[0] = fma(cb, x[b], fma(ca, x[a], const)),
+        revenue += fma(delivered, rt, da_offer * (da - rt)); otherwise the matrix form, equal to the kernels' to a tolerance"""
+        import torch
+        tr = self.tr
+        day_ahead = self.da_offer[:, k] * (self.da_prices[:, k] - rt0)
+        if exact:
+            p = tr.PT_const[0].expand(self.B)
+            for e in range(tr.p0_cols.shape[0]):
+                p = exact_fma(torch, tr.p0_coef[e].expand(self.B), x[:, tr.p0_cols[e]], p)
+            self.delivered.copy_(p)
+        else:
+            self.delivered.copy_(tr.power_output(x)[:, 0])
+        for j, col in enumerate(tr.state_real):
             self.state[:, j] = torch.round(x[:, col] * self.scale[j]) / self._scale_t[j]
-        self.revenue += self.delivered * rt[:, 0] + self.da_offer[:, k] * (self.da_prices[:, k] - rt[:, 0])
+        self.revenue += exact_fma(torch, self.delivered, rt0, day_ahead) if exact else self.delivered * rt0 + day_ahead
         self.energy_mwh += self.delivered
         self.hour_t += 1
 
@@ -827,15 +824,20 @@ class BatchedDoubleLoop:
         rhs = self.rt_dispatch - tr.PT_const
         tr.rlo[:, tr.track_rows] = rhs
         tr.rhi[:, tr.track_rows] = rhs
-        for j, col in enumerate(tr.state_init):
-            tr.lb[:, col] = self.state[:, j]
-            tr.ub[:, col] = self.state[:, j]
-        if tr.wind is not None:
-            cols, avail, waste = self._avail(tr)
-            tr.ub[:, cols] = avail
-            tr.c0.copy_((tr.base_c0 if tr.c0_plant is None else tr.c0_plant) + waste)
+        self._set_tracker_plant(tr, self.state)
+
+    def _set_tracker_plant(self, m, state, offset=0):
+        """the plant half of a tracker's LP: state columns fixed to state [B, n_state], wind bounds of the window that starts `offset`
+        hours after the clock, c0 = base_c0 + per_kw sum_t avail[t]"""
+        for j, col in enumerate(m.state_init):
+            m.lb[:, col] = state[:, j]
+            m.ub[:, col] = state[:, j]
+        if m.wind is not None:
+            cols, avail, waste = self._avail(m, offset)
+            m.ub[:, cols] = avail
+            m.c0.copy_((m.base_c0 if m.c0_plant is None else m.c0_plant) + waste)
         else:
-            tr.c0.fill_(tr.base_c0)
+            m.c0.fill_(m.base_c0)
 
     def _curves(self, power, price, status):
         """power, price [B, S, Tc]; status [B * S] -> (U, M [S + 1, B * Tc] int64 cents, count [B * Tc]) - workflow/market.py::plant_curves"""
@@ -852,8 +854,8 @@ class BatchedDoubleLoop:
 
     def _store_curves(self, curve, cnt, U, M, count):
         import torch
-        B, Tc = cnt.shape
-        curve.copy_(torch.stack([U.t().reshape(B, Tc, self.S + 1), M.t().reshape(B, Tc, self.S + 1)], dim=3))
+        B, Tc, slots, _ = curve.shape
+        curve.copy_(torch.stack([U.t().reshape(B, Tc, slots), M.t().reshape(B, Tc, slots)], dim=3))
         cnt.copy_(count.reshape(B, Tc))
 
     def _day_ahead_step_stochastic(self, bid=False):
@@ -933,32 +935,7 @@ class BatchedDoubleLoop:
         self._set_tracker()
         out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
         self._check(out)
-        x, rt0 = out["x"], rt0[:, 0]
-        if self.sized:                                # a sized batch states phase 2 of dsp_loop_update exactly, sums included (as the parametrized mode)
-            self._hand_off_exact(x, rt0, k)
-            return
-        self.delivered.copy_(tr.power_output(x)[:, 0])
-        for j, col in enumerate(tr.state_real):
-            self.state[:, j] = torch.round(x[:, col] * self.scale[j]) / self._scale_t[j]
-        self.revenue += self.delivered * rt0 + self.da_offer[:, k] * (self.da_prices[:, k] - rt0)
-        self.energy_mwh += self.delivered
-        self.hour_t += 1
-
-    def _hand_off_exact(self, x, rt0, k):
-        """delivered power, state, revenue, energy and clock in the arithmetic of phase 2 of dsp_loop_update, so that the tensor form and
-        the kernels agree bit for bit on the sums too: P_T[0] = fma(cb, x[b], fma(ca, x[a], const)), revenue += fma(delivered, rt,
-        da_offer * (da - rt))   (the statement of _hour_step_parametrized)"""
-        import torch
-        tr = self.tr
-        p = tr.PT_const[0].expand(self.B)
-        for e in range(tr.p0_cols.shape[0]):
-            p = exact_fma(torch, tr.p0_coef[e].expand(self.B), x[:, tr.p0_cols[e]], p)
-        self.delivered.copy_(p)
-        for j, col in enumerate(tr.state_real):
-            self.state[:, j] = torch.round(x[:, col] * self.scale[j]) / self._scale_t[j]
-        self.revenue += exact_fma(torch, self.delivered, rt0, self.da_offer[:, k] * (self.da_prices[:, k] - rt0))
-        self.energy_mwh += self.delivered
-        self.hour_t += 1
+        self._hand_off(out["x"], rt0[:, 0], k, exact=self.exact)
 
     # -- parametrized mode: two-tier closed-form curves (workflow/parametrized_bidder.py), no bidding LP ---------------------------------
     def _param_curves(self, cf):
@@ -975,15 +952,8 @@ class BatchedDoubleLoop:
         price = torch.stack([zero, zero, self.bid_price[:, None].expand_as(w)]).reshape(3, -1)
         return plant_curves(torch, power, price, torch.ones_like(power, dtype=torch.bool), p_min_cents=0)
 
-    def _store_param_curves(self, curve, cnt, U, M, count):
-        import torch
-        B, Tc = cnt.shape
-        curve.copy_(torch.stack([U.t().reshape(B, Tc, 4), M.t().reshape(B, Tc, 4)], dim=3))
-        cnt.copy_(count.reshape(B, Tc))
-
     def _day_ahead_step_parametrized(self):
         """one curve per plant-hour from the day-ahead capacity factors, cleared at the realised day-ahead price; no LP"""
-        import torch
         if self.use_fused:
             self._param(0, -1)
         else:
@@ -991,10 +961,8 @@ class BatchedDoubleLoop:
             realised = self._window(self.da_series, 24)
             self.da_offer.copy_(self._clear(U, M, count, realised))
             self.da_prices.copy_(realised)
-            self._store_param_curves(self.da_curve, self.da_count, U, M, count)
-        self.da_energy_mwh += self.da_offer.sum(1)
-        last = torch.gather(self.da_curve[:, :, :, 0], 2, (self.da_count.to(torch.int64) - 1)[:, :, None])[:, :, 0]
-        self.offered_mwh += (last.to(torch.float64) / self._hundred).sum(1)
+            self._store_curves(self.da_curve, self.da_count, U, M, count)
+        self._account_day_ahead()
 
     def _param_dispatch(self, k):
         """the first half of hour k: curves of the tracked periods, their clearing, and the tracker's LP on the cleared dispatch"""
@@ -1004,7 +972,7 @@ class BatchedDoubleLoop:
         tr = self.tr
         U, M, count = self._param_curves(self._window(self.cf_series, tr.T))
         self.rt_dispatch.copy_(self._clear(U, M, count, self._window(self.rt_series, tr.T)))
-        self._store_param_curves(self.rt_curve, self.rt_count, U, M, count)
+        self._store_curves(self.rt_curve, self.rt_count, U, M, count)
         self._set_tracker()
 
     def _param_hydrogen(self, k):
@@ -1020,7 +988,6 @@ class BatchedDoubleLoop:
         """Hour k of the day: one curve per plant and tracked period from the real-time capacity factors, cleared at the real-time price
         of that period (the perfect forecast IS the realised price; the day-ahead dispatch plays no part, as in the reference); tracking
         of the cleared dispatch (B LPs); hydrogen of the implemented hour; state hand-off, revenue and clock as _hour_step."""
-        import torch
         tr, B = self.tr, self.B
         hour = k if self.simplex_warm else None
         self._param_dispatch(k)
@@ -1030,18 +997,7 @@ class BatchedDoubleLoop:
             self._fused(2, k)                         # delivered power, state hand-off, revenue, energy, clock: unchanged (reads the tracker only)
             return
         self._check(out)
-        x, rt0 = out["x"], self._window(self.rt_series, 1)[:, 0]
-        # delivered power and revenue in the arithmetic of phase 2 of dsp_loop_update, so that this form and the kernels agree bit for
-        # bit on the sums too: P_T[0] = fma(cb, x[b], fma(ca, x[a], const)), revenue += fma(delivered, rt, da_offer * (da - rt))
-        p = tr.PT_const[0].expand(B)
-        for e in range(tr.p0_cols.shape[0]):
-            p = exact_fma(torch, tr.p0_coef[e].expand(B), x[:, tr.p0_cols[e]], p)
-        self.delivered.copy_(p)
-        for j, col in enumerate(tr.state_real):
-            self.state[:, j] = torch.round(x[:, col] * self.scale[j]) / self._scale_t[j]
-        self.revenue += exact_fma(torch, self.delivered, rt0, self.da_offer[:, k] * (self.da_prices[:, k] - rt0))
-        self.energy_mwh += self.delivered
-        self.hour_t += 1
+        self._hand_off(out["x"], self._window(self.rt_series, 1)[:, 0], k, exact=True)
 
     def _run(self, key, fn):
         import torch
@@ -1087,7 +1043,7 @@ class BatchedDoubleLoop:
     def _project_write(self, j):
         """the projection tracker's LP of chain step j (the window that starts at clock + j): dispatch rows inside the day on the
         current day-ahead dispatch, rows past midnight free on both sides (Tracker._pass_market_dispatch on a short list), state
-        columns fixed to proj_state[j], wind and c0 as _set_tracker"""
+        columns fixed to proj_state[j], wind and c0 of the window (_set_tracker_plant)"""
         if self.use_fused:
             self._project(0, j)
             return
@@ -1101,15 +1057,7 @@ class BatchedDoubleLoop:
         if known < pj.T:
             pj.rlo[:, pj.track_rows[known:]] = float("-inf")
             pj.rhi[:, pj.track_rows[known:]] = float("inf")
-        for e, col in enumerate(pj.state_init):
-            pj.lb[:, col] = self.proj_state[j, :, e]
-            pj.ub[:, col] = self.proj_state[j, :, e]
-        if pj.wind is not None:
-            cols, avail, waste = self._avail(pj, offset=j)
-            pj.ub[:, cols] = avail
-            pj.c0.copy_((pj.base_c0 if pj.c0_plant is None else pj.c0_plant) + waste)
-        else:
-            pj.c0.fill_(pj.base_c0)
+        self._set_tracker_plant(pj, self.proj_state[j], offset=j)
 
     def _project_hand_off(self, j, out):
         import torch

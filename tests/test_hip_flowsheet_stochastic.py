@@ -214,6 +214,86 @@ def test_entry_points_refuse_malformed_descriptors_on_the_host():
     assert lib.dsp_loop_market_clear(None, None, None, 0, 4, None, None, None, None) == -1
 
 
+@gpu
+def test_loop_update_refuses_malformed_descriptors_on_the_host():
+    """dsp_loop_update on descriptors of B = 3, rt.T = 4, tr.T = 2, n_state = 1 over buffers filled with a sentinel: with ONE field broken -
+    the documented "no such column" -1 in pda_cols, a power term, a dispatch row, a state or wind column outside its buffer, a state
+    column with a NULL state - every phase returns DSP_ERR_INVALID and every buffer is still all sentinel (nothing is launched).  A
+    tracker of rt.T + 1 periods whose every index is valid (the offer of its last period would silently be pt_const): phases 0 and 1
+    refuse it the same way; phase 2, which reads the tracker alone, accepts it.  The unbroken descriptors are accepted by every phase,
+    and write"""
+    import torch
+    from dispatches_amd.hip_solver import DspLoopModel, DspLoopState, load_library
+    lib = load_library()
+    dev = torch.device("cuda", 0)
+    B, n, m, N, SENTINEL = 3, 16, 5, 48, -7.0      # (m = 5 dispatch rows: room for a tracker of rt.T + 1 periods)
+    f64 = lambda *shape, fill=SENTINEL: torch.full(shape, fill, dtype=torch.float64, device=dev)
+
+    def call(edit=None, phases=(0, 1, 2)):
+        written = {f"{name}_{key}": f64(B, n if key in ("c", "lb", "ub") else m) for name in ("rt", "tr") for key in ("c", "lb", "ub", "rlo", "rhi")}
+        written.update(rt_c0=f64(B), tr_c0=f64(B), state=f64(B, 1), delivered=f64(B), revenue=f64(B), energy_mwh=f64(B))
+        read = dict(x=f64(B, n, fill=2.0), base_c=f64(n, fill=0.5), series=f64(N, fill=0.25), offers=f64(B, 24, fill=3.0),
+                    start=torch.arange(B, dtype=torch.int64, device=dev), hour=torch.zeros((), dtype=torch.int64, device=dev),
+                    bad=torch.zeros((), dtype=torch.bool, device=dev), uncertified=torch.zeros((), dtype=torch.int64, device=dev))
+        st = DspLoopState()
+        st.B, st.N, st.start, st.hour = B, N, read["start"].data_ptr(), read["hour"].data_ptr()
+        st.da_series = st.rt_series = st.cf_series = read["series"].data_ptr()
+        st.state, st.da_offer, st.da_prices = written["state"].data_ptr(), read["offers"].data_ptr(), read["offers"].data_ptr()
+        st.state_scale[0] = st.state_scale[1] = 100.0
+        st.delivered, st.revenue, st.energy_mwh = (written[key].data_ptr() for key in ("delivered", "revenue", "energy_mwh"))
+        st.bad, st.uncertified = read["bad"].data_ptr(), read["uncertified"].data_ptr()
+        rt, tr = DspLoopModel(), DspLoopModel()
+        for name, w, T in (("rt", rt, 4), ("tr", tr, 2)):
+            w.c, w.lb, w.ub, w.rlo, w.rhi, w.c0 = (written[f"{name}_{key}"].data_ptr() for key in ("c", "lb", "ub", "rlo", "rhi", "c0"))
+            w.base_c, w.x = read["base_c"].data_ptr(), read["x"].data_ptr()
+            w.n, w.m, w.T, w.n_state = n, m, T, 1
+            for t in range(16):
+                live = t < T
+                w.pt_cols[t][0], w.pt_cols[t][1] = (t if live else -1), (4 + t if live and t % 2 == 0 else -1)     # odd periods have ONE term
+                w.pt_coef[t][0], w.pt_coef[t][1], w.pt_const[t] = CA, CB, 0.5
+                w.pda_cols[t] = 6 + t if live and name == "rt" else -1
+                w.track_rows[t] = 2 * t if live and name == "tr" else -1
+                w.wind_cols[t] = 10 + t if live else -1
+            w.state_init[0], w.state_real[0] = 14, 15
+            w.wind_kw, w.waste_per_kw, w.c0_base = 100.0, 1e-3, 17.5
+        if edit is not None:
+            edit(st, rt, tr)
+        rcs = [lib.dsp_loop_update(C.byref(st), C.byref(rt), C.byref(tr), phase, 5, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+               for phase in phases]
+        torch.cuda.synchronize()
+        return rcs, {key: v.cpu().numpy() for key, v in written.items()}, int(read["hour"].item())
+
+    def item(which, name, at, value):
+        def edit(st, rt, tr):
+            target = getattr(rt if which == "rt" else tr, name)
+            if isinstance(at, tuple):
+                target[at[0]][at[1]] = value
+            else:
+                target[at] = value
+        return edit
+    broken = [item("rt", "pda_cols", 1, -1), item("rt", "pt_cols", (2, 1), n), item("tr", "pt_cols", (0, 0), n), item("tr", "track_rows", 0, m),
+              item("rt", "state_init", 0, -1), item("tr", "state_init", 0, -1), item("tr", "state_real", 0, n),
+              lambda st, rt, tr: setattr(st, "state", None),
+              item("tr", "wind_cols", 1, n), item("rt", "wind_cols", 3, -1), lambda st, rt, tr: setattr(st, "cf_series", None)]
+    for at, edit in enumerate(broken):
+        rcs, out, hour = call(edit)
+        assert rcs == [-1, -1, -1] and hour == 0 and all((v == SENTINEL).all() for v in out.values()), at
+
+    def longer_tracker(st, rt, tr):                 # tr.T = rt.T + 1 = 5 and NOTHING else wrong: distinct dispatch rows, columns in range
+        tr.T = rt.T + 1
+        for t, (row, wind) in enumerate(((0, 10), (2, 11), (1, 12), (3, 13), (4, 9))):
+            tr.track_rows[t], tr.wind_cols[t] = row, wind
+            tr.pt_cols[t][0], tr.pt_cols[t][1] = t, -1
+    rcs, out, hour = call(longer_tracker, phases=(0, 1))
+    assert rcs == [-1, -1] and hour == 0 and all((v == SENTINEL).all() for v in out.values())
+    rcs, out, hour = call(longer_tracker, phases=(2,))
+    assert rcs == [0] and hour == 1 and all((out[key] != SENTINEL).all() for key in ("state", "delivered", "revenue", "energy_mwh"))
+    rcs, out, hour = call()
+    assert rcs == [0, 0, 0] and hour == 1
+    assert all((out[key] != SENTINEL).all() for key in ("rt_c0", "tr_c0", "state", "delivered", "revenue", "energy_mwh"))
+    assert (out["rt_ub"][:, 10:14] == 25.0).all() and (out["tr_rlo"][:, [0, 2]] != SENTINEL).all() and (out["tr_rlo"][:, [1, 3, 4]] == SENTINEL).all()
+
+
 def _snapshot(loop):
     res, ok = loop.results()
     out = {k: v.cpu().numpy().copy() for k, v in res.items()}
