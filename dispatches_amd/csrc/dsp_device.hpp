@@ -126,7 +126,8 @@ constexpr unsigned long long kBuildSwitches = DSP_SW_TRACE | DSP_SW_PROF | DSP_S
 constexpr unsigned long long kSolveArgsToken =
     ((unsigned long long)sizeof(SolveArgs) << 40) ^ ((unsigned long long)__builtin_offsetof(SolveArgs, opt) << 28) ^
     ((unsigned long long)__builtin_offsetof(SolveArgs, queue) << 16) ^ ((unsigned long long)sizeof(DeviceProblem) << 52) ^
-    ((unsigned long long)DSP_VERSION << 8) ^ kBuildSwitches;
+    ((unsigned long long)DSP_VERSION << 8) ^ kBuildSwitches ^
+    ((unsigned long long)rare_lds_bytes(0) << 20);          // (the waves' LDS regions are sized by the library, laid out by the kernel)
 
 // in-wave dense simplex for tiny LPs (dsp_simplex.hip)
 struct SimplexArgs {

@@ -125,12 +125,15 @@ struct RegEll {
     // Two passes: ALL loads first, then the conversions.  (One pass - load, scale, fold the address, pin it with the asm
     // below - made every entry wait for its own load: total() serialised L2 round trips at every restart that changes the
     // weight, 16 on the 24-h shape = ~7800 cycles = 10 iterations, 28 on the 48-h one; tools/gpu_check_profile.py.)
-    // The lane's base address is made opaque HERE: left to itself the compiler forms the total() entry addresses once per
-    // kernel (they are loop-invariant), runs out of registers for them and reloads each from scratch before its load.
-    const Entry *gl = g + lane;
+    // The lane's byte offset is made opaque HERE: left to itself the compiler forms the total() entry addresses once per
+    // kernel (they are loop-invariant), runs out of registers for them and reloads each from scratch before its load.  (The
+    // offset, not the base address g + lane: that sum is loop-invariant too, was formed once per kernel, spilled, and came back
+    // from scratch behind an s_waitcnt of its own in front of the loads of every restart.)
+    uint32_t lane_off = (uint32_t)sizeof(Entry) * (uint32_t)lane;
 #ifndef DSP_NO_OPAQUE_BASE
-    asm volatile("" : "+v"(gl));
+    asm volatile("" : "+v"(lane_off));
 #endif
+    const Entry *gl = reinterpret_cast<const Entry *>(reinterpret_cast<const char *>(g) + lane_off);
     typedef int v4i __attribute__((ext_vector_type(4)));                 // (a plain vector type: HIP's int4 class has no
     using gv4i = const __attribute__((address_space(1))) v4i;            //  assignment from an address-space-qualified source)
     gv4i *gp = (gv4i *)gl;
@@ -143,6 +146,21 @@ struct RegEll {
       off[t] = (uint32_t)raw[t].z + vec_lds;
       asm volatile("" : "+v"(off[t]));             // keep the folded address in a VGPR (no re-add per iteration)
     }
+  }
+  // The same re-read in two halves, for the restart block: fetch() issues the loads of the VALUES (the folded offsets do not
+  // depend on the scale) as soon as a restart is decided, rescale() multiplies when the new weight is known - the L2 round trip
+  // runs under the reduction and the weight update instead of after them.  v = scale * value, the multiplication of load().
+  __device__ __forceinline__ void fetch(const Entry *__restrict__ g, int lane, double (&raw)[N]) const {
+    uint32_t lane_off = (uint32_t)sizeof(Entry) * (uint32_t)lane;
+    asm volatile("" : "+v"(lane_off));
+    using gdbl = const __attribute__((address_space(1))) double;
+    gdbl *gp = (gdbl *)(reinterpret_cast<const char *>(g) + lane_off);
+#pragma unroll
+    for (int t = 0; t < total(); ++t) raw[t] = gp[t * 64 * (int)(sizeof(Entry) / sizeof(double))];
+  }
+  __device__ __forceinline__ void rescale(double scale, const double (&raw)[N]) {
+#pragma unroll
+    for (int t = 0; t < total(); ++t) v[t] = scale * raw[t];
   }
   // out = init + (scaled matrix) * (vector in LDS); out and init may be the same array
   __device__ __forceinline__ void product(double (&out)[S], const double (&init)[S]) const {
@@ -201,6 +219,14 @@ __device__ __forceinline__ void stage_entries(Entry *dst, const Entry *__restric
 // (register-resident kernels): a lane-private copy in the wave's LDS region, read where it is used - kept in registers these
 // values (2 RPL + 9 doubles per lane) are what the allocator spills first, and the rare blocks then reload them from scratch
 // one memory round trip at a time.  L = false: a plain register (the LDS-matrix kernels run 8 waves per block).
+#ifndef DSP_EARLY_MAT_UPTO
+#define DSP_EARLY_MAT_UPTO 8
+#endif
+// Only the row bounds are per lane (slot k of the lane at + 512 k).  The nine values that are the same in every lane (norms,
+// objective offset, weight guards, polish state, objective) have ONE 8-byte slot per wave at a wave-uniform address: every lane
+// stores the same number, and what is read back is uniform to the compiler, so every test on it - and on the weight, the step
+// sizes and the counters that depend on it - is a scalar branch (v_cmp + s_cbranch_vcc), not an EXEC-mask region.  Read from
+// lane-private copies they made the whole check path, down to the hot loop's back edge, divergent in the compiler's eyes.
 template <bool L>
 struct Rare {
   double v;
@@ -212,6 +238,8 @@ struct Rare {
 template <int CPL, int RPL, bool LONG, unsigned WC, unsigned WR, bool QP = false>
 __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 256 : 512, (CPL + RPL <= 6) ? DSP_MIN_WAVES_SMALL : ((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 1 : 2)) pdlp_solve_kernel(SolveArgs a) {
   constexpr bool MATREG = WC != 0;
+  constexpr bool EARLY_MAT = MATREG && CPL + RPL <= DSP_EARLY_MAT_UPTO;   // restart block: matrix re-read issued ahead of the weight update
+  constexpr bool RLDS = MATREG;                                        // rare per-scenario values in LDS (struct Rare)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // after a simplex pass that certified every scenario there is nothing to do (one scalar load per wave)
   if (a.skip_solved == 1 && __builtin_amdgcn_readfirstlane(*a.unsolved) == 0) return;
@@ -229,7 +257,7 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
   const DeviceProblem &P = a.P;
   const dsp_batch &b = a.b;
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform, and known to be)
 
   // ---- carve LDS: shared matrix region, then one exchange buffer pair per wave ----------------------------
   Entry *ellc = reinterpret_cast<Entry *>(smem);                       // A^T (columns)  [Wc*CPL*64]
@@ -255,14 +283,15 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
   const uint32_t scl_lds = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)(wave_buf + (size_t)(blockDim.x >> 6) * ((size_t)(P.n_pad + P.m_pad) * 8 + (MATREG ? rare_lds_bytes(RPL) : 0))) + 8u * (uint32_t)lane;
   DSP_TRACE("[trace] staged: Wc=%d Wr=%d B=%d maxit=%d\n", P.Wc, P.Wr, b.B, a.opt.max_iter);
 
-  constexpr bool RLDS = MATREG;                                        // rare per-scenario values in LDS (struct Rare)
   const size_t wave_stride = (size_t)(P.n_pad + P.m_pad) * 8 + (RLDS ? rare_lds_bytes(RPL) : 0);
   char *xb = wave_buf + (size_t)wave * wave_stride;                    // gathered by row products
   char *yb = xb + (size_t)P.n_pad * 8;                                 // gathered by column products
   // LDS byte addresses of this lane's own elements in the exchange buffers (permuted slots: dsp_prepare.hpp, optimise_slots)
   using lds_cptr = const __attribute__((address_space(3))) char *;
   const uint32_t xb_lds = (uint32_t)(uintptr_t)(lds_cptr)xb, yb_lds = (uint32_t)(uintptr_t)(lds_cptr)yb;
-  const uint32_t rare_lds = yb_lds + 8u * (uint32_t)P.m_pad + 8u * (uint32_t)lane;   // slot k of struct Rare at + 512 k
+  const uint32_t rare_lds = yb_lds + 8u * (uint32_t)P.m_pad + 8u * (uint32_t)lane;   // per-lane slot k of struct Rare at + 512 k
+  const uint32_t rare_uni = yb_lds + 8u * (uint32_t)P.m_pad + 1024u * RPL;           // wave-uniform slot k at + 8 k
+  static_assert(!RLDS || rare_lds_bytes(RPL) == 1024 * RPL + 8 * 9, "host LDS sizing (dsp_capi.hip) and the layout of struct Rare disagree");
   // SHARED (shapes with more than 8 owned elements per lane): the host built the same slot map for every 64-position block,
   // so ONE address register per buffer + the compile-time offsets 512 q serve all owned elements (the stores pair up into
   // ds_write2_b64); with one address VGPR per element the 48-h kernel reloaded three of them from scratch EVERY iteration
@@ -320,11 +349,11 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
   const int kkt_every = a.opt.kkt_every > 0 ? a.opt.kkt_every : 1;
   // the restart / steady tests on SQUARED residuals: r <= beta r0  <=>  r^2 <= beta^2 r0^2,
   // |r - rprev| <= s r  <=>  (1 - s)^2 r^2 <= rprev^2 <= (1 + s)^2 r^2
-  const double beta_s2 = a.opt.restart_sufficient * a.opt.restart_sufficient;
-  const double beta_n2 = a.opt.restart_necessary * a.opt.restart_necessary;
-  const double steady_lo2 = (1.0 - a.opt.jump_steady) * (1.0 - a.opt.jump_steady);
-  const double steady_hi2 = (1.0 + a.opt.jump_steady) * (1.0 + a.opt.jump_steady);
-  const double ieta = 1.0 / a.eta;
+  // These factors (and 1 / eta) are formed WHERE THEY ARE USED, from the kernel arguments (scalar registers): computed once up
+  // here they are wave-uniform doubles that sit in VGPRs through the whole solve, the register file is full, and they are what the
+  // allocator spills - four scratch reloads, each behind its own s_waitcnt, on the path of every check.  `opt_here` keeps the
+  // compiler from hoisting them back out of the loop.
+  auto opt_here = [](double v) __attribute__((always_inline)) { asm volatile("" : "+s"(v)); return v; };
   // The step sizes are folded into the products: out = init + tau A^T (vector in yb) and out = init - sig A (vector in
   // xb).  Register-resident matrices hold tau A^T / -sig A themselves, so a PDHG half-step is the FMA chain alone;
   // the LDS matrix is shared by the block's waves (each with its own weight) and is scaled on the way out.
@@ -408,9 +437,10 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
       for (int q = 0; q < RPL; ++q) rlo[q].addr = rare_lds + 512u * (k_++);
 #pragma unroll
       for (int q = 0; q < RPL; ++q) rhi[q].addr = rare_lds + 512u * (k_++);
-      qn.addr = rare_lds + 512u * (k_++); cn.addr = rare_lds + 512u * (k_++); c0.addr = rare_lds + 512u * (k_++);
-      w_lo.addr = rare_lds + 512u * (k_++); w_hi.addr = rare_lds + 512u * (k_++); w_init.addr = rare_lds + 512u * (k_++);
-      pol_best.addr = rare_lds + 512u * (k_++); pol_po.addr = rare_lds + 512u * (k_++); pobj.addr = rare_lds + 512u * (k_++);
+      k_ = 0;
+      qn.addr = rare_uni + 8u * (k_++); cn.addr = rare_uni + 8u * (k_++); c0.addr = rare_uni + 8u * (k_++);
+      w_lo.addr = rare_uni + 8u * (k_++); w_hi.addr = rare_uni + 8u * (k_++); w_init.addr = rare_uni + 8u * (k_++);
+      pol_best.addr = rare_uni + 8u * (k_++); pol_po.addr = rare_uni + 8u * (k_++); pobj.addr = rare_uni + 8u * (k_++);
     }
     double kap[QP ? RPL : 1], srow[QP ? RPL : 1];        // QP: scaled compliance kappa d_r^2 and 1 / (1 + sig kappa)
     double nrm[4] = {0.0, 0.0, 0.0, 0.0};                // |q|^2 unscaled, |c|^2 unscaled, |q|^2 scaled, |c|^2 scaled
@@ -577,17 +607,21 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
     // and the step-scaled register matrices: functions of the primal weight, refreshed only where it changes (one FP64
     // division; the matrices are re-read from L2, 16 bytes per entry and lane, so they stay exact)
     double tau, sig, iw, ylo[RPL], yhi[RPL];
-#define DSP_SET_STEPS()                                                                                     \
+#define DSP_SET_STEPS() { DSP_SET_SCALARS() DSP_SET_MATRICES() }
+#define DSP_SET_MATRICES()                                                                                  \
+  {                                                                                                         \
+    if constexpr (MATREG) {                                                                                 \
+      mreg_c.load(P.mr_ellc, lane, yb_lds, tau);                                                            \
+      mreg_r.load(P.mr_ellr, lane, xb_lds, -sig);                                                           \
+    }                                                                                                       \
+  }
+#define DSP_SET_SCALARS()                                                                                   \
   {                                                                                                         \
     iw = 1.0 / w;                                                                                           \
     tau = eta * iw;                                                                                         \
     sig = eta * w;                                                                                          \
     _Pragma("unroll") for (int q = 0; q < RPL; ++q) { ylo[q] = -(sig * rhi[q].get()); yhi[q] = -(sig * rlo[q].get()); } \
     if constexpr (QP) { _Pragma("unroll") for (int q = 0; q < RPL; ++q) srow[q] = 1.0 / fma(sig, kap[q], 1.0); } \
-    if constexpr (MATREG) {                                                                                 \
-      mreg_c.load(P.mr_ellc, lane, yb_lds, tau);                                                            \
-      mreg_r.load(P.mr_ellr, lane, xb_lds, -sig);                                                           \
-    }                                                                                                       \
   }
     DSP_SET_STEPS()
     DSP_TRACE("[trace] enter loop\n");
@@ -648,6 +682,7 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
           for (int q = 0; q < CPL; ++q) lds_store_f64(xw[q], xp[q]);
           wave_lds_fence();
           row_step(axp, zero_r, -sig);                   // -sig A x+
+          const double ieta = 1.0 / opt_here(a.eta);
           const double itau = w * ieta, nisig = -(iw * ieta);
           // red: 0 pres^2, 1 dres^2, 2 pobj, 3 dobj, 4 sum|y| viol, 5 sum|c x|, 6 sum|dual residual| |x|
           //      (4 and 6 bound the objective error caused by the remaining infeasibility)
@@ -782,6 +817,8 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
         }
         // ---- restart test (r0 = residual at the first check after a restart) ----------------------------------
         const bool first = !(r0 < INFINITY);
+        const double rs_ = opt_here(a.opt.restart_sufficient), rn_ = opt_here(a.opt.restart_necessary);
+        const double beta_s2 = rs_ * rs_, beta_n2 = rn_ * rn_;
         const bool decayed = (r <= beta_s2 * r0) || (r <= beta_n2 * r0 && r > rprev);
         const bool artificial = (double)k >= a.opt.restart_artificial * (double)(it - it0 + 1);
         const bool give_up_warm = warm && it >= a.opt.warm_patience;
@@ -797,6 +834,8 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
 #else
         // steady residual over two checks, or (chaining, ray_jumps = 2) the previous event was a jump: a landing point
         // usually lies on the next piece's ray already, so it is tested again at its first check
+        const double js_ = opt_here(a.opt.jump_steady);
+        const double steady_lo2 = (1.0 - js_) * (1.0 - js_), steady_hi2 = (1.0 + js_) * (1.0 + js_);
         const bool steady = a.opt.ray_jumps && !do_restart && k >= jump_not_before &&
                             ((k >= 2 * check_every && rprev >= steady_lo2 * r && rprev <= steady_hi2 * r) ||
                              (a.opt.ray_jumps > 1 && lastjump && k >= check_every));
@@ -804,6 +843,10 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
         if (first) r0 = r;
         rprev = r;
         if (do_restart) {
+          // the matrix values are on their way while the displacement is reduced and the weight updated (EARLY_MAT: shapes
+          // whose register file has room for them next to the iterate)
+          double mat_c[EARLY_MAT ? RegEll<CPL, WC>::N : 1], mat_r[EARLY_MAT ? RegEll<RPL, WR>::N : 1];
+          if constexpr (EARLY_MAT) { mreg_c.fetch(P.mr_ellc, lane, mat_c); mreg_r.fetch(P.mr_ellr, lane, mat_r); }
           double dd[2] = {0.0, 0.0};
 #pragma unroll
           for (int q = 0; q < CPL; ++q) { const double t = xp[q] - x0[q]; dd[0] = fma(t, t, dd[0]); }
@@ -826,11 +869,16 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
             // log(w |dx| / |dy|) and the exponential in single precision (hardware v_log_f32 / v_exp_f32): the weight
             // is a heuristic parameter, 1e-7 relative noise on it is irrelevant and FP64 log + exp cost ~150 instructions
             const float e = __logf((float)w) + 0.5f * (__logf((float)dd[0]) - __logf((float)dd[1]));
-            const float dl = fminf(fmaxf(-(float)a.opt.pid_kp * e, -(float)a.opt.max_dlog_weight), (float)a.opt.max_dlog_weight);
+            const float kp_ = (float)opt_here(a.opt.pid_kp), md_ = (float)opt_here(a.opt.max_dlog_weight);
+            const float dl = fminf(fmaxf(-kp_ * e, -md_), md_);
             w *= (double)__expf(dl);
           }
           { const double wl_ = w_lo.get(); w = fmin(fmax(w, wl_), fmax(w_hi.get(), wl_)); }
-          if (w != w_was) DSP_SET_STEPS()
+          if constexpr (EARLY_MAT) {
+            if (w != w_was) { DSP_SET_SCALARS() mreg_c.rescale(tau, mat_c); mreg_r.rescale(-sig, mat_r); }
+          } else {
+            if (w != w_was) DSP_SET_STEPS()
+          }
 #pragma unroll
           for (int q = 0; q < CPL; ++q) { x[q] = xp[q]; x0[q] = xp[q]; }
 #pragma unroll
@@ -854,6 +902,7 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
           // two extra products fit without new spills on the common paths (in the KKT block they cost the 48-h kernel 10 %).
           if constexpr (CERT) if (suspect) {
             DSP_PDHG_STEP()                                // (x+, y+) = T(x, y) from the restart point: the displacement the certificates use
+            const double ieta = 1.0 / opt_here(a.eta);
             const double itau = w * ieta, nisig = -(iw * ieta);
             double atyp[CPL], axp[RPL];
             double rr[6] = {0, 0, 0, 0, 0, 0};   // 0 |dual residual of the ray|^2, 1 its bound value, 2 |bounds|^2, 3 |recession violation|^2, 4 c.d, 5 |c|^2
@@ -933,7 +982,8 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
           // the ratio test (one FP64 division per owned element + a wave-min) only for rays that pass the translation
           // test: about one attempt in ten
           double alpha = 0.0;
-          if (tt[1] > 0.0 && tt[0] <= a.opt.jump_tol * a.opt.jump_tol * tt[1]) {
+          const double jt_ = opt_here(a.opt.jump_tol);
+          if (tt[1] > 0.0 && tt[0] <= jt_ * jt_ * tt[1]) {
             // the unprojected points of the FIRST application, recomputed (bit-identical to what the step above had)
             double g0x[CPL], g0y[RPL];
 #pragma unroll
@@ -983,6 +1033,8 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
     }
 #undef DSP_PDHG_STEP
 #undef DSP_SET_STEPS
+#undef DSP_SET_SCALARS
+#undef DSP_SET_MATRICES
 #undef DSP_HALPERN_STEP
 
     DSP_TRACE("[trace] store status=%d it=%d\n", status, it);
@@ -1003,6 +1055,7 @@ __global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 
         wave_lds_fence();
         double axq[RPL];
         row_step(axq, zero_r, -sig);                     // -sig A x+
+        const double ieta = 1.0 / opt_here(a.eta);
 #pragma unroll
         for (int q = 0; q < RPL; ++q)
           if (kap[q] > 0.0) { const double dev = -(iw * ieta) * axq[q] - rlo[q].get(); po = fma(0.5 * dev, dev / kap[q], po); }

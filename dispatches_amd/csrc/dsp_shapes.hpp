@@ -9,8 +9,9 @@ namespace dsp {
 constexpr bool shared_slot_maps(int cpl, int rpl) { return cpl + rpl > 8; }   // (>= 6 measured: -1.5 % on the 24-h metric kernel, more gather conflicts)
 
 // Register-resident solve kernels keep the per-scenario values that only their rare blocks touch (row bounds, norms, weight
-// guards, ...: struct Rare in dsp_kernels.hip) in the wave's LDS region: 2 rpl + 9 lane-private doubles.
-constexpr int rare_lds_bytes(int rpl) { return (2 * rpl + 9) * 512; }
+// guards, ...: struct Rare in dsp_kernels.hip) in the wave's LDS region: 2 rpl lane-private doubles (the row bounds) and 9
+// wave-uniform ones, 8 bytes each.
+constexpr int rare_lds_bytes(int rpl) { return 2 * rpl * 512 + 9 * 8; }
 // Every solve kernel stages the scale factors of the owned columns / rows behind the waves' buffers, once per block:
 // [cpl + rpl][64] doubles (the KKT test measures its residuals in the unscaled space).
 constexpr int scale_lds_bytes(int cpl, int rpl) { return (cpl + rpl) * 512; }
