@@ -206,6 +206,14 @@ __device__ __forceinline__ void stage_entries(Entry *dst, const Entry *__restric
 #ifndef DSP_MIN_WAVES_SMALL
 #define DSP_MIN_WAVES_SMALL 2
 #endif
+// The metric kernel - the 24-h wind + battery LP, <4, 2, false, 0x1133, 0x44> - is compiled for THREE waves per SIMD (168 VGPRs): its
+// plain-iteration loop stays free of scratch there and, since the check path lost its spills on the common paths, the third wave's
+// latency hiding outweighs the spills of the rare blocks (profiles/HISTORY.md, "Three waves for the metric kernel, r81a").  That
+// shape alone: it is the one this was measured on; at 168 VGPRs the nuclear 24-h kernel and the generic one gain scratch on paths
+// that have none at two waves, and the padded <4, 2> shape holds 24 matrix entries per lane instead of 16.
+constexpr bool three_waves_shape(int cpl, int rpl, unsigned wc, unsigned wr, bool qp) {
+  return !qp && cpl == 4 && rpl == 2 && wc == 0x1133u && wr == 0x44u;
+}
 #ifndef DSP_ONE_WAVE_FROM
 #define DSP_ONE_WAVE_FROM 99      /* CPL + RPL from which the kernel is compiled for ONE wave per SIMD (512 registers: 256 V + 256 A) */
 #endif
@@ -236,7 +244,7 @@ struct Rare {
 };
 
 template <int CPL, int RPL, bool LONG, unsigned WC, unsigned WR, bool QP = false>
-__global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 256 : 512, (CPL + RPL <= 6) ? DSP_MIN_WAVES_SMALL : ((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 1 : 2)) pdlp_solve_kernel(SolveArgs a) {
+__global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 256 : 512, three_waves_shape(CPL, RPL, WC, WR, QP) ? 3 : (CPL + RPL <= 6) ? DSP_MIN_WAVES_SMALL : ((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 1 : 2)) pdlp_solve_kernel(SolveArgs a) {
   constexpr bool MATREG = WC != 0;
   constexpr bool EARLY_MAT = MATREG && CPL + RPL <= DSP_EARLY_MAT_UPTO;   // restart block: matrix re-read issued ahead of the weight update
   constexpr bool RLDS = MATREG;                                        // rare per-scenario values in LDS (struct Rare)
