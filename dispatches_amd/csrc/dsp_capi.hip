@@ -449,21 +449,39 @@ static bool loop_market_state_ok(const dsp_loop_market_state *st) {
   if (!st || st->B < 0 || st->N < 1 || st->S < 1 || st->S > DSP_MARKET_MAX_S || st->p_min_cents < 0 || st->p_min_cents > 2000000000ll) return false;
   if (st->backcast ? (st->D < 1 || st->S > st->D || 24ll * st->D > st->N) : st->S != 1) return false;
   if (st->rt_history_lag_days < 0 || (st->backcast && 24ll * ((long long)st->D + st->rt_history_lag_days) > st->N)) return false;      // (ABI 17)
+  if (st->self_schedule < 0 || st->self_schedule > 1) return false;                                                                     // (ABI 18)
+  if (st->curve_slots != 0 && (st->curve_slots < st->S + 1 || st->curve_slots > DSP_MARKET_MAX_S + 1)) return false;
   return st->start && st->hour && st->da_series && st->rt_series;
 }
 static bool loop_market_model_ok(const dsp_loop_market_model *m) {
-  return m && m->n >= 1 && m->T >= 1 && m->T <= DSP_MARKET_MAX_T && m->n_state >= 0 && m->n_state <= 2;
+  return m && m->n >= 1 && m->T >= 1 && m->T <= DSP_MARKET_MAX_T && m->n_state >= 0 && m->n_state <= 2 &&
+         (m->row_stride == 0 || m->row_stride >= m->n);                                                                                 // (ABI 18)
+}
+// the checks dsp_loop_market_prepare and dsp_loop_schedule_prepare share: every buffer and column index a lane writes through
+static bool loop_market_prepare_ok(const dsp_loop_market_state *st, const dsp_loop_market_model *m) {
+  if (!m->c || !m->lb || !m->ub || !m->base_c || !m->c0) return false;
+  if ((m->n_state > 0 && !st->state) || !loop_cols_ok(m->state_init, m->n_state, m->n)) return false;
+  if (!loop_wind_ok(m->wind_cols, m->T, m->n, st->cf_series) || !plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return false;
+  return loop_cols_ok(m->pda_cols, m->T, m->n) && loop_terms_ok(m->pt_cols, m->T, m->n);
 }
 
 int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, int32_t k, void *hipStream) {
   if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < -1 || k > 23) return DSP_ERR_INVALID;
-  if (!m->c || !m->lb || !m->ub || !m->base_c || !m->c0) return DSP_ERR_INVALID;
+  if (m->row_stride != 0 && m->row_stride != m->n) return DSP_ERR_INVALID;      // (ABI 18: its rows are n apart)
   if (k >= 0 && (!st->da_offer || !st->da_prices)) return DSP_ERR_INVALID;
-  if ((m->n_state > 0 && !st->state) || !loop_cols_ok(m->state_init, m->n_state, m->n)) return DSP_ERR_INVALID;
-  if (!loop_wind_ok(m->wind_cols, m->T, m->n, st->cf_series) || !plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return DSP_ERR_INVALID;
-  if (!loop_cols_ok(m->pda_cols, m->T, m->n) || !loop_terms_ok(m->pt_cols, m->T, m->n)) return DSP_ERR_INVALID;
+  if (!loop_market_prepare_ok(st, m)) return DSP_ERR_INVALID;
   if (st->B == 0) return DSP_OK;
   HIP_TRY(launch_loop_market_prepare(*st, *m, (int)k, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
+// the coupled day-ahead LP of a self-scheduling plant (ABI 18): `m` describes one of the S blocks of a row of row_stride doubles
+int dsp_loop_schedule_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, void *hipStream) {
+  if (!loop_market_state_ok(st) || !loop_market_model_ok(m)) return DSP_ERR_INVALID;
+  if ((long long)m->row_stride < (long long)st->S * m->n) return DSP_ERR_INVALID;
+  if (!loop_market_prepare_ok(st, m) || m->wind_kw_plant || m->c0_base_plant) return DSP_ERR_INVALID;
+  if (st->B == 0) return DSP_OK;
+  HIP_TRY(launch_loop_schedule_prepare(*st, *m, (hipStream_t)hipStream));
   return DSP_OK;
 }
 

@@ -14,6 +14,8 @@
 //                           -Rpass-analysis=kernel-resource-usage); duplicates, the zero-power point and the running maximum are one
 //                           pass over the sorted registers, which also clears the curve at the price that occurs.
 //
+//   loop_schedule_prepare_kernel   the coupled day-ahead LP of a self-scheduling plant (dsp_loop_schedule_prepare): S scenario blocks in
+//                           ONE row per plant, one lane per (plant, scenario), the row's constant summed in the order of i by one lane.
 //   loop_market_prepare_kernel / loop_market_clear_kernel   the same two for ANY flowsheet, by descriptor (dsp_loop_market_*; rolling_flowsheets.py):
 //                           power P_T = (x[a] ca + x[b] cb) + const, curves that start at the generator's p_min, <= 2 state columns,
 //                           optional wind; the clearing lanes also write the tracker's LP (a dsp_loop_model).  VGPRs / scratch of every
@@ -221,6 +223,60 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
   }
 }
 
+// The coupled day-ahead LP of a self-scheduling plant (dsp_loop_schedule_prepare, ABI 18): S scenario blocks of m.n columns side by side
+// in row b (m.row_stride doubles apart), one lane per (plant, scenario).  Block i is written as loop_market_prepare_kernel with k = -1
+// writes row b * S + i; the lane of scenario 0 also sums the S objective constants in the order of i - alone, so that the order is the
+// tensor form's (BatchedDoubleLoop._day_ahead_step_self_schedule).
+__global__ void __launch_bounds__(256) loop_schedule_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= s.B * s.S) return;
+  const int b = r / s.S, i = r - b * s.S;
+  const long long h = *s.hour, st0 = s.start[b];
+  const bool wind = m.wind_cols[0] >= 0;
+  const size_t at0 = (size_t)b * m.row_stride + (size_t)i * m.n;
+  double *c = m.c + at0, *lb = m.lb + at0, *ub = m.ub + at0;
+  double avail_sum = 0.0;
+  for (int t = 0; t < m.T; ++t) {
+    const long long at = loop_scenario_index(s, st0, h, i, 0, t);
+    const double rtp = s.rt_series[lmk_rt(s, at)];
+    const double dap = s.da_series[at];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int col = m.pt_cols[t][e];
+      if (col >= 0) c[col] = __dsub_rn(m.base_c[col], loop_opaque(__dmul_rn(m.pt_coef[t][e], rtp)));
+    }
+    const int pda = m.pda_cols[t];
+    c[pda] = __dsub_rn(m.base_c[pda], loop_opaque(__dsub_rn(dap, rtp)));
+    if (wind) {
+      const double avail = loop_opaque(__dmul_rn(m.wind_kw, s.cf_series[(st0 + h + t) % s.N]));
+      ub[m.wind_cols[t]] = avail;
+      avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
+    }
+    lb[pda] = 0.0;
+    ub[pda] = INFINITY;
+  }
+  for (int j = 0; j < m.n_state; ++j) {
+    const double v = s.state[(size_t)b * m.n_state + j];
+    lb[m.state_init[j]] = v; ub[m.state_init[j]] = v;
+  }
+  if (i != 0) return;
+  // ---- the row's objective constant: the S scenario constants added in the order of i ----
+  const double waste = wind ? loop_opaque(__dmul_rn(m.waste_per_kw, avail_sum)) : 0.0;
+  double total = 0.0;
+  for (int j = 0; j < s.S; ++j) {
+    double price_sum = 0.0;
+    for (int t = 0; t < m.T; ++t) {
+      const double rtp = s.rt_series[lmk_rt(s, loop_scenario_index(s, st0, h, j, 0, t))];
+      const double pc = loop_opaque(__dmul_rn(rtp, m.pt_const[t]));
+      price_sum = t ? __dadd_rn(price_sum, pc) : pc;
+    }
+    double c0 = loop_opaque(__dsub_rn(m.c0_base, price_sum));
+    if (wind) c0 = loop_opaque(__dadd_rn(c0, waste));
+    total = j ? __dadd_rn(total, c0) : c0;
+  }
+  m.c0[b] = total;
+}
+
 template <int SP>
 __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_state s, dsp_loop_market_model m, dsp_loop_model tr, int has_tr,
                                                                 int k, int T, double *dispatch, int32_t *curve, int32_t *count) {
@@ -243,7 +299,7 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
     if (i < S) {
       const size_t row = (size_t)b * S + i;
       if (m.status[row] == 0) {
-        const double *x = m.x + row * m.n;
+        const double *x = m.x + row * (size_t)(m.row_stride ? m.row_stride : m.n);      // (ABI 18: block 0 of a coupled row)
         double power;
         if (k < 0) {
           power = x[ca];
@@ -253,7 +309,7 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
           power = __dadd_rn(p, fc);
         }
         const long long at = loop_scenario_index(s, st0, h, i, hod, t);
-        const double price = series[k < 0 ? at : lmk_rt(s, at)];
+        const double price = s.self_schedule ? 0.0 : series[k < 0 ? at : lmk_rt(s, at)];      // (ABI 18: a schedule is offered at cost 0)
         const long long pc = bid_cents(power), cc = bid_cents(price);
         if (pc >= pmin && fabs(power) < INFINITY && fabs(price) < INFINITY) key = bid_key(pc, cc);
       } else {
@@ -269,7 +325,8 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
   // ---- the price that occurs: realised for the day-ahead market and for the hour at hand, scenario 0's for the look-ahead hours ----
   const double lmp = (k < 0 || t == 0) ? series[(st0 + h + t) % s.N] : series[lmk_rt(s, loop_scenario_index(s, st0, h, 0, hod, t))];
   // ---- the curve from the p_min point on, cleared at that price ----
-  const double disp = loop_curve_and_clear<SP>(keys, S, pmin, s.price_taker != 0, lmp, curve + (size_t)g * (S + 1) * 2, count + g);
+  const int slots = s.curve_slots ? s.curve_slots : S + 1;      // (ABI 18: points per stored curve)
+  const double disp = loop_curve_and_clear<SP>(keys, slots - 1, pmin, s.price_taker != 0, lmp, curve + (size_t)g * slots * 2, count + g);
   dispatch[g] = disp;
   if (k < 0) {
     s.da_prices[(size_t)b * 24 + t] = lmp;
@@ -287,6 +344,12 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
 hipError_t launch_loop_market_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, int k, hipStream_t stream) {
   const long long rows = (long long)st.B * st.S;
   hipLaunchKernelGGL(loop_market_prepare_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, st, m, k);
+  return hipGetLastError();
+}
+
+hipError_t launch_loop_schedule_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, hipStream_t stream) {
+  const long long rows = (long long)st.B * st.S;
+  hipLaunchKernelGGL(loop_schedule_prepare_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, st, m);
   return hipGetLastError();
 }
 

@@ -108,10 +108,11 @@ class DspLoopState(C.Structure):
 EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_step", "dsp_get_dims",
                     "dsp_get_scaling", "dsp_destroy", "dsp_strerror", "dsp_last_hip_error", "dsp_version",
                     "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
-                    "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step", "dsp_loop_project")
+                    "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step", "dsp_loop_project",
+                    "dsp_loop_schedule_prepare")
 
 
-ABI_VERSION = 17         # DSP_VERSION of the include/dsp_hip.h these structures mirror
+ABI_VERSION = 18         # DSP_VERSION of the include/dsp_hip.h these structures mirror
 
 
 BID_MAX_HOURS, BID_MAX_SCENARIOS = 64, 16384
@@ -146,10 +147,10 @@ class DspMarketState(C.Structure):
 
 
 class DspLoopMarketModel(C.Structure):
-    """include/dsp_hip.h: dsp_loop_market_model (ABI 14) - a bidding LP of the descriptor loop's stochastic mode, B * S rows"""
+    """include/dsp_hip.h: dsp_loop_market_model (ABI 14; row_stride: ABI 18) - a bidding LP of the descriptor loop's stochastic mode, B * S rows"""
     _fields_ = [("c", C.c_void_p), ("lb", C.c_void_p), ("ub", C.c_void_p), ("base_c", C.c_void_p), ("x", C.c_void_p), ("c0", C.c_void_p),
                 ("status", C.c_void_p), ("flags", C.c_void_p),
-                ("n", C.c_int32), ("T", C.c_int32), ("n_state", C.c_int32), ("reserved", C.c_int32),
+                ("n", C.c_int32), ("T", C.c_int32), ("n_state", C.c_int32), ("row_stride", C.c_int32),
                 ("pt_cols", (C.c_int32 * 2) * MARKET_MAX_T), ("pt_coef", (C.c_double * 2) * MARKET_MAX_T), ("pt_const", C.c_double * MARKET_MAX_T),
                 ("pda_cols", C.c_int32 * MARKET_MAX_T), ("wind_cols", C.c_int32 * MARKET_MAX_T), ("state_init", C.c_int32 * 2),
                 ("wind_kw", C.c_double), ("c0_base", C.c_double), ("waste_per_kw", C.c_double),
@@ -157,13 +158,13 @@ class DspLoopMarketModel(C.Structure):
 
 
 class DspLoopMarketState(C.Structure):
-    """include/dsp_hip.h: dsp_loop_market_state (ABI 14)"""
+    """include/dsp_hip.h: dsp_loop_market_state (ABI 14; self_schedule, curve_slots: ABI 18)"""
     _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("D", C.c_int32), ("N", C.c_int32), ("backcast", C.c_int32), ("price_taker", C.c_int32),
                 ("start", C.c_void_p), ("hour", C.c_void_p),
                 ("da_series", C.c_void_p), ("rt_series", C.c_void_p), ("cf_series", C.c_void_p),
                 ("state", C.c_void_p), ("da_offer", C.c_void_p), ("da_prices", C.c_void_p),
                 ("bad", C.c_void_p), ("uncertified", C.c_void_p), ("p_min_cents", C.c_int64),
-                ("rt_history_lag_days", C.c_int32), ("reserved", C.c_int32)]
+                ("rt_history_lag_days", C.c_int32), ("self_schedule", C.c_int32), ("curve_slots", C.c_int32), ("reserved", C.c_int32)]
 
 
 class DspLoopParamState(C.Structure):
@@ -275,6 +276,8 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_market_prepare.restype = C.c_int
     lib.dsp_loop_market_clear.argtypes = [C.POINTER(DspLoopMarketState), C.POINTER(DspLoopMarketModel), C.POINTER(DspLoopModel), i32, i32, vp, vp, vp, vp]
     lib.dsp_loop_market_clear.restype = C.c_int
+    lib.dsp_loop_schedule_prepare.argtypes = [C.POINTER(DspLoopMarketState), C.POINTER(DspLoopMarketModel), vp]
+    lib.dsp_loop_schedule_prepare.restype = C.c_int
     lib.dsp_loop_param_step.argtypes = [C.POINTER(DspLoopParamState), C.POINTER(DspLoopModel), i32, i32, vp]
     lib.dsp_loop_param_step.restype = C.c_int
     lib.dsp_loop_project.argtypes = [C.POINTER(DspLoopProjectState), C.POINTER(DspLoopModel), i32, i32, vp]

@@ -47,7 +47,21 @@ day d - i, real-time scenario i day d - 1 - i (day d is not a whole day of real-
 the start of day d + 1 day_ahead() solves nothing and makes them current (activate_pending_DA_bids).  The hourly steps are unchanged,
 including what their backcast knows - OURS: a Prescient-fed Backcaster would hold tomorrow's day-ahead prices after the RUC.
 `_project_write` / `_project_hand_off` / `_activate` are the specification as tensor operations; csrc/dsp_project.hip (dsp_loop_project)
-is the same arithmetic in one kernel per step.  proj_state / proj_real / proj_obj keep the last chain."""
+is the same arithmetic in one kernel per step.  proj_state / proj_real / proj_obj keep the last chain.
+
+Self-scheduling (bidder="self_schedule"; the reference's run_double_loop_battery.py --participation_mode SelfSchedule, idaes'
+SelfScheduler; our host restatement is workflow/bidder.py::SelfScheduler on workflow/coupling.py::CoupledScenarioModel): the plant offers
+ONE schedule for all S price scenarios, day_ahead_power[s, t] == day_ahead_power[0, t].  The day-ahead step therefore solves ONE
+coupled LP per plant - B rows of S * n1 columns, block i of row b being what row b * S + i of the LP bidder is, plus (S - 1) T static
+coupling rows with bounds 0, 0 - with objective constant c0[b] = sum_i c0(b, i) added in the order of i.  The schedule of hour t is
+block 0's day_ahead_power; the bid is the one pair (schedule, 0 $/MWh) through the same curve and clearing rules - (p_min, 0) in front,
+integer cents where the reference rounds to 4 dp - so a price taker runs at its schedule when the price is >= 0 and at p_min otherwise.
+Inside the cleared day every day_ahead_power column of the hourly problem is fixed to the cleared offer in all scenarios, the coupling
+rows are vacuous and the coupled LP separates: the hourly step solves B real-time LPs, scenario 0 only, and bids (P_T[t], 0).  OURS:
+in the last T_rt - 1 hours of a day the look-ahead periods past midnight have a free day_ahead_power which the host would still tie
+across scenarios; this loop does not.  `_day_ahead_step_self_schedule` / `_hour_step_self_schedule` are the specification as tensor
+operations; csrc/dsp_market.hip (dsp_loop_schedule_prepare; dsp_loop_market_prepare / _clear on an S = 1 state with
+row_stride / self_schedule / curve_slots) is the same arithmetic, bit for bit."""
 from __future__ import annotations
 
 import numpy as np
@@ -112,6 +126,7 @@ class _Model:
         self.state_init = [int(c) for c in state_init]                    # columns fixed to the realised state
         self.pda_cols = self.track_rows = self.state_real = None          # day-ahead power columns (bidding models); dispatch rows, state after period 0 (trackers)
         self.kw_plant = self.c0_plant = None                              # per-plant sizes: wind kW [B, 1], objective constant [B] (set_plant_sizes)
+        self.per_plant = None                                             # rows per plant of a bidding model (None: the loop's S)
         self.wind = None
         if wind is not None:                                              # (columns, kW, curtailment cost per kW, template availability sum)
             cols, kw, per_kw, template_sum = wind
@@ -132,6 +147,46 @@ class _Model:
                             flags=torch.zeros(B, dtype=torch.int32, device=dev))
         else:
             self.opts, self.dlp, self.out = None, lp_backend(self.lp), None
+
+    def couple(self, model, S, B, dev, device_index, lp_backend):
+        """-> the COUPLED day-ahead model of a self-scheduling batch built on this one-row block model (of `model`, the day-ahead
+        template): B rows of the LP of CoupledScenarioModel(model, "non_anticipative") - S blocks of this LP side by side, (S - 1) T
+        coupling rows pda[s, t] - pda[0, t] with bounds 0, 0 written here, once, like the blocks' static bounds.  Afterwards THIS
+        model is the [B * S, n1] view of the coupled rows' c / lb / ub (block i of row b = its row b * S + i), which _set_rows writes;
+        its c0 [B * S] holds the scenario constants that the coupled c0 sums."""
+        import types
+        import torch
+        from .workflow.coupling import CoupledScenarioModel
+        shim = types.SimpleNamespace(lp=model.lp, n_scenario=S, HOUR=model.HOUR, pda_cols=model.pda_cols, block=model.block,
+                                     solver_hints=getattr(model, "solver_hints", None))
+        coupled = CoupledScenarioModel(shim, "non_anticipative")
+        cm = _Model.__new__(_Model)
+        cm.__dict__.update(self.__dict__)                                 # block data: base_c, PT, state / wind / day-ahead columns (block-relative)
+        cm.lp, cm.S, cm.n1 = coupled.lp, S, self.lp.n
+        if getattr(self.lp, "col_scale", None) is not None:               # the blocks keep the template's column scaling (DeviceLP reads it):
+            cm.lp.col_scale = np.tile(np.asarray(self.lp.col_scale, np.float64), S)      # wind + battery columns span 200 .. 1e9
+        n1, m1, Tc = self.lp.n, self.lp.m, (S - 1) * self.T
+        cm.c = self.base_c.repeat(S).repeat(B, 1)
+        cm.c0 = torch.zeros(B, dtype=torch.float64, device=dev)
+        cm.lb, cm.ub = self.lb[0].repeat(S).repeat(B, 1), self.ub[0].repeat(S).repeat(B, 1)
+        zeros = torch.zeros(Tc, dtype=torch.float64, device=dev)
+        cm.rlo = torch.cat([self.rlo[0, :m1].repeat(S), zeros]).repeat(B, 1)
+        cm.rhi = torch.cat([self.rhi[0, :m1].repeat(S), zeros]).repeat(B, 1)
+        if lp_backend is None:
+            cm.opts = default_options(**{"recertify_passes": 3, **coupled.solver_hints})      # (a T > 16 model's options)
+            from .hip_solver import DspOptions
+            cm.opts_warm, cm.opts_first = DspOptions.from_buffer_copy(cm.opts), DspOptions.from_buffer_copy(cm.opts)
+            cm.dlp = DeviceLP(cm.lp, device_index, cm.opts)
+            n, m = cm.lp.n, max(cm.lp.m, 1)
+            cm.out = dict(x=torch.zeros((B, n), dtype=torch.float64, device=dev), y=torch.zeros((B, m), dtype=torch.float64, device=dev),
+                          obj=torch.zeros(B, dtype=torch.float64, device=dev), status=torch.zeros(B, dtype=torch.int32, device=dev),
+                          iters=torch.zeros(B, dtype=torch.int32, device=dev), jumps=torch.zeros(B, dtype=torch.int32, device=dev),
+                          flags=torch.zeros(B, dtype=torch.int32, device=dev))
+        else:
+            cm.opts, cm.dlp, cm.out = None, lp_backend(cm.lp), None
+        self.c, self.lb, self.ub = (v.view(B * S, n1) for v in (cm.c, cm.lb, cm.ub))
+        self.c0 = torch.zeros(B * S, dtype=torch.float64, device=dev)
+        return cm
 
     def power_output(self, x):
         return x @ self.PT.T + self.PT_const                              # [B, T] MW
@@ -203,7 +258,7 @@ def _fill_descriptor(w, m, n_state):
     carries them (None: the pointers stay NULL, the kernels read the scalars).  Entries past the horizon are -1 / 0."""
     w.c, w.lb, w.ub, w.base_c, w.x, w.c0 = (t.data_ptr() for t in (m.c, m.lb, m.ub, m.base_c, m.out["x"], m.c0))
     w.status, w.flags = m.out["status"].data_ptr(), m.out["flags"].data_ptr()
-    w.n, w.T, w.n_state = m.lp.n, m.T, n_state
+    w.n, w.T, w.n_state = getattr(m, "n1", m.lp.n), m.T, n_state      # (a coupled model is described by ONE of its blocks)
     cols, coef = m.terms()
     PTc = m.PT_const.cpu().numpy()
     pda = m.pda_cols.cpu().tolist() if m.pda_cols is not None else []
@@ -355,7 +410,17 @@ class BatchedDoubleLoop:
         H, 1 <= H <= 23: the reference's timeline (module docstring, "Bidding at the RUC hour").  Explicit, no default of ours: the
         reference's drivers leave Prescient's ruc_execution_hour at Prescient's own default, 16.  Refused (ValueError): a value that
         is not an integer of 1 .. 23, bidder="parametrized" (no bidding LP and no state in the bid: nothing to project), and
-        forecaster="backcast" with 24 (max_historical_days + 1) hours more than the series holds."""
+        forecaster="backcast" with 24 (max_historical_days + 1) hours more than the series holds.
+        bidder="self_schedule" (all three flowsheets; n_price_scenarios = S, forecaster, max_historical_days, market, plant_windows and
+        the horizons with the stochastic mode's meaning and validation; S = 1 on the perfect forecaster works and has no coupling rows):
+        the reference's SelfSchedule participation mode (module docstring, "Self-scheduling").  ONE day-ahead schedule per plant for all
+        S price scenarios, from one coupled LP per plant (self.da: B rows of S * n1 columns; self.da_block is its [B * S, n1] view);
+        the schedule is offered at cost 0, so da_curve / da_count keep the stochastic mode's shapes (S + 1 slots) with one or two points
+        used, prices 0, p_min in front; powers are integer cents where the reference rounds to 4 dp.  The hourly steps solve B real-time
+        LPs on scenario 0.  results() has the stochastic mode's keys.  The hourly steps replay from graphs; so does the day-ahead step
+        where the coupled LP stays in the fused kernels (nuclear, wind + PEM) - a coupled LP that the solver streams (wind + battery)
+        is solved from the host and its step stays eager (day_ahead()).  Refused (ValueError): ruc_hour, per-plant sizes (wind_mw,
+        battery_mw, battery_mwh), bid_price / storage_mw."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
@@ -367,9 +432,16 @@ class BatchedDoubleLoop:
             raise ValueError(f"forecaster='backcast' needs 1 <= n_price_scenarios <= min(16, max_historical_days), not {S} (max_historical_days={D})")
         if forecaster == "perfect" and S != 1:
             raise ValueError("forecaster='perfect' knows one price scenario: n_price_scenarios must be 1")
-        if bidder not in ("lp", "parametrized"):
-            raise ValueError(f"bidder is 'lp' or 'parametrized', not {bidder!r}")
+        if bidder not in ("lp", "parametrized", "self_schedule"):
+            raise ValueError(f"bidder is 'lp', 'parametrized' or 'self_schedule', not {bidder!r}")
         self.parametrized = bidder == "parametrized"
+        self.self_schedule = bidder == "self_schedule"
+        if self.self_schedule:
+            if ruc_hour is not None:
+                raise ValueError("ruc_hour belongs to bidder='lp': a self-schedule made at the RUC hour on a projected state is a follow-up (DESIGN 9)")
+            sized = [k for k, v in (("wind_mw", wind_mw), ("battery_mw", battery_mw), ("battery_mwh", battery_mwh)) if v is not None]
+            if sized:
+                raise ValueError(f"{', '.join(sized)}: per-plant sizes belong to bidder='lp' (a self-scheduling batch of different plants is a follow-up, DESIGN 9)")
         if self.parametrized:
             if flowsheet not in ("wind_pem", "wind_battery"):
                 raise ValueError(f"bidder='parametrized' is the wind + PEM / wind + battery bidders' rule: not for {flowsheet!r}")
@@ -400,8 +472,8 @@ class BatchedDoubleLoop:
                 raise ValueError(f"plant_windows is an int array of length {B}")
             plant_windows = plant_windows.astype(np.int64)
         self.forecaster, self.market = forecaster, market
-        self.stochastic = forecaster != "perfect" or market != "stub" or self.parametrized
-        rows = 1 if self.parametrized else B * S                           # rows of the bidding batches (plant b, scenario i: row b * S + i; no bidding LP is solved in parametrized mode: one template row)
+        self.stochastic = forecaster != "perfect" or market != "stub" or self.parametrized or self.self_schedule
+        rows = 1 if self.parametrized else B if self.self_schedule else B * S                           # rows of the bidding batches (plant b, scenario i: row b * S + i; no bidding LP is solved in parametrized mode: one template row)
         self.dev = dev = torch.device("cuda", device) if lp_backend is None else torch.device("cpu")
         # one template for the batch, built at its largest sizes (None: the default plant's, untouched)
         bidder, da_model, rt_model, tracker, d = _templates(flowsheet, day_ahead_horizon, tracking_horizon,
@@ -435,7 +507,14 @@ class BatchedDoubleLoop:
             cols = [p["wind"].index for p in f["periods"]]
             return cols, f["wind_kw"], d["per_kw"], f["wind_kw"] * float(np.sum(cf_s[:len(cols)]))
         mk = lambda model, nb, solved=True: _Model(model, fam, nb, dev, device, power, d["init"](model.block), wind_of(model), lp_backend, solved)
-        self.da, self.rt, self.tr = mk(da_model, rows, not self.parametrized), mk(rt_model, rows, not self.parametrized), mk(tr_model, B)
+        if self.self_schedule:                        # ONE coupled day-ahead LP per plant; the hourly LPs are scenario 0's (module docstring)
+            self.da_block = mk(da_model, 1, False)
+            self.da_block.pda_cols = idx(da_model.pda_cols)
+            self.da = self.da_block.couple(da_model, S, B, dev, device, lp_backend)
+            self.rt, self.tr = mk(rt_model, B), mk(tr_model, B)
+            self.rt.per_plant = 1
+        else:
+            self.da, self.rt, self.tr = mk(da_model, rows, not self.parametrized), mk(rt_model, rows, not self.parametrized), mk(tr_model, B)
         self.da.pda_cols, self.rt.pda_cols = idx(da_model.pda_cols), idx(rt_model.pda_cols)
         self.tr.track_rows = idx([tr_model.block.kept_row_index(r) for r in tr_model.tracking_rows])
         self.tr.state_real = d["real"](tr_model.block)
@@ -454,8 +533,9 @@ class BatchedDoubleLoop:
         self.use_graphs = bool(use_graphs) and lp_backend is None
         self.simplex_warm = bool(simplex_warm) and lp_backend is None
         self._graphs, self._warm = {}, False
+        self._da_capturable = None                    # self-schedule: may the coupled day-ahead step be a graph node (day_ahead)
         self.use_fused = bool(use_fused) and lp_backend is None and self.rt.T <= 16 and self.tr.T <= 16 and len(self.scale) <= 2
-        self.exact = self.sized or self.parametrized    # these state phase 2 of dsp_loop_update exactly, sums included (_hand_off)
+        self.exact = self.sized or self.parametrized or self.self_schedule    # these state phase 2 of dsp_loop_update exactly, sums included (_hand_off)
         if self.exact:
             self.tr.set_first_period_terms(dev)
         if self.sized:
@@ -464,7 +544,7 @@ class BatchedDoubleLoop:
             self._parametrized_setup(d, bid_price, storage_mw, tr_model, fam)
         elif self.stochastic:
             self.p_min_cents = int(round(float(bidder.bidding_model_object.model_data.p_min) * 100.0))     # Bidder._assemble_bids: p_min of the generator
-            for m in (self.da, self.rt):
+            for m in ((self.da_block if self.self_schedule else self.da), self.rt):
                 cols = m.set_terms(dev)
                 if set(cols[cols >= 0].tolist()) & set(m.pda_cols.cpu().tolist()):
                     raise ValueError("a column is both a term of the power output and day_ahead_power: the prices' objective entries would collide")
@@ -645,6 +725,15 @@ class BatchedDoubleLoop:
         mk.p_min_cents = self.p_min_cents
         self._mk_state = mk
         self._mk_da, self._mk_rt = (_fill_descriptor(DspLoopMarketModel(), m, len(self.scale)) for m in (self.da, self.rt))
+        if self.self_schedule:
+            # the coupled rows: one block described, blocks S * n1 apart; c0 / status / flags one entry per plant.  Everything but the
+            # day-ahead fan-out runs on an S = 1 state (scenario 0 = the most recent backcast day): pairs priced at 0, curves in the
+            # loop's S + 1 slots
+            self._mk_da.row_stride = self.da.lp.n
+            self._mk_sched = mk
+            one = DspLoopMarketState.from_buffer_copy(mk)
+            one.S, one.self_schedule, one.curve_slots = 1, 1, self.S + 1
+            self._mk_state = one
         if self.ruc_hour is not None:                  # the bid made at the RUC hour: its own clock, the projected state, the pending buffers
             bid = DspLoopMarketState.from_buffer_copy(mk)
             bid.hour, bid.state = self.bid_hour_t.data_ptr(), self.proj_state[-1].data_ptr() if len(self.scale) else None
@@ -783,9 +872,10 @@ class BatchedDoubleLoop:
         pos = (24 * (D - 1 - i) + hod + t) % (24 * D)
         return series[(self.start[:, None, None] + 24 * (d - D) + pos[None]) % self.N]
 
-    def _rows(self, v):
-        """per-plant values [B, ...] -> per-row [B * S, ...] (a plant's S rows are adjacent)"""
-        return v if self.S == 1 else v.repeat_interleave(self.S, dim=0)
+    def _rows(self, v, m=None):
+        """per-plant values [B, ...] -> per-row [B * S, ...] (a plant's S rows are adjacent; m.per_plant: that model's rows per plant)"""
+        per = self.S if m is None or m.per_plant is None else m.per_plant
+        return v if per == 1 else v.repeat_interleave(per, dim=0)
 
     def _avail(self, m, offset=0):
         """wind availability of the window [B, T] and its sum accumulated in the order of t (the kernels' order: bit-identical constants)"""
@@ -805,17 +895,17 @@ class BatchedDoubleLoop:
             psum = rt[:, 0] * m.PT_const[0]
             for t in range(1, m.T):
                 psum = psum + rt[:, t] * m.PT_const[t]
-            c0 = (m.base_c0_t if m.c0_plant is None else self._rows(m.c0_plant)) - psum
+            c0 = (m.base_c0_t if m.c0_plant is None else self._rows(m.c0_plant, m)) - psum
         else:
-            c0 = m.base_c0_t.expand(rt.shape[0]) if m.c0_plant is None else self._rows(m.c0_plant)
+            c0 = m.base_c0_t.expand(rt.shape[0]) if m.c0_plant is None else self._rows(m.c0_plant, m)
         for j, col in enumerate(m.state_init):
-            v = self._rows(self._st[:, j])
+            v = self._rows(self._st[:, j], m)
             m.lb[:, col] = v
             m.ub[:, col] = v
         if m.wind is not None:
             cols, avail, waste = self._avail(m)
-            m.ub[:, cols] = self._rows(avail)
-            c0 = c0 + self._rows(waste)
+            m.ub[:, cols] = self._rows(avail, m)
+            c0 = c0 + self._rows(waste, m)
         m.c0.copy_(c0)
 
     def _set_tracker(self):
@@ -855,6 +945,9 @@ class BatchedDoubleLoop:
     def _store_curves(self, curve, cnt, U, M, count):
         import torch
         B, Tc, slots, _ = curve.shape
+        if U.shape[0] < slots:                        # (a self-schedule's one-pair curve in the loop's S + 1 slots: the rest stays 0)
+            pad = torch.zeros((slots - U.shape[0], U.shape[1]), dtype=U.dtype, device=U.device)
+            U, M = torch.cat([U, pad]), torch.cat([M, pad])
         curve.copy_(torch.stack([U.t().reshape(B, Tc, slots), M.t().reshape(B, Tc, slots)], dim=3))
         cnt.copy_(count.reshape(B, Tc))
 
@@ -936,6 +1029,86 @@ class BatchedDoubleLoop:
         out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
         self._check(out)
         self._hand_off(out["x"], rt0[:, 0], k, exact=self.exact)
+
+    # -- self-scheduling: one coupled day-ahead LP per plant, the schedule offered at cost 0 (module docstring) ----------------------------
+    def _schedule_curves(self, power, status):
+        """power [B, Tc] MW, status [B] -> the curves of the ONE pair (power, 0 $/MWh) per plant and period (plant_curves with S = 1)"""
+        import torch
+        return self._curves(power[:, None, :], torch.zeros_like(power)[:, None, :], status)
+
+    def _day_ahead_step_self_schedule(self):
+        """B coupled day-ahead LPs: block i of row b on scenario i's backcast prices, plant b's state and wind, day_ahead_power free
+        (what _set_rows gives row b * S + i), tied by the static coupling rows; c0[b] = sum_i c0(b, i) in the order of i.  The
+        schedule - block 0's day_ahead_power - is offered at cost 0 and cleared at the realised day-ahead price."""
+        import ctypes as C
+        import torch
+        m, blk, B, S = self.da, self.da_block, self.B, self.S
+        if self.use_fused:
+            rc = self._lib.dsp_loop_schedule_prepare(C.byref(self._mk_sched), C.byref(self._mk_da), C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"dsp_loop_schedule_prepare failed ({rc})")
+        else:
+            da = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T)
+            rt = self._forecast(self.rt_series, m.T, 0).expand(B, S, m.T)
+            self._set_rows(blk, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
+            blk.lb.index_fill_(1, m.pda_cols, 0.0)
+            blk.ub.index_fill_(1, m.pda_cols, float("inf"))
+            each = blk.c0.view(B, S)
+            total = each[:, 0]
+            for i in range(1, S):
+                total = total + each[:, i]
+            m.c0.copy_(total)
+        out = m.solve(B)
+        if self.use_fused:
+            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_da), None, -1, 24, C.c_void_p(self.da_offer.data_ptr()),
+                         C.c_void_p(self.da_curve.data_ptr()), C.c_void_p(self.da_count.data_ptr()))
+        else:
+            self._check(out)
+            U, M, count = self._schedule_curves(out["x"][:, m.pda_cols[:24]], out["status"])      # (block 0: the block-relative columns)
+            realised = self._window(self.da_series, 24)
+            self.da_offer.copy_(self._clear(U, M, count, realised))
+            self.da_prices.copy_(realised)
+            self._store_curves(self.da_curve, self.da_count, U, M, count)
+        self._account_day_ahead()
+
+    def _hour_step_self_schedule(self, k):
+        """Hour k of the day: B real-time LPs on scenario 0 (the most recent backcast day; realised day-ahead prices and the cleared
+        day_ahead_power inside the cleared day - where the coupled hourly problem separates), the one-pair curve (P_T[t], 0) per
+        tracked period cleared at the realised price (t = 0) / scenario 0's forecast (t >= 1); tracking, hand-off, revenue, clock as
+        _hour_step_stochastic."""
+        import ctypes as C
+        import torch
+        m, tr, B = self.rt, self.tr, self.B
+        hour = k if self.simplex_warm else None
+        if self.use_fused:
+            self._market(self._lib.dsp_loop_market_prepare, C.byref(self._mk_rt), k)
+            m.solve(B, hour=hour)
+            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_rt), C.byref(self._loop_tr), k, tr.T, C.c_void_p(self.rt_dispatch.data_ptr()),
+                         C.c_void_p(self.rt_curve.data_ptr()), C.c_void_p(self.rt_count.data_ptr()))
+            tr.solve(B, hour=hour)
+            self._fused(2, k)
+            return
+        rt_f = self._forecast(self.rt_series, m.T, k)[:, 0].expand(B, m.T)
+        da_f = self._forecast(self.da_series, m.T, k)[:, 0].expand(B, m.T).clone()
+        known = min(m.T, 24 - k)                                          # hours of the horizon inside the cleared day
+        da_f[:, :known] = self.da_prices[:, k:k + known]
+        self._set_rows(m, da_f, rt_f)
+        m.lb.index_fill_(1, m.pda_cols, 0.0)
+        m.ub.index_fill_(1, m.pda_cols, float("inf"))
+        m.lb[:, m.pda_cols[:known]] = self.da_offer[:, k:k + known]
+        m.ub[:, m.pda_cols[:known]] = self.da_offer[:, k:k + known]
+        out = m.solve(B, hour=hour) if m.opts is not None else m.solve(B)
+        self._check(out)
+        x, Tc = out["x"], tr.T
+        power = (x[:, m.pt_a[:Tc]] * m.pt_ca[:Tc] + x[:, m.pt_b[:Tc]] * m.pt_cb[:Tc]) + m.PT_const[:Tc]      # two-term elementwise form, not a matmul
+        U, M, count = self._schedule_curves(power, out["status"])
+        rt0 = self._window(self.rt_series, 1)
+        self.rt_dispatch.copy_(self._clear(U, M, count, torch.cat([rt0, rt_f[:, 1:Tc]], dim=1)))
+        self._store_curves(self.rt_curve, self.rt_count, U, M, count)
+        self._set_tracker()
+        out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
+        self._check(out)
+        self._hand_off(out["x"], rt0[:, 0], k, exact=True)
 
     # -- parametrized mode: two-tier closed-form curves (workflow/parametrized_bidder.py), no bidding LP ---------------------------------
     def _param_curves(self, cf):
@@ -1114,6 +1287,20 @@ class BatchedDoubleLoop:
         if self.parametrized:
             self._run("da", self._day_ahead_step_parametrized)
             return self.da_offer.clone()
+        if self.self_schedule:
+            # A coupled LP beyond the register / LDS-resident kernels (wind + battery: 582 columns, 408 rows at 24 h) runs in the solver's
+            # HBM-resident streaming form, which is driven from the host (it polls the scenarios' completion between check periods): it
+            # cannot be a node of a captured graph, and the step stays eager, once per simulated day.  A coupled LP that stays in the
+            # fused kernels (nuclear, wind + PEM at S = 3) is captured and replayed like the stochastic mode's.  Which of the two a handle
+            # is, the first - eager - day's solve reports (dsp_stats::streaming).
+            if self._da_capturable is None and self._warm:
+                self._da_capturable = self.use_graphs and not self.da.dlp.last_stats.streaming
+            if self._da_capturable:
+                self._run("da", self._day_ahead_step_self_schedule)
+            else:
+                self._day_ahead_step_self_schedule()
+            self.solves += self.B
+            return self.da_offer.clone()
         self._run("da", self._day_ahead_step_stochastic if self.stochastic else self._day_ahead_step)
         self.solves += self.B * self.S
         return self.da_offer.clone()
@@ -1123,6 +1310,9 @@ class BatchedDoubleLoop:
         if self.parametrized:
             self._run(k, lambda: self._hour_step_parametrized(k))
             self.solves += self.B
+        elif self.self_schedule:
+            self._run(k, lambda: self._hour_step_self_schedule(k))
+            self.solves += 2 * self.B
         else:
             step = (lambda: self._hour_step_stochastic(k)) if self.stochastic else (lambda: self._hour_step(k))
             if k == self.ruc_hour:

@@ -24,6 +24,9 @@
  * dsp_loop_project runs the coordinator's projection tracker (bid_into_DAM: the rest of today's cleared day-ahead dispatch tracked to
  * midnight, free dispatch rows past it) and makes the bid computed at the RUC hour current at midnight;
  * dsp_loop_market_state::rt_history_lag_days ages the real-time backcast of that bid by the day that is not complete yet.
+ * ABI 18 adds the self-scheduling plant: dsp_loop_schedule_prepare writes ONE coupled day-ahead LP per plant (S scenario blocks side by
+ * side in a row, tied by static non-anticipativity rows) and dsp_loop_market_clear reads block 0 of such a row
+ * (dsp_loop_market_model::row_stride) and prices the schedule at 0 (dsp_loop_market_state::self_schedule, curve_slots).
  */
 #ifndef DSP_HIP_H
 #define DSP_HIP_H
@@ -36,7 +39,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 17
+#define DSP_VERSION 18
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -522,7 +525,12 @@ typedef struct dsp_loop_market_model {
   const double *x;                     /* [B * S][n] solution of its last solve                                                   */
   double *c0;                          /* [B * S] objective constant of every row                                                 */
   const int32_t *status, *flags;       /* [B * S] outputs of its last solve (flags may be NULL)                                   */
-  int32_t n, T, n_state, reserved;     /* columns, horizon (T <= DSP_MARKET_MAX_T), state columns (<= 2)                          */
+  int32_t n, T, n_state;               /* columns, horizon (T <= DSP_MARKET_MAX_T), state columns (<= 2)                          */
+  int32_t row_stride;                  /* (ABI 18; was reserved) doubles between two rows of c / lb / ub / x; 0 = n, as before, bit for
+                                          bit.  A coupled self-schedule LP keeps its S scenario blocks of n columns side by side in
+                                          one row: row_stride >= S * n, `n` and every column index describe ONE block.  Read by
+                                          dsp_loop_schedule_prepare (all blocks) and dsp_loop_market_clear (x of block 0);
+                                          dsp_loop_market_prepare takes 0 or n only.  status / flags / c0 stay one entry per row    */
   int32_t pt_cols[DSP_MARKET_MAX_T][2];/* -1 = no such term                                                                       */
   double  pt_coef[DSP_MARKET_MAX_T][2];
   double  pt_const[DSP_MARKET_MAX_T];
@@ -549,6 +557,12 @@ typedef struct dsp_loop_market_state {
   int32_t rt_history_lag_days;         /* (ABI 17) backcast only: the REAL-TIME scenarios come from a history that ends this many
                                           days earlier (0: as before, bit for bit; 1: a bid made at the RUC hour for the next day,
                                           when today is not a whole day of real-time prices yet).  >= 0, 24 (D + lag) <= N          */
+  int32_t self_schedule;               /* (ABI 18; was reserved) dsp_loop_market_clear: 0 = as before, bit for bit; 1 = every pair is
+                                          priced at 0 cents whatever the forecast (SelfScheduler._assemble_bids offers its schedule
+                                          at cost 0): the curve is (p_min, 0), (schedule, 0)                                       */
+  int32_t curve_slots;                 /* (ABI 18) points per stored curve in `curve`: 0 = S + 1, as before; otherwise
+                                          S + 1 <= curve_slots <= DSP_MARKET_MAX_S + 1 (a loop that clears with an S = 1 state into
+                                          buffers sized for its S price scenarios); unused slots are written 0                     */
   int32_t reserved;
 } dsp_loop_market_state;
 
@@ -565,6 +579,10 @@ int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_mark
  * (the tracking model of B rows, tr->T == T) the lanes also write the tracker's LP of this hour: dispatch rows = dispatch[t] -
  * tr->pt_const[t], state columns, wind availability and c0 = c0_base + waste_per_kw * sum_t availability (as phase 1 of dsp_loop_update).
  * Refusals as dsp_loop_market_prepare, and for a dispatch row of `tr` outside [0, tr->m).
+ * ABI 18: x of row r is read at m->x + r * (row_stride ? row_stride : n) - with an S = 1 state and the descriptor of
+ * dsp_loop_schedule_prepare that is block 0 of plant r's coupled row, the schedule; st->self_schedule prices every pair at 0 cents and
+ * st->curve_slots sets the stride of `curve`.  All three are kernel arguments, uniform over the grid; 0 / 0 / 0 is ABI 17 bit for bit.
+ * Refused: 0 < row_stride < n, curve_slots outside {0} and S + 1 .. DSP_MARKET_MAX_S + 1, self_schedule outside 0 / 1.
  * Per-plant sizes (ABI 16; BatchedDoubleLoop(wind_mw=, battery_mw=, battery_mwh=)): with wind_kw_plant / c0_base_plant the lanes read
  * plant b's wind capacity and objective constant at the very sites that read the scalars - same intrinsics, same order, so that kernel
  * = tensor form = graph replay stays bit for bit.  A size is never a matrix coefficient of these flowsheets: the battery's power and
@@ -573,6 +591,22 @@ int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_mark
  * (dsp_loop_update: `rt` and `tr`) that do not carry them together. */
 int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market_model *m, const dsp_loop_model *tr, int32_t k, int32_t T,
                           double *dispatch, int32_t *curve, int32_t *count, void *hipStream);
+
+/* The day-ahead LP of a SELF-SCHEDULING plant (ABI 18; dispatches_amd/rolling_flowsheets.py: BatchedDoubleLoop with
+ * bidder="self_schedule").  The reference's run_double_loop_battery.py --participation_mode SelfSchedule bids with idaes' SelfScheduler,
+ * which ties the S price scenarios of the day-ahead problem to ONE schedule, day_ahead_power[s, t] == day_ahead_power[0, t]
+ * (workflow/coupling.py::CoupledScenarioModel, "non_anticipative").  That is one LP per plant: S blocks of the scenario LP side by side in
+ * a row of m->row_stride >= S * m->n doubles, plus (S - 1) T static coupling rows that the caller writes once (bounds 0, 0).
+ * `m` describes ONE block: n, pt_cols, pda_cols, wind_cols and state_init are relative to the block; c / lb / ub are [B][row_stride],
+ * c0 is [B].  One lane per (plant b, scenario i) writes block i of row b exactly as dsp_loop_market_prepare with k = -1 writes row
+ * b * S + i: objective on scenario i's backcast prices (same index rule, products rounded on their own), state columns, wind bounds,
+ * day_ahead_power free in every period.  The lane of scenario 0 also writes the row's constant
+ *   c0[b] = sum_i ((c0_base - sum_t rt_i[t] * pt_const[t]) + waste_per_kw * sum_t availability[t]),   accumulated in the order of i
+ * (inner sums in the order of t): one lane, no atomics - bit-identical to the tensor form.
+ * DSP_ERR_INVALID, nothing launched and nothing written, for: what dsp_loop_market_prepare refuses (a NULL buffer that is used; S, D, T
+ * or n_state out of range; a used column index outside the block [0, n); n_state > 0 with a NULL state; wind columns with a NULL
+ * cf_series); row_stride < S * n; per-plant size pointers (a self-scheduling batch has one plant size). */
+int dsp_loop_schedule_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, void *hipStream);
 
 /* Parametrized two-tier bidding in the descriptor loop (ABI 15; dispatches_amd/rolling_flowsheets.py: BatchedDoubleLoop with
  * bidder="parametrized").  The reference's wind + PEM and wind + battery sweeps bid without an LP (PEM_parametrized_bidder.py:50-122,

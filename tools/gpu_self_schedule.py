@@ -1,0 +1,102 @@
+"""Time the self-scheduling mode of the descriptor double loop (dispatches_amd/rolling_flowsheets.py::BatchedDoubleLoop with
+bidder="self_schedule") against its neighbour: the LP bidder (bidder="lp") at the same B and S - S independent day-ahead LPs per plant
+there, ONE coupled LP per plant here; S hourly bidding LPs per plant there, one here.
+
+    python tools/gpu_self_schedule.py [--out profiles/self_schedule_timings.jsonl] [--days 30] [--rounds 2]
+
+Cases: wind + battery at 256 and 2048 plants, nuclear at 256, S = 3, day-ahead horizon 24.  Every measurement is a child process of its
+own under `timeout`, self-schedule and LP bidder alternating, `--rounds` rounds (the process order of tools/gpu_flowsheet_stochastic.py);
+the driver stops at the first child that fails (no retries) and appends one JSON line per measurement to --out.  A self-schedule line
+also records how the coupled day-ahead solve ran: dsp_stats::streaming / stream_form of the last day's solve, the distribution of its
+iteration counts, and the share of optimal / uncertified rows.  The numbers are recorded, not gated.
+
+    python tools/gpu_self_schedule.py --one wind_battery --plants 256 --bidder self_schedule      (one measurement: prints its JSON line)
+
+Warm-up days first (handles, kernels, the hipGraphs of a day), then reset() and `--days` timed days from hour 0."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CASES = (("wind_battery", 256, 420), ("wind_battery", 2048, 560), ("nuclear", 256, 420))     # flowsheet, plants, seconds allowed per measurement
+
+
+def one(a):
+    import numpy as np
+    import torch
+    import __graft_entry__ as g
+    g.build()
+    from dispatches_amd.hip_solver import load_library
+    from dispatches_amd.rolling_flowsheets import BatchedDoubleLoop
+    loop = BatchedDoubleLoop(a.one, a.plants, device=0, bidder=a.bidder, n_price_scenarios=a.scenarios, forecaster="backcast",
+                             max_historical_days=a.history_days, market="price_taker", day_ahead_horizon=a.day_ahead_horizon)
+    for _ in range(a.warmup):
+        loop.run_day()
+    torch.cuda.synchronize()
+    loop.reset()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.days):
+        loop.run_day()
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    res, ok = loop.results()
+    line = dict(tool="gpu_self_schedule", flowsheet=a.one, B=a.plants, S=a.scenarios, bidder=a.bidder, day_ahead_horizon=a.day_ahead_horizon,
+                days=a.days, seconds=seconds, ms_per_simulated_day=1e3 * seconds / a.days, solves=loop.solves, all_optimal=bool(ok),
+                uncertified=int(loop.uncertified.item()), revenue_sum=float(res["obj"].sum().item()),
+                offered_mwh=float(res["offered_mwh"].sum().item()), cleared_mwh=float(res["da_energy_mwh"].sum().item()),
+                day_ahead_columns=loop.da.lp.n, day_ahead_rows=loop.da.lp.m, source_hash=load_library().dsp_source_hash().decode())
+    # the last day's day-ahead solve (its outputs are still in place: the hourly models have their own)
+    stats = loop.da.dlp.last_stats
+    iters = loop.da.out["iters"].cpu().numpy()
+    status, flags = loop.da.out["status"].cpu().numpy(), loop.da.out["flags"].cpu().numpy()
+    line.update(day_ahead_streaming=int(stats.streaming), day_ahead_stream_form=int(stats.stream_form),
+                day_ahead_iterations=dict(min=int(iters.min()), median=float(np.median(iters)), p90=float(np.percentile(iters, 90)), max=int(iters.max())),
+                day_ahead_optimal_share=float((status == 0).mean()), day_ahead_uncertified_share=float(((flags & 1) != 0).mean()))
+    print(json.dumps(line), flush=True)
+    return 0           # (a run with rows that are not optimal is a result here: all_optimal and the shares are in the line)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "self_schedule_timings.jsonl"))
+    ap.add_argument("--days", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--history-days", type=int, default=10)
+    ap.add_argument("--day-ahead-horizon", type=int, default=24)
+    ap.add_argument("--cases", default="wind_battery:256,wind_battery:2048,nuclear:256")
+    ap.add_argument("--one", default=None, help="flowsheet of ONE measurement in this process (with --plants / --bidder)")
+    ap.add_argument("--plants", type=int, default=256)
+    ap.add_argument("--scenarios", type=int, default=3)
+    ap.add_argument("--bidder", default="self_schedule", choices=("self_schedule", "lp"))
+    a = ap.parse_args()
+    if a.one:
+        return one(a)
+    for flowsheet, plants, limit in CASES:
+        if f"{flowsheet}:{plants}" not in a.cases.split(","):
+            continue
+        for r in range(a.rounds):
+            for bidder in ("self_schedule", "lp"):
+                cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--one", flowsheet, "--plants", str(plants),
+                       "--bidder", bidder, "--scenarios", str(a.scenarios), "--days", str(a.days), "--warmup", str(a.warmup),
+                       "--history-days", str(a.history_days), "--day-ahead-horizon", str(a.day_ahead_horizon)]
+                p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+                lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+                if p.returncode != 0 or not lines:
+                    print(f"{flowsheet} {plants} {bidder} round {r + 1}: exit status {p.returncode} - stopping here", flush=True)
+                    return p.returncode or 1
+                line = dict(run=f"{flowsheet}{plants}_{bidder}_{r + 1}", **json.loads(lines[-1]))
+                print(json.dumps(line), flush=True)
+                with open(a.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
