@@ -51,6 +51,9 @@ struct dsp_handle {
   Geometry geo[2];
   int matreg = 0;                 // register-resident-matrix kernel available for this shape
   int matreg_qp = 0;              // ... and its QP instantiation
+  // The LP first pass is a three-wave kernel (168 VGPRs) and its follow-up passes run the generic kernel's light instantiation in
+  // blocks of one wave with this much LDS (0: today's geometry - blocks of up to 4 waves of the 256-VGPR kernel)
+  size_t light_lds = 0;
   // run-time compiled specialisation (dsp_rtc.hpp) for shapes without an ahead-of-time one: [0] LP, [1] QP instantiation
   RtcKernel rtc[2];
   int rtc_state[2] = {0, 0};      // 0 = not applicable, 1 = loaded, -1 = to be compiled at the first solve that needs it
@@ -748,6 +751,14 @@ int dsp_create(const dsp_lp_desc *d, int device, const dsp_options *opt, dsp_han
   h->queue = (int *)q;
   if (hipMemset(q, 0, sizeof(int) * kQueueRing * kQueueStride) != hipSuccess) { dsp_destroy(h); return DSP_ERR_HIP; }
   if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) { dsp_destroy(h); return DSP_ERR_HIP; }
+  if (h->matreg && h->rtc_state[0] != 1) {
+    // follow-up passes behind a three-wave first pass: the runtime's occupancy answer for a one-wave block of the light kernel with the
+    // LDS matrix decides (on the 24-h LP about 27 KB, beside eleven first-pass blocks of about 8 KB in the CU's 160 KB); 0 = as before
+    SolveArgs first{};
+    first.P = h->P; first.matreg = 1; first.qp = 0;
+    const size_t l = lds_bytes(h->P, 1, 0, h->cpl, h->rpl);
+    if (l <= (size_t)h->lds_limit && light_followup_blocks(h->cpl, h->rpl, first, l) > 0) h->light_lds = l;
+  }
   *out = h;
   return DSP_OK;
 }
@@ -871,13 +882,19 @@ int dsp_solve(dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, dsp
   // geometry of the certificate pass (below), fixed BEFORE the first pass runs: a register-resident kernel may only leave scenarios
   // DSP_STATUS_SUSPECT if the generic kernel that takes them over can be launched (it always can for an LP of the fused path - it is
   // the fallback of every shape -; if not, the first pass keeps every scenario and the certificates are off for this call)
+  // Behind a three-wave first pass (168 VGPRs a wave, 504 of a SIMD's 512) the follow-up passes - certificates and re-certification -
+  // are one-wave blocks of the light instantiation: each fits the registers ONE leaving first-pass wave sets free.  A 256-VGPR wave
+  // needs two of a SIMD's three gone with none dispatched in between, a block of four that on one CU four times over - which happens
+  // only while the GPU drains, and the packets queued behind the pass on its hardware queue wait with it (profiles/HISTORY.md, r82a).
+  const bool light = a.matreg && !qp && h->rtc_state[0] != 1 && h->light_lds > 0;
   int cert_wpb = 0;
   size_t cert_lds = 0;
   if (a.matreg && a.opt.eps_infeasible > 0.0) {
-    for (int wpb = 1; wpb <= 4; ++wpb) {              // a few waves per block share the LDS matrix; the pass is rare, not tuned
+    for (int wpb = 1; wpb <= 4 && !light; ++wpb) {    // a few waves per block share the LDS matrix; the pass is rare, not tuned
       const size_t l = lds_bytes(h->P, wpb, 0, h->cpl, h->rpl);
       if (l <= (size_t)h->lds_limit) { cert_wpb = wpb; cert_lds = l; }
     }
+    if (light) { cert_wpb = 1; cert_lds = h->light_lds; }
     if (!cert_wpb) a.opt.eps_infeasible = 0.0;
   }
   const bool timed = stats && sync_stats;
@@ -948,7 +965,8 @@ int dsp_solve(dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, dsp
     if (nsus != 0) {
       const int want = nsus > 0 ? (nsus + cert_wpb - 1) / cert_wpb : (cert_grid_env > 0 ? cert_grid_env : 8);
       const int grid2 = std::max(1, std::min(std::min((B + cert_wpb - 1) / cert_wpb, want), 2 * h->num_cus));
-      HIP_TRY(launch_solve(h->cpl, h->rpl, c, dim3(grid2), dim3(64 * cert_wpb), cert_lds, st));
+      HIP_TRY(light ? launch_solve_light(h->cpl, h->rpl, a, c, grid2, cert_lds, st)
+                    : launch_solve(h->cpl, h->rpl, c, dim3(grid2), dim3(64 * cert_wpb), cert_lds, st));
     }
   }
   if (a.opt.recertify_passes > 0 && batch->flags) {
@@ -961,10 +979,11 @@ int dsp_solve(dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, dsp
     static const struct { double pid_kp, restart_artificial; int check_every; } kRecertify[3] = {{0.45, 0.3, 0}, {0.8, 0.15, 0}, {0.3, 0.5, 12}};
     int rwpb = 0;
     size_t rlds = 0;
-    for (int wpb = 1; wpb <= 4; ++wpb) {
+    for (int wpb = 1; wpb <= 4 && !light; ++wpb) {
       const size_t l = lds_bytes(h->P, wpb, 0, h->cpl, h->rpl);
       if (l <= (size_t)h->lds_limit) { rwpb = wpb; rlds = l; }
     }
+    if (light) { rwpb = 1; rlds = h->light_lds; }            // (one-wave blocks of the light kernel: above)
     for (int v = 0; rwpb && v < std::min(a.opt.recertify_passes, 3); ++v) {
       SolveArgs c = a;
       c.matreg = 0;
@@ -977,7 +996,8 @@ int dsp_solve(dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, dsp
       if (kRecertify[v].check_every) c.opt.check_every = kRecertify[v].check_every;
       c.opt.polish_patience = std::max(c.opt.polish_patience, 1024);       // (a pass that waives as readily as the first certifies nothing)
       const int rgrid = std::max(1, std::min((B + rwpb - 1) / rwpb, 64));
-      HIP_TRY(launch_solve(h->cpl, h->rpl, c, dim3(rgrid), dim3(64 * rwpb), rlds, st));
+      HIP_TRY(light ? launch_solve_light(h->cpl, h->rpl, a, c, rgrid, rlds, st)
+                    : launch_solve(h->cpl, h->rpl, c, dim3(rgrid), dim3(64 * rwpb), rlds, st));
     }
   }
   if (timed) HIP_TRY(hipEventRecord(h->ev1, st));

@@ -164,6 +164,10 @@ inline unsigned uniform_pack(int slots, int w) { unsigned p = 0; for (int q = 0;
 hipError_t launch_solve(int cpl, int rpl, const SolveArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t st);
 int matreg_available(int cpl, int rpl, unsigned wc_pack, unsigned wr_pack, bool lng, bool qp = false);   // 0 / 1
 hipError_t occupancy_solve(int cpl, int rpl, const SolveArgs &a, int block_threads, size_t lds, int *blocks_per_cu);
+// follow-up passes (certificates, re-certification) of a three-wave first pass `first`: the generic kernel's light instantiation in
+// blocks of one wave (dsp_kernels.hip).  light_followup_blocks: resident blocks per CU, 0 = no such kernel for this first pass
+int light_followup_blocks(int cpl, int rpl, const SolveArgs &first, size_t lds);
+hipError_t launch_solve_light(int cpl, int rpl, const SolveArgs &first, const SolveArgs &a, int grid, size_t lds, hipStream_t st);
 size_t simplex_lds_bytes(int n, int m, int *row_stride);
 hipError_t launch_simplex(const SimplexArgs &a, int grid, size_t lds, hipStream_t st);
 // float32-iterate solve (dsp_qp.hip); returns the launch geometry it chose

@@ -214,6 +214,12 @@ __device__ __forceinline__ void stage_entries(Entry *dst, const Entry *__restric
 constexpr bool three_waves_shape(int cpl, int rpl, unsigned wc, unsigned wr, bool qp) {
   return !qp && cpl == 4 && rpl == 2 && wc == 0x1133u && wr == 0x44u;
 }
+// The one place that says which first passes are three-wave kernels as the HOST sees a launch (shape of the handle, long vectors, QP):
+// their follow-up passes (certificates, re-certification) run the LIGHT instantiation of the generic kernel of the same <CPL, RPL>,
+// compiled ahead of time for exactly these (light_fn).  Every other first pass holds 256 VGPRs like the generic kernel and keeps it.
+constexpr bool three_waves_first_pass(int cpl, int rpl, unsigned wc, unsigned wr, bool lng, bool qp) {
+  return !lng && three_waves_shape(cpl, rpl, wc, wr, qp);
+}
 #ifndef DSP_ONE_WAVE_FROM
 #define DSP_ONE_WAVE_FROM 99      /* CPL + RPL from which the kernel is compiled for ONE wave per SIMD (512 registers: 256 V + 256 A) */
 #endif
@@ -243,8 +249,12 @@ struct Rare {
   __device__ __forceinline__ void set(double x) { if constexpr (L) lds_store_f64(addr, x); else v = x; }
 };
 
-template <int CPL, int RPL, bool LONG, unsigned WC, unsigned WR, bool QP = false>
-__global__ void __launch_bounds__((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 256 : 512, three_waves_shape(CPL, RPL, WC, WR, QP) ? 3 : (CPL + RPL <= 6) ? DSP_MIN_WAVES_SMALL : ((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 1 : 2)) pdlp_solve_kernel(SolveArgs a) {
+// LIGHT (launch bounds only - the body is the same): the generic kernel as the FOLLOW-UP pass (certificates, re-certification) of a
+// three-wave first pass, compiled for blocks of one wave at three waves per SIMD, so that a block fits the 168 VGPRs ONE leaving
+// wave of the first pass sets free; at 256 VGPRs a wave needs two of a SIMD's three gone, a block of four that on one CU four times
+// over, and the stream's next solve waits behind it.  It spills; it runs for suspects and flagged scenarios only.
+template <int CPL, int RPL, bool LONG, unsigned WC, unsigned WR, bool QP = false, bool LIGHT = false>
+__global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 256 : 512, (LIGHT || three_waves_shape(CPL, RPL, WC, WR, QP)) ? 3 : (CPL + RPL <= 6) ? DSP_MIN_WAVES_SMALL : ((CPL + RPL >= DSP_ONE_WAVE_FROM && WC != 0) ? 1 : 2)) pdlp_solve_kernel(SolveArgs a) {
   constexpr bool MATREG = WC != 0;
   constexpr bool EARLY_MAT = MATREG && CPL + RPL <= DSP_EARLY_MAT_UPTO;   // restart block: matrix re-read issued ahead of the weight update
   constexpr bool RLDS = MATREG;                                        // rare per-scenario values in LDS (struct Rare)
@@ -1258,6 +1268,38 @@ static const void *generic_fn(bool lng, bool qp) {
   if (qp) return lng ? nullptr : reinterpret_cast<const void *>(&pdlp_solve_kernel<CPL, RPL, false, 0u, 0u, true>);
   return lng ? reinterpret_cast<const void *>(&pdlp_solve_kernel<CPL, RPL, true, 0u, 0u>)
              : reinterpret_cast<const void *>(&pdlp_solve_kernel<CPL, RPL, false, 0u, 0u>);
+}
+
+// the LIGHT instantiation of the generic kernel that follows the first pass `first`, nullptr where the first pass is no three-wave kernel
+static const void *light_fn(int cpl, int rpl, const SolveArgs &first) {
+#ifndef DSP_NO_MATREG
+  const bool lng = first.P.long_c.count > 0 || first.P.long_r.count > 0;
+  if (!first.matreg || !three_waves_first_pass(cpl, rpl, first.P.mr_wc_pack, first.P.mr_wr_pack, lng, first.qp != 0)) return nullptr;
+  static_assert(three_waves_first_pass(4, 2, 0x1133u, 0x44u, false, false), "the light instantiation below follows this first pass");
+  if (cpl == 4 && rpl == 2) return reinterpret_cast<const void *>(&pdlp_solve_kernel<4, 2, false, 0u, 0u, false, true>);
+#endif
+  return nullptr;
+}
+// resident one-wave blocks per CU of the light follow-up kernel behind the first pass `first`; 0: there is none (or it does not fit)
+int light_followup_blocks(int cpl, int rpl, const SolveArgs &first, size_t lds) {
+  const void *fn = light_fn(cpl, rpl, first);
+  int nb = 0;
+  if (!fn || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64, lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return nb;
+}
+// a follow-up pass `a` (matreg = 0) in blocks of one wave; `first`: the first pass it follows
+hipError_t launch_solve_light(int cpl, int rpl, const SolveArgs &first, const SolveArgs &a, int grid, size_t lds, hipStream_t st) {
+  const void *fn = light_fn(cpl, rpl, first);
+  if (!fn || a.matreg || a.waves_per_block != 1) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  SolveArgs args = a;
+  void *params[] = {&args};
+  return hipLaunchKernel(fn, dim3(grid), dim3(64), params, lds, st);
 }
 
 template <int CPL, int RPL>

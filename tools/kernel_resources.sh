@@ -13,6 +13,7 @@ template __global__ void pdlp_solve_kernel<4, 3, true, 0x1122u, 0x233u, false>(S
 template __global__ void pdlp_solve_kernel<3, 2, false, 0x122u, 0x24u, false>(SolveArgs);            // nuclear 24 h
 template __global__ void pdlp_solve_kernel<1, 1, false, 0x3u, 0x4u, false>(SolveArgs);               // 4-h hourly LPs
 template __global__ void pdlp_solve_kernel<4, 2, false, 0u, 0u, false>(SolveArgs);                   // generic (LDS matrix, with certificates)
+$(grep -q 'bool LIGHT' "$src/dsp_kernels.hip" && echo 'template __global__ void pdlp_solve_kernel<4, 2, false, 0u, 0u, false, true>(SolveArgs);             // ... its light instantiation (follow-up passes of a three-wave first pass)')
 }
 EOT
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 $KRES_FLAGS -S --cuda-device-only -I$src -o $out/$tag.s $out/$tag.hip -Rpass-analysis=kernel-resource-usage 2> $out/$tag.res
