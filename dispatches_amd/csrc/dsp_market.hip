@@ -16,6 +16,7 @@
 //
 //   loop_schedule_prepare_kernel   the coupled day-ahead LP of a self-scheduling plant (dsp_loop_schedule_prepare): S scenario blocks in
 //                           ONE row per plant, one lane per (plant, scenario), the row's constant summed in the order of i by one lane.
+//                           A block is written once, by lmk_write_block, for this kernel and for loop_market_prepare_kernel.
 //   loop_market_prepare_kernel / loop_market_clear_kernel   the same two for ANY flowsheet, by descriptor (dsp_loop_market_*; rolling_flowsheets.py):
 //                           power P_T = (x[a] ca + x[b] cb) + const, curves that start at the generator's p_min, <= 2 state columns,
 //                           optional wind; the clearing lanes also write the tracker's LP (a dsp_loop_model).  VGPRs / scratch of every
@@ -180,17 +181,30 @@ __device__ __forceinline__ long long lmk_rt(const dsp_loop_market_state &s, long
   return v < 0 ? v + s.N : v;
 }
 
-__global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m, int k) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= s.B * s.S) return;
-  const int b = r / s.S, i = r - b * s.S;
+// sum_t rt[t] pt_const[t] of scenario j's real-time prices asked at hour-of-day hod, in the order of t: the prices' share of a block's
+// objective constant
+__device__ __forceinline__ double lmk_price_sum(const dsp_loop_market_state &s, const dsp_loop_market_model &m, long long st0, long long h,
+                                                int j, int hod) {
+  double price_sum = 0.0;
+  for (int t = 0; t < m.T; ++t) {
+    const double rtp = s.rt_series[lmk_rt(s, loop_scenario_index(s, st0, h, j, hod, t))];
+    const double pc = loop_opaque(__dmul_rn(rtp, m.pt_const[t]));
+    price_sum = t ? __dadd_rn(price_sum, pc) : pc;
+  }
+  return price_sum;
+}
+
+// One bidding block - c / lb / ub of a row of a bidding batch, or of scenario block i of a coupled row - of plant b at hour k of the
+// day (-1: the day-ahead bid): objective entries of the two power terms and of day_ahead_power on scenario i's prices, wind bounds of
+// the realised window (wind size kw), day_ahead_power fixed to the cleared offer inside the cleared day and free beyond it, state
+// columns.  Returns what the block's objective constant takes: sum_t rt[t] pt_const[t] and sum_t avail[t], each in the order of t.
+struct lmk_sums { double price, avail; };
+__device__ __forceinline__ lmk_sums lmk_write_block(const dsp_loop_market_state &s, const dsp_loop_market_model &m, double *c, double *lb,
+                                                    double *ub, int b, int i, int k, double kw) {
   const long long h = *s.hour, st0 = s.start[b];
   const int hod = k < 0 ? 0 : k;
   const int known = k < 0 ? 0 : min(m.T, 24 - k);
   const bool wind = m.wind_cols[0] >= 0;
-  const double kw = m.wind_kw_plant ? m.wind_kw_plant[b] : m.wind_kw;       // per-plant sizes (ABI 16): row r belongs to plant b = r / S
-  const double c0_base = m.c0_base_plant ? m.c0_base_plant[b] : m.c0_base;
-  double *c = m.c + (size_t)r * m.n, *lb = m.lb + (size_t)r * m.n, *ub = m.ub + (size_t)r * m.n;
   double avail_sum = 0.0, price_sum = 0.0;
   for (int t = 0; t < m.T; ++t) {
     const long long at = loop_scenario_index(s, st0, h, i, hod, t);
@@ -214,64 +228,49 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
     lb[pda] = fix;
     ub[pda] = t < known ? fix : INFINITY;
   }
-  double c0 = loop_opaque(__dsub_rn(c0_base, price_sum));
-  if (wind) c0 = __dadd_rn(c0, loop_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
-  m.c0[r] = c0;
   for (int j = 0; j < m.n_state; ++j) {
     const double v = s.state[(size_t)b * m.n_state + j];
     lb[m.state_init[j]] = v; ub[m.state_init[j]] = v;
   }
+  return {price_sum, avail_sum};
+}
+
+// a block's objective constant: (base - price_sum) + waste, the wind term only where there is wind
+__device__ __forceinline__ double lmk_c0(double base, double price_sum, bool wind, double waste) {
+  const double c0 = loop_opaque(__dsub_rn(base, price_sum));
+  return wind ? loop_opaque(__dadd_rn(c0, waste)) : c0;
+}
+
+__global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m, int k) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= s.B * s.S) return;
+  const int b = r / s.S, i = r - b * s.S;
+  const bool wind = m.wind_cols[0] >= 0;
+  const double kw = m.wind_kw_plant ? m.wind_kw_plant[b] : m.wind_kw;       // per-plant sizes (ABI 16): row r belongs to plant b = r / S
+  const double c0_base = m.c0_base_plant ? m.c0_base_plant[b] : m.c0_base;
+  const size_t at0 = (size_t)r * m.n;
+  const lmk_sums sums = lmk_write_block(s, m, m.c + at0, m.lb + at0, m.ub + at0, b, i, k, kw);
+  m.c0[r] = lmk_c0(c0_base, sums.price, wind, wind ? loop_opaque(__dmul_rn(m.waste_per_kw, sums.avail)) : 0.0);
 }
 
 // The coupled day-ahead LP of a self-scheduling plant (dsp_loop_schedule_prepare, ABI 18): S scenario blocks of m.n columns side by side
-// in row b (m.row_stride doubles apart), one lane per (plant, scenario).  Block i is written as loop_market_prepare_kernel with k = -1
-// writes row b * S + i; the lane of scenario 0 also sums the S objective constants in the order of i - alone, so that the order is the
-// tensor form's (BatchedDoubleLoop._day_ahead_step_self_schedule).
+// in row b (m.row_stride doubles apart), one lane per (plant, scenario).  Block i is the block that loop_market_prepare_kernel writes
+// into row b * S + i with k = -1; the lane of scenario 0 also sums the S objective constants in the order of i - alone, so that the
+// order is the tensor form's (BatchedDoubleLoop._day_ahead_step_self_schedule).
 __global__ void __launch_bounds__(256) loop_schedule_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= s.B * s.S) return;
   const int b = r / s.S, i = r - b * s.S;
-  const long long h = *s.hour, st0 = s.start[b];
   const bool wind = m.wind_cols[0] >= 0;
   const size_t at0 = (size_t)b * m.row_stride + (size_t)i * m.n;
-  double *c = m.c + at0, *lb = m.lb + at0, *ub = m.ub + at0;
-  double avail_sum = 0.0;
-  for (int t = 0; t < m.T; ++t) {
-    const long long at = loop_scenario_index(s, st0, h, i, 0, t);
-    const double rtp = s.rt_series[lmk_rt(s, at)];
-    const double dap = s.da_series[at];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int col = m.pt_cols[t][e];
-      if (col >= 0) c[col] = __dsub_rn(m.base_c[col], loop_opaque(__dmul_rn(m.pt_coef[t][e], rtp)));
-    }
-    const int pda = m.pda_cols[t];
-    c[pda] = __dsub_rn(m.base_c[pda], loop_opaque(__dsub_rn(dap, rtp)));
-    if (wind) {
-      const double avail = loop_opaque(__dmul_rn(m.wind_kw, s.cf_series[(st0 + h + t) % s.N]));
-      ub[m.wind_cols[t]] = avail;
-      avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
-    }
-    lb[pda] = 0.0;
-    ub[pda] = INFINITY;
-  }
-  for (int j = 0; j < m.n_state; ++j) {
-    const double v = s.state[(size_t)b * m.n_state + j];
-    lb[m.state_init[j]] = v; ub[m.state_init[j]] = v;
-  }
+  const lmk_sums sums = lmk_write_block(s, m, m.c + at0, m.lb + at0, m.ub + at0, b, i, -1, m.wind_kw);
   if (i != 0) return;
   // ---- the row's objective constant: the S scenario constants added in the order of i ----
-  const double waste = wind ? loop_opaque(__dmul_rn(m.waste_per_kw, avail_sum)) : 0.0;
+  const long long h = *s.hour, st0 = s.start[b];
+  const double waste = wind ? loop_opaque(__dmul_rn(m.waste_per_kw, sums.avail)) : 0.0;
   double total = 0.0;
   for (int j = 0; j < s.S; ++j) {
-    double price_sum = 0.0;
-    for (int t = 0; t < m.T; ++t) {
-      const double rtp = s.rt_series[lmk_rt(s, loop_scenario_index(s, st0, h, j, 0, t))];
-      const double pc = loop_opaque(__dmul_rn(rtp, m.pt_const[t]));
-      price_sum = t ? __dadd_rn(price_sum, pc) : pc;
-    }
-    double c0 = loop_opaque(__dsub_rn(m.c0_base, price_sum));
-    if (wind) c0 = loop_opaque(__dadd_rn(c0, waste));
+    const double c0 = lmk_c0(m.c0_base, lmk_price_sum(s, m, st0, h, j, 0), wind, waste);
     total = j ? __dadd_rn(total, c0) : c0;
   }
   m.c0[b] = total;

@@ -39,12 +39,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import scenarios
-from .hip_solver import DeviceLP, default_options
-
-
-class _NoSolver:
-    def solve(self, *a, **k):
-        raise RuntimeError("template model: never solved on the host")
+from ._device_loop import _DeviceLoop, _NoSolver, attach_solver  # noqa: F401  (_NoSolver: re-exported)
 
 
 class _DeviceModel:
@@ -82,34 +77,7 @@ class _DeviceModel:
         self.wind_kw = float(fam["wind_kw"])
         # P_T[t] = 1e-3 (grid_elec[t] + elec_out[t]): the two columns of every hour
         self.pt_cols = idx([[p["grid_elec"].index, p["elec_out"].index] for p in per])       # [T, 2]
-        if lp_backend is None:
-            # recertify: the loop never reads a flag back between solves (its days are hipGraph replays), so a solve accepted without a
-            # certified objective accuracy is re-solved on the device under other settings (dsp_options::recertify_passes)
-            # (three passes for the day-ahead LP, which the PDLP kernel solves; one for the hourly LPs, which the in-wave simplex solves to a
-            #  vertex and which pay an empty launch per pass and solve, 49 solves per plant-day)
-            # The hourly LPs get neither: they carry slack columns (always feasible - and the simplex reports an infeasible input itself), and a
-            # first-order fallback has not been needed once (zero hand-overs); should one ever come back flagged, the loop's `uncertified`
-            # count says so.  Two empty launches per solve less, 96 per plant-day.
-            extra = {"recertify_passes": 3} if self.T > 16 else {"recertify_passes": 0, "eps_infeasible": 0.0}
-            self.opts = default_options(**{**extra, **(hints or {})})
-            # The hourly LPs of a plant share one matrix from hour to hour: the simplex starts hour k from hour k - 1's final basis
-            # (dsp_options::simplex_warm: 2 - 4 pivots instead of ~26) and from the slack basis in the first hour of every day.
-            from .hip_solver import DspOptions
-            self.opts_warm, self.opts_first = DspOptions.from_buffer_copy(self.opts), DspOptions.from_buffer_copy(self.opts)
-            if self.T <= 16:
-                self.opts_warm.simplex_warm, self.opts_first.simplex_warm = 1, 2
-            self.dlp = DeviceLP(self.lp, device_index, self.opts)
-            # output buffers with fixed addresses from the start (the fused update kernel and the hipGraphs hold pointers)
-            n, m = self.lp.n, max(self.lp.m, 1)
-            self.out = dict(x=torch.zeros((B, n), dtype=torch.float64, device=dev), y=torch.zeros((B, m), dtype=torch.float64, device=dev),
-                            obj=torch.zeros(B, dtype=torch.float64, device=dev), status=torch.zeros(B, dtype=torch.int32, device=dev),
-                            iters=torch.zeros(B, dtype=torch.int32, device=dev), jumps=torch.zeros(B, dtype=torch.int32, device=dev),
-                            flags=torch.zeros(B, dtype=torch.int32, device=dev))
-        else:                                   # tests: a stand-in with DeviceLP.solve's signature (CPU tensors + HiGHS)
-            self.opts = None
-            self.dlp = lp_backend(self.lp)
-        if lp_backend is not None:
-            self.out = None
+        attach_solver(self, B, dev, device_index, hints, lp_backend)
 
     def wb_struct(self, needs_state=True):
         """dsp_wb_model of this LP (include/dsp_hip.h) for the fused rolling-update kernel.  needs_state: the kernel reads the
@@ -167,7 +135,7 @@ class _DeviceModel:
         return self.out
 
 
-class BatchedWindBatteryDoubleLoop:
+class BatchedWindBatteryDoubleLoop(_DeviceLoop):
     def __init__(self, n_scenarios, device=0, first_scenario=0, series="rts_gmlc_309.npz", stride=17,
                  day_ahead_horizon=48, real_time_horizon=4, tracking_horizon=4, wind_mw=200.0, batt_mw=25.0,
                  price_cap=500.0, warm_start=True, lp_backend=None, use_graphs=True, use_fused=True, record=None, simplex_warm=True, warm_patience=10000,
@@ -199,12 +167,7 @@ class BatchedWindBatteryDoubleLoop:
         self.B = B = int(n_scenarios)
         self.S = S = int(n_price_scenarios)
         self.D = D = int(max_historical_days)
-        if forecaster not in ("perfect", "backcast") or market not in ("stub", "price_taker"):
-            raise ValueError(f"forecaster is 'perfect' or 'backcast' and market 'stub' or 'price_taker', not {forecaster!r} / {market!r}")
-        if forecaster == "backcast" and not 1 <= S <= min(16, D):
-            raise ValueError(f"forecaster='backcast' needs 1 <= n_price_scenarios <= min(16, max_historical_days), not {S} (max_historical_days={D})")
-        if forecaster == "perfect" and S != 1:
-            raise ValueError("forecaster='perfect' knows one price scenario: n_price_scenarios must be 1")
+        self._check_market_arguments(forecaster, market, S, D)
         self.forecaster, self.market = forecaster, market
         self.stochastic = forecaster != "perfect" or market != "stub"
         rows = B * S                                                       # rows of the bidding LPs' batches (plant b, scenario i: row b * S + i)
@@ -284,6 +247,7 @@ class BatchedWindBatteryDoubleLoop:
         self.uncertified = torch.zeros((), dtype=torch.int64, device=dev)  # solves accepted with DSP_FLAG_OBJ_WAIVED so far
         self.hour = 0
         self.hour_t = torch.zeros((), dtype=torch.int64, device=dev)      # the clock ON THE DEVICE (graphs replay across days)
+        self._clk = self.hour_t                                           # (what the windows read: _DeviceLoop)
         self.da_offer = torch.zeros((B, 24), dtype=torch.float64, device=dev)
         self.da_prices = torch.zeros((B, 24), dtype=torch.float64, device=dev)
         self.da_pw = torch.zeros(rows, dtype=torch.float64, device=dev)
@@ -374,13 +338,7 @@ class BatchedWindBatteryDoubleLoop:
             self.da_x0.zero_(), self.da_y0.zero_()
         self.hour = self.solves = 0
 
-    # -- windows -----------------------------------------------------------------------------------------------------------
-    def _window(self, series, T):
-        """[B, T] window of `series` that starts at the current hour of every plant (clock read on the device)"""
-        import torch
-        idx = (self.start[:, None] + self.hour_t + torch.arange(T, device=self.dev)[None, :]) % self.N
-        return series[idx]
-
+    # -- what update_model writes -----------------------------------------------------------------------------------------
     def _set_prices(self, m, da, rt):
         """c = base - RT x dP_T/dx - (DA - RT) on day_ahead_power   (Bidder._pass_price_forecasts, on the device)"""
         m.c[:] = m.base_c
@@ -402,13 +360,6 @@ class BatchedWindBatteryDoubleLoop:
                 total = total + avail[:, t]
             m.c0.copy_(m._c0_base + m._waste_per_kw * total)
 
-    def _check(self, out):
-        self.bad |= (out["status"] != 0).any()
-        # accepted without a certified objective accuracy (DSP_FLAG_OBJ_WAIVED): counted, on the device (the loop is replayed
-        # from hipGraphs: no host round trip to re-solve them here); results() reports the count next to `ok`
-        if out.get("flags") is not None:
-            self.uncertified += ((out["flags"] & 1) != 0).sum()
-
     # -- one simulated day -------------------------------------------------------------------------------------------------
     def _day_ahead_step(self):
         """Device work of the day-ahead bids (capturable: reads / writes persistent tensors only)."""
@@ -417,8 +368,7 @@ class BatchedWindBatteryDoubleLoop:
         da, rt = self._window(self.da_series, m.T), self._window(self.rt_series, m.T)
         self._set_prices(m, da, rt)
         self._set_state(m)
-        m.lb.index_fill_(1, m.pda_cols, 0.0)          # (index_fill_, not lb[:, cols] = 0.0: a Python scalar on the right-hand
-        m.ub.index_fill_(1, m.pda_cols, float("inf"))  #  side becomes a host-to-device copy, which a graph capture refuses)
+        self._free_day_ahead_power(m)
         if self.warm_start:
             out = m.solve(self.B, x0=self.da_x0, y0=self.da_y0, primal_weight=self.da_pw)
             torch.index_select(out["x"], 1, self.da_cmap, out=self.da_x0)
@@ -437,23 +387,6 @@ class BatchedWindBatteryDoubleLoop:
         self.da_energy_mwh += self.da_offer.sum(1)
 
     # -- stochastic mode: backcast scenarios, bid curves, market clearing ---------------------------------------------------------
-    def _forecast(self, series, T, hod):
-        """[B, S, T] price scenarios asked at hour-of-day `hod` of the current day (clock read on the device).  Backcast: exactly
-        Backcaster._forecast over the D whole days before the current day of every plant's own circular series -
-        pos = (24 (D - 1 - i) + hod + t) mod 24 D into that history, i.e. series[(start + 24 (d - D) + pos) mod N]."""
-        import torch
-        if self.forecaster == "perfect":
-            return self._window(series, T)[:, None, :]
-        D = self.D
-        d = torch.div(self.hour_t, 24, rounding_mode="floor")
-        i, t = torch.arange(self.S, device=self.dev)[:, None], torch.arange(T, device=self.dev)[None, :]
-        pos = (24 * (D - 1 - i) + hod + t) % (24 * D)
-        return series[(self.start[:, None, None] + 24 * (d - D) + pos[None]) % self.N]
-
-    def _rows(self, v):
-        """per-plant values [B, ...] -> per-row [B * S, ...] (a plant's S rows are adjacent)"""
-        return v if self.S == 1 else v.repeat_interleave(self.S, dim=0)
-
     def _set_state_rows(self, m):
         """_set_state for a bidding model of B * S rows: the plant's state, wind availability and objective constant in each of its rows"""
         soc, thr = self._rows(self.soc), self._rows(self.thr)
@@ -468,31 +401,9 @@ class BatchedWindBatteryDoubleLoop:
             total = total + avail[:, t]
         m.c0.copy_(self._rows(m._c0_base + m._waste_per_kw * total))
 
-    def _curves(self, power, price, status):
-        """power, price [B, S, Tc]; status [B * S] -> (U, M [S + 1, B * Tc] int64 cents, count [B * Tc]) - workflow/market.py::plant_curves"""
-        import torch
-        from .workflow.market import plant_curves
-        B, S, Tc = power.shape
-        lanes = lambda a: a.expand(B, S, Tc).permute(1, 0, 2).reshape(S, B * Tc)
-        return plant_curves(torch, lanes(power), lanes(price), lanes((status == 0).reshape(B, S, 1)))
-
-    def _clear(self, U, M, count, lmp):
-        import torch
-        from .workflow.market import clear_curves
-        return clear_curves(torch, U, M, count, lmp.reshape(-1), self._hundred, price_taker=self.market == "price_taker").reshape(lmp.shape)
-
-    def _store_curves(self, curve, cnt, U, M, count):
-        import torch
-        B, Tc = cnt.shape
-        curve.copy_(torch.stack([U.t().reshape(B, Tc, self.S + 1), M.t().reshape(B, Tc, self.S + 1)], dim=3))
-        cnt.copy_(count.reshape(B, Tc))
-
     def _market(self, fn, *args):
         import ctypes as C
-        import torch
-        rc = fn(C.byref(self._mk_state), *args, C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"{fn.__name__} failed ({rc})")
+        self._call(fn, C.byref(self._mk_state), *args)
 
     def _day_ahead_step_stochastic(self):
         """Day-ahead bids of the stochastic mode (capturable): B * S 48-h LPs - row b * S + i on scenario i's day-ahead and real-time
@@ -509,8 +420,7 @@ class BatchedWindBatteryDoubleLoop:
             da, rt = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T), self._forecast(self.rt_series, m.T, 0).expand(B, S, m.T)
             self._set_prices(m, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
             self._set_state_rows(m)
-            m.lb.index_fill_(1, m.pda_cols, 0.0)
-            m.ub.index_fill_(1, m.pda_cols, float("inf"))
+            self._free_day_ahead_power(m)
         if self.warm_start:
             out = m.solve(B * S, x0=self.da_x0, y0=self.da_y0, primal_weight=self.da_pw)
             torch.index_select(out["x"], 1, self.da_cmap, out=self.da_x0)
@@ -536,9 +446,7 @@ class BatchedWindBatteryDoubleLoop:
             self._record("da_obj", out["obj"].reshape(B, S), daily=True)
             for key, v in (("da_curve", self.da_curve), ("da_count", self.da_count), ("da_dispatch", self.da_offer)):
                 self._record(key, v, daily=True)
-        self.da_energy_mwh += self.da_offer.sum(1)
-        last = torch.gather(self.da_curve[:, :, :, 0], 2, (self.da_count.to(torch.int64) - 1)[:, :, None])[:, :, 0]
-        self.offered_mwh += (last.to(torch.float64) / self._hundred).sum(1)
+        self._account_day_ahead()
 
     def _hour_step_stochastic(self, k):
         """Hour k of the day in the stochastic mode (capturable): B * S real-time LPs (scenario i = the real-time backcast at hour-of-day
@@ -564,11 +472,8 @@ class BatchedWindBatteryDoubleLoop:
             da_f[:, :, :known] = self.da_prices[:, None, k:k + known]
             self._set_prices(m, da_f.reshape(B * S, m.T), rt_f.reshape(B * S, m.T))
             self._set_state_rows(m)
-            m.lb.index_fill_(1, m.pda_cols, 0.0)
-            m.ub.index_fill_(1, m.pda_cols, float("inf"))
-            m.lb[:, m.pda_cols[:known]] = self._rows(self.da_offer[:, k:k + known])
-            m.ub[:, m.pda_cols[:known]] = self._rows(self.da_offer[:, k:k + known])
-            out = m.solve(B * S, hour=hour) if m.opts is not None else m.solve(B * S)
+            self._free_day_ahead_power(m, k, S)
+            out = m.solve(B * S, hour=hour)
             self._check(out)
             power = m.power_output(out["x"])[:, :tr.T].reshape(B, S, tr.T)
             U, M, count = self._curves(power, rt_f[:, :, :tr.T], out["status"])
@@ -578,7 +483,7 @@ class BatchedWindBatteryDoubleLoop:
             self._set_state(tr)
             tr.rlo[:, tr.track_rows] = self.rt_dispatch
             tr.rhi[:, tr.track_rows] = self.rt_dispatch
-            out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
+            out = tr.solve(B, hour=hour)
             self._check(out)
         if self._rec is not None:
             self._record("rt_x", m.out["x"].reshape(B, S, -1))
@@ -601,11 +506,7 @@ class BatchedWindBatteryDoubleLoop:
 
     def _fused(self, phase, k):
         import ctypes as C
-        import torch
-        rc = self._lib.dsp_wb_rolling_update(C.byref(self._wb_state), C.byref(self._wb_rt), C.byref(self._wb_tr), phase, k,
-                                             C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"dsp_wb_rolling_update failed ({rc})")
+        self._call(self._lib.dsp_wb_rolling_update, C.byref(self._wb_state), C.byref(self._wb_rt), C.byref(self._wb_tr), phase, k)
 
     def _hour_step(self, k):
         """Device work of hour k of the day: real-time bid, stub clearing, tracking, state hand-off, clock (capturable)."""
@@ -632,12 +533,9 @@ class BatchedWindBatteryDoubleLoop:
         da[:, :known] = self.da_prices[:, k:k + known]
         self._set_prices(m, da, rt)
         self._set_state(m)
-        m.lb.index_fill_(1, m.pda_cols, 0.0)          # (index_fill_, not lb[:, cols] = 0.0: a Python scalar on the right-hand
-        m.ub.index_fill_(1, m.pda_cols, float("inf"))  #  side becomes a host-to-device copy, which a graph capture refuses)
-        m.lb[:, m.pda_cols[:known]] = self.da_offer[:, k:k + known]
-        m.ub[:, m.pda_cols[:known]] = self.da_offer[:, k:k + known]
+        self._free_day_ahead_power(m, k)
         hour = k if self.simplex_warm else None
-        out = m.solve(self.B, hour=hour) if self.rt.opts is not None else m.solve(self.B)
+        out = m.solve(self.B, hour=hour)
         self._check(out)
         offer = m.power_output(out["x"])                                 # real-time offer = SCED dispatch in the stub market
         # tracking
@@ -645,7 +543,7 @@ class BatchedWindBatteryDoubleLoop:
         self._set_state(tr)
         tr.rlo[:, tr.track_rows] = offer[:, :tr.T]
         tr.rhi[:, tr.track_rows] = offer[:, :tr.T]
-        out = tr.solve(self.B, hour=hour) if self.tr.opts is not None else tr.solve(self.B)
+        out = tr.solve(self.B, hour=hour)
         self._check(out)
         if self._rec is not None:
             for key, mm in (("rt", self.rt), ("tr", self.tr)):
@@ -662,22 +560,6 @@ class BatchedWindBatteryDoubleLoop:
         self.energy_mwh += self.delivered
         self.hour_t += 1
 
-    def _run(self, key, fn):
-        """Run one step: eagerly, or - with use_graphs - captured once into a hipGraph and replayed from then on."""
-        import torch
-        if not self.use_graphs or not self._warm:
-            fn()
-            return
-        g = self._graphs.get(key)
-        if g is None:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
-            self._graphs[key] = g
-        g.replay()
-
-    _warm = False          # the first day runs eagerly (handles, output buffers and kernels get created), then graphs
-
     def day_ahead(self):
         """Day-ahead bids of every plant for the day that starts at self.hour: returns the offers [B, 24] (= cleared dispatch)."""
         self.day_start = self.hour
@@ -692,12 +574,6 @@ class BatchedWindBatteryDoubleLoop:
         self.solves += self.B * self.S + self.B
         self.hour += 1
         return self.delivered.clone()
-
-    def run_day(self):
-        self.day_ahead()
-        for _ in range(24):
-            self.hour_step()
-        self._warm = True
 
     def results(self):
         """Per-scenario totals so far (device tensors) + whether every solve was optimal (one device->host sync)."""

@@ -19,7 +19,7 @@ Stochastic mode (n_price_scenarios / forecaster="backcast" / market="price_taker
 n_scenario = 3 on a Backcaster, nuclear_flowsheet_double_loop.ipynb): the semantics of rolling.py's stochastic mode over the descriptor.
 Every plant bids on S backcast scenarios (rows b * S + i of the bidding batches), the S solutions of a period become one bid curve that
 starts at the generator's p_min (400 MW for the nuclear unit, Bidder._assemble_bids), a price-taker market dispatches the plant along it,
-and the tracker follows the cleared dispatch.  `_day_ahead_step_stochastic` / `_hour_step_stochastic` are the executable specification as
+and the tracker follows the cleared dispatch.  `_day_ahead_step_stochastic` / `_hour_step_bid` are the executable specification as
 tensor operations; csrc/dsp_market.hip (dsp_loop_market_*) is the same arithmetic in two kernels, bit for bit.
 
 Parametrized mode (bidder="parametrized", bid_price, storage_mw; the reference's wind + PEM study run_double_loop_PEM.py bids with a
@@ -59,16 +59,15 @@ integer cents where the reference rounds to 4 dp - so a price taker runs at its 
 Inside the cleared day every day_ahead_power column of the hourly problem is fixed to the cleared offer in all scenarios, the coupling
 rows are vacuous and the coupled LP separates: the hourly step solves B real-time LPs, scenario 0 only, and bids (P_T[t], 0).  OURS:
 in the last T_rt - 1 hours of a day the look-ahead periods past midnight have a free day_ahead_power which the host would still tie
-across scenarios; this loop does not.  `_day_ahead_step_self_schedule` / `_hour_step_self_schedule` are the specification as tensor
-operations; csrc/dsp_market.hip (dsp_loop_schedule_prepare; dsp_loop_market_prepare / _clear on an S = 1 state with
+across scenarios; this loop does not.  `_day_ahead_step_self_schedule` / `_hour_step_bid` (the one hourly bidding step, here with
+one row per plant and pairs priced at 0) are the specification as tensor operations; csrc/dsp_market.hip (dsp_loop_schedule_prepare; dsp_loop_market_prepare / _clear on an S = 1 state with
 row_stride / self_schedule / curve_slots) is the same arithmetic, bit for bit."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import scenarios
-from .hip_solver import DeviceLP, default_options
-from .rolling import _NoSolver
+from ._device_loop import _DeviceLoop, _NoSolver, attach_solver
 
 
 def exact_fma(torch, a, b, c):
@@ -132,21 +131,7 @@ class _Model:
             cols, kw, per_kw, template_sum = wind
             self.wind = (idx(cols), float(kw), float(per_kw))
             self.base_c0 -= float(per_kw) * float(template_sum)           # the template's curtailment constant leaves; the window's enters
-        if lp_backend is None:
-            extra = {"recertify_passes": 3} if self.T > 16 else {"recertify_passes": 0, "eps_infeasible": 0.0}     # (as rolling.py)
-            self.opts = default_options(**{**extra, **(getattr(model, "solver_hints", None) or {})})
-            from .hip_solver import DspOptions
-            self.opts_warm, self.opts_first = DspOptions.from_buffer_copy(self.opts), DspOptions.from_buffer_copy(self.opts)
-            if self.T <= 16:                       # hourly LPs: the simplex starts from the previous hour's basis (dsp_options::simplex_warm)
-                self.opts_warm.simplex_warm, self.opts_first.simplex_warm = 1, 2
-            self.dlp = DeviceLP(self.lp, device_index, self.opts) if solved else None      # (parametrized mode never solves its bidding templates)
-            m = max(self.lp.m, 1)
-            self.out = dict(x=torch.zeros((B, n), dtype=torch.float64, device=dev), y=torch.zeros((B, m), dtype=torch.float64, device=dev),
-                            obj=torch.zeros(B, dtype=torch.float64, device=dev), status=torch.zeros(B, dtype=torch.int32, device=dev),
-                            iters=torch.zeros(B, dtype=torch.int32, device=dev), jumps=torch.zeros(B, dtype=torch.int32, device=dev),
-                            flags=torch.zeros(B, dtype=torch.int32, device=dev))
-        else:
-            self.opts, self.dlp, self.out = None, lp_backend(self.lp), None
+        attach_solver(self, B, dev, device_index, getattr(model, "solver_hints", None), lp_backend, solved)      # (solved=False: parametrized mode never solves its bidding templates)
 
     def couple(self, model, S, B, dev, device_index, lp_backend):
         """-> the COUPLED day-ahead model of a self-scheduling batch built on this one-row block model (of `model`, the day-ahead
@@ -172,19 +157,8 @@ class _Model:
         zeros = torch.zeros(Tc, dtype=torch.float64, device=dev)
         cm.rlo = torch.cat([self.rlo[0, :m1].repeat(S), zeros]).repeat(B, 1)
         cm.rhi = torch.cat([self.rhi[0, :m1].repeat(S), zeros]).repeat(B, 1)
-        if lp_backend is None:
-            cm.opts = default_options(**{"recertify_passes": 3, **coupled.solver_hints})      # (a T > 16 model's options)
-            from .hip_solver import DspOptions
-            cm.opts_warm, cm.opts_first = DspOptions.from_buffer_copy(cm.opts), DspOptions.from_buffer_copy(cm.opts)
-            cm.dlp = DeviceLP(cm.lp, device_index, cm.opts)
-            n, m = cm.lp.n, max(cm.lp.m, 1)
-            cm.out = dict(x=torch.zeros((B, n), dtype=torch.float64, device=dev), y=torch.zeros((B, m), dtype=torch.float64, device=dev),
-                          obj=torch.zeros(B, dtype=torch.float64, device=dev), status=torch.zeros(B, dtype=torch.int32, device=dev),
-                          iters=torch.zeros(B, dtype=torch.int32, device=dev), jumps=torch.zeros(B, dtype=torch.int32, device=dev),
-                          flags=torch.zeros(B, dtype=torch.int32, device=dev))
-        else:
-            cm.opts, cm.dlp, cm.out = None, lp_backend(cm.lp), None
-        self.c, self.lb, self.ub = (v.view(B * S, n1) for v in (cm.c, cm.lb, cm.ub))
+        attach_solver(cm, B, dev, device_index, coupled.solver_hints, lp_backend)      # (a day-ahead horizon: a T > 16 model's options)
+        self.c,self.lb, self.ub = (v.view(B * S, n1) for v in (cm.c, cm.lb, cm.ub))
         self.c0 = torch.zeros(B * S, dtype=torch.float64, device=dev)
         return cm
 
@@ -252,10 +226,12 @@ def _per_plant(v, name, B, positive=False, below=None):
     return np.broadcast_to(a, (B,)).copy()
 
 
-def _fill_descriptor(w, m, n_state):
-    """the fields that DspLoopModel and DspLoopMarketModel (hip_solver.py) share, from a _Model: buffers, sizes, the two-term power output
-    (_Model.terms), day-ahead power / wind / state columns, the wind size and the objective constants, per plant where the model
-    carries them (None: the pointers stay NULL, the kernels read the scalars).  Entries past the horizon are -1 / 0."""
+def _describe(cls, m, n_state):
+    """-> the descriptor `cls()` - DspLoopModel or DspLoopMarketModel (hip_solver.py) - of a _Model.  What the two share: buffers, sizes,
+    the two-term power output (_Model.terms), day-ahead power / wind / state columns, the wind size and the objective constants, per
+    plant where the model carries them (None: the pointers stay NULL, the kernels read the scalars).  What only a DspLoopModel has:
+    rows, dispatch rows, the state after period 0.  Entries past the horizon are -1 / 0."""
+    w = cls()
     w.c, w.lb, w.ub, w.base_c, w.x, w.c0 = (t.data_ptr() for t in (m.c, m.lb, m.ub, m.base_c, m.out["x"], m.c0))
     w.status, w.flags = m.out["status"].data_ptr(), m.out["flags"].data_ptr()
     w.n, w.T, w.n_state = getattr(m, "n1", m.lp.n), m.T, n_state      # (a coupled model is described by ONE of its blocks)
@@ -277,6 +253,13 @@ def _fill_descriptor(w, m, n_state):
     w.c0_base = m.base_c0
     if m.kw_plant is not None:
         w.wind_kw_plant, w.c0_base_plant = m.kw_plant.data_ptr(), m.c0_plant.data_ptr()
+    if hasattr(w, "track_rows"):
+        w.rlo, w.rhi, w.m = m.rlo.data_ptr(), m.rhi.data_ptr(), m.lp.m
+        track = m.track_rows.cpu().tolist() if m.track_rows is not None else []
+        for t in range(len(w.track_rows)):
+            w.track_rows[t] = int(track[t]) if t < len(track) else -1
+        for j in range(len(w.state_real)):
+            w.state_real[j] = m.state_real[j] if m.state_real is not None and j < len(m.state_real) else 0
     return w
 
 
@@ -379,7 +362,7 @@ def _objective_constant(model_object, horizon, weighted_family, per_kw, cf):
     return float(const) - float(per_kw) * float(fam["wind_kw"] * float(np.sum(cf[:horizon])))
 
 
-class BatchedDoubleLoop:
+class BatchedDoubleLoop(_DeviceLoop):
     def __init__(self, flowsheet, n_scenarios, device=0, first_scenario=0, day_ahead_horizon=48, tracking_horizon=4, lp_backend=None,
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
                  market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
@@ -426,51 +409,9 @@ class BatchedDoubleLoop:
         self.B = B = int(n_scenarios)
         self.S = S = int(n_price_scenarios)
         self.D = D = int(max_historical_days)
-        if forecaster not in ("perfect", "backcast") or market not in ("stub", "price_taker"):
-            raise ValueError(f"forecaster is 'perfect' or 'backcast' and market 'stub' or 'price_taker', not {forecaster!r} / {market!r}")
-        if forecaster == "backcast" and not 1 <= S <= min(16, D):
-            raise ValueError(f"forecaster='backcast' needs 1 <= n_price_scenarios <= min(16, max_historical_days), not {S} (max_historical_days={D})")
-        if forecaster == "perfect" and S != 1:
-            raise ValueError("forecaster='perfect' knows one price scenario: n_price_scenarios must be 1")
-        if bidder not in ("lp", "parametrized", "self_schedule"):
-            raise ValueError(f"bidder is 'lp', 'parametrized' or 'self_schedule', not {bidder!r}")
-        self.parametrized = bidder == "parametrized"
-        self.self_schedule = bidder == "self_schedule"
-        if self.self_schedule:
-            if ruc_hour is not None:
-                raise ValueError("ruc_hour belongs to bidder='lp': a self-schedule made at the RUC hour on a projected state is a follow-up (DESIGN 9)")
-            sized = [k for k, v in (("wind_mw", wind_mw), ("battery_mw", battery_mw), ("battery_mwh", battery_mwh)) if v is not None]
-            if sized:
-                raise ValueError(f"{', '.join(sized)}: per-plant sizes belong to bidder='lp' (a self-scheduling batch of different plants is a follow-up, DESIGN 9)")
-        if self.parametrized:
-            if flowsheet not in ("wind_pem", "wind_battery"):
-                raise ValueError(f"bidder='parametrized' is the wind + PEM / wind + battery bidders' rule: not for {flowsheet!r}")
-            if S != 1 or forecaster != "perfect":
-                raise ValueError("bidder='parametrized' bids on a perfect forecast: forecaster='perfect', n_price_scenarios=1")
-            if not 1 <= int(tracking_horizon) <= 16:
-                raise ValueError("bidder='parametrized' takes a tracking_horizon of 1 .. 16 periods")
-            for name, v in (("bid_price", bid_price), ("storage_mw", storage_mw)):
-                if v is None:
-                    raise ValueError(f"bidder='parametrized' needs {name}")
-            bid_price, storage_mw = (_per_plant(v, name, B, below=2.0e7) for v, name in ((bid_price, "bid_price"), (storage_mw, "storage_mw")))      # (2e7: the range of the cent arithmetic, bid_curves.cents)
-        elif bid_price is not None or storage_mw is not None:
-            raise ValueError("bid_price and storage_mw belong to bidder='parametrized'")
-        if ruc_hour is not None:
-            if isinstance(ruc_hour, bool) or not isinstance(ruc_hour, (int, np.integer)) or not 1 <= int(ruc_hour) <= 23:
-                raise ValueError(f"ruc_hour is None or an integer hour of the day 1 .. 23, not {ruc_hour!r}")
-            if self.parametrized:
-                raise ValueError("ruc_hour belongs to bidder='lp': a parametrized bid has no bidding LP and no state, nothing to project")
-            ruc_hour = int(ruc_hour)
-        self.ruc_hour = ruc_hour
-        sizes = self._plant_sizes(flowsheet, B, wind_mw, battery_mw, battery_mwh)
-        self.sized = sizes is not None
-        if plant_windows is None:
-            plant_windows = np.arange(B)
-        else:
-            plant_windows = np.asarray(plant_windows)
-            if plant_windows.shape != (B,) or plant_windows.dtype.kind not in "iu":
-                raise ValueError(f"plant_windows is an int array of length {B}")
-            plant_windows = plant_windows.astype(np.int64)
+        bid_price, storage_mw, ruc_hour, sizes, plant_windows = self._validate(
+            forecaster, market, bidder, tracking_horizon, bid_price, storage_mw, ruc_hour, wind_mw, battery_mw, battery_mwh, plant_windows)
+        self.ruc_hour, self.sized = ruc_hour, sizes is not None
         self.forecaster, self.market = forecaster, market
         self.stochastic = forecaster != "perfect" or market != "stub" or self.parametrized or self.self_schedule
         rows = 1 if self.parametrized else B if self.self_schedule else B * S                           # rows of the bidding batches (plant b, scenario i: row b * S + i; no bidding LP is solved in parametrized mode: one template row)
@@ -532,10 +473,13 @@ class BatchedDoubleLoop:
         self.hour = self.solves = 0
         self.use_graphs = bool(use_graphs) and lp_backend is None
         self.simplex_warm = bool(simplex_warm) and lp_backend is None
-        self._graphs, self._warm = {}, False
+        self._graphs, self._warm, self._pending = {}, False, False
         self._da_capturable = None                    # self-schedule: may the coupled day-ahead step be a graph node (day_ahead)
         self.use_fused = bool(use_fused) and lp_backend is None and self.rt.T <= 16 and self.tr.T <= 16 and len(self.scale) <= 2
         self.exact = self.sized or self.parametrized or self.self_schedule    # these state phase 2 of dsp_loop_update exactly, sums included (_hand_off)
+        # what reset() zeroes and what results() reports beyond obj / energy_mwh / state: every setup below adds its own
+        self._zeroed = [self.state, self.revenue, self.energy_mwh, self.delivered, self.da_offer, self.da_prices, self.hour_t, self.uncertified, self.bad]
+        self._result_keys = []
         if self.exact:
             self.tr.set_first_period_terms(dev)
         if self.sized:
@@ -548,13 +492,7 @@ class BatchedDoubleLoop:
                 cols = m.set_terms(dev)
                 if set(cols[cols >= 0].tolist()) & set(m.pda_cols.cpu().tolist()):
                     raise ValueError("a column is both a term of the power output and day_ahead_power: the prices' objective entries would collide")
-            i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
-            # curves (integer cents: power, price; `count` points each) and dispatches of the current day / hour: persistent, like everything a step touches
-            self.da_curve, self.da_count = i32(B, 24, S + 1, 2), i32(B, 24)
-            self.rt_curve, self.rt_count = i32(B, self.tr.T, S + 1, 2), i32(B, self.tr.T)
-            self.rt_dispatch = z(B, self.tr.T)
-            self.da_energy_mwh, self.offered_mwh = z(B), z(B)
-            self._hundred = torch.full((), 100.0, dtype=torch.float64, device=dev)
+            self._market_buffers(S + 1)
         if self.ruc_hour is not None:
             self._ruc_setup(mk(tr_model, B))
         if self.use_fused:
@@ -563,6 +501,75 @@ class BatchedDoubleLoop:
                 self._param_setup()
             elif self.stochastic:
                 self._market_setup()
+        # the mode's day-ahead step, hour step and LP solves per call of day_ahead() / hour_step(), bound once
+        if self.parametrized:
+            self._da_step, self._hour, self._n_da, self._n_hour = self._day_ahead_step_parametrized, self._hour_step_parametrized, 0, B
+        elif self.self_schedule:
+            self._da_step, self._hour, self._n_da, self._n_hour = self._day_ahead_step_self_schedule, self._hour_step_bid, B, 2 * B
+        else:
+            self._da_step = self._day_ahead_step_stochastic if self.stochastic else self._day_ahead_step
+            self._hour = self._hour_step_bid if self.stochastic else self._hour_step
+            self._n_da, self._n_hour = B * S, B * S + B
+
+    # -- setup: buffers, argument checks, per-mode operands, the kernels' descriptors -----------------------------------------------------
+    def _market_buffers(self, slots):
+        """curves (integer cents: power, price; `count` points each, `slots` stored) and dispatches of the current day / hour, and the
+        day's sums: persistent, like everything a step touches"""
+        import torch
+        B, dev, Tc = self.B, self.dev, self.tr.T
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        self.da_curve, self.da_count = i32(B, 24, slots, 2), i32(B, 24)
+        self.rt_curve, self.rt_count = i32(B, Tc, slots, 2), i32(B, Tc)
+        self.rt_dispatch = z(B, Tc)
+        self.da_energy_mwh, self.offered_mwh = z(B), z(B)
+        self._hundred = torch.full((), 100.0, dtype=torch.float64, device=dev)
+        self._zeroed += [self.da_energy_mwh, self.offered_mwh]
+        self._result_keys += ["da_energy_mwh", "offered_mwh"]             # what the market left on the table: offered (the curves' last points) against cleared
+
+    def _validate(self, forecaster, market, bidder, tracking_horizon, bid_price, storage_mw, ruc_hour, wind_mw, battery_mw, battery_mwh, plant_windows):
+        """the arguments' checks that need no template (ValueError; __init__'s docstring) -> the normalised (bid_price, storage_mw,
+        ruc_hour, sizes, plant_windows); sets self.parametrized / self.self_schedule"""
+        flowsheet, B, S = self.flowsheet, self.B, self.S
+        self._check_market_arguments(forecaster, market, S, self.D)
+        if bidder not in ("lp", "parametrized", "self_schedule"):
+            raise ValueError(f"bidder is 'lp', 'parametrized' or 'self_schedule', not {bidder!r}")
+        self.parametrized = bidder == "parametrized"
+        self.self_schedule = bidder == "self_schedule"
+        if self.self_schedule:
+            if ruc_hour is not None:
+                raise ValueError("ruc_hour belongs to bidder='lp': a self-schedule made at the RUC hour on a projected state is a follow-up (DESIGN 9)")
+            sized = [k for k, v in (("wind_mw", wind_mw), ("battery_mw", battery_mw), ("battery_mwh", battery_mwh)) if v is not None]
+            if sized:
+                raise ValueError(f"{', '.join(sized)}: per-plant sizes belong to bidder='lp' (a self-scheduling batch of different plants is a follow-up, DESIGN 9)")
+        if self.parametrized:
+            if flowsheet not in ("wind_pem", "wind_battery"):
+                raise ValueError(f"bidder='parametrized' is the wind + PEM / wind + battery bidders' rule: not for {flowsheet!r}")
+            if S != 1 or forecaster != "perfect":
+                raise ValueError("bidder='parametrized' bids on a perfect forecast: forecaster='perfect', n_price_scenarios=1")
+            if not 1 <= int(tracking_horizon) <= 16:
+                raise ValueError("bidder='parametrized' takes a tracking_horizon of 1 .. 16 periods")
+            for name, v in (("bid_price", bid_price), ("storage_mw", storage_mw)):
+                if v is None:
+                    raise ValueError(f"bidder='parametrized' needs {name}")
+            bid_price, storage_mw = (_per_plant(v, name, B, below=2.0e7) for v, name in ((bid_price, "bid_price"), (storage_mw, "storage_mw")))      # (2e7: the range of the cent arithmetic, bid_curves.cents)
+        elif bid_price is not None or storage_mw is not None:
+            raise ValueError("bid_price and storage_mw belong to bidder='parametrized'")
+        if ruc_hour is not None:
+            if isinstance(ruc_hour, bool) or not isinstance(ruc_hour, (int, np.integer)) or not 1 <= int(ruc_hour) <= 23:
+                raise ValueError(f"ruc_hour is None or an integer hour of the day 1 .. 23, not {ruc_hour!r}")
+            if self.parametrized:
+                raise ValueError("ruc_hour belongs to bidder='lp': a parametrized bid has no bidding LP and no state, nothing to project")
+            ruc_hour = int(ruc_hour)
+        sizes = self._plant_sizes(flowsheet, B, wind_mw, battery_mw, battery_mwh)
+        if plant_windows is None:
+            plant_windows = np.arange(B)
+        else:
+            plant_windows = np.asarray(plant_windows)
+            if plant_windows.shape != (B,) or plant_windows.dtype.kind not in "iu":
+                raise ValueError(f"plant_windows is an int array of length {B}")
+            plant_windows = plant_windows.astype(np.int64)
+        return bid_price, storage_mw, ruc_hour, sizes, plant_windows
 
     def _plant_sizes(self, flowsheet, B, wind_mw, battery_mw, battery_mwh):
         """validated sizes -> dict of float64 arrays [B] (wind_mw; wind_battery: battery_mw, battery_mwh too), or None without sizes"""
@@ -625,7 +632,7 @@ class BatchedDoubleLoop:
     def _parametrized_setup(self, d, bid_price, storage_mw, tr_model, fam):
         import torch
         from .flowsheets import parameters as prm
-        dev, B, Tc = self.dev, self.B, self.tr.T
+        dev = self.dev
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float64), device=dev)
         self.p_min_cents = 0
         self.bid_price, self.storage_mw = t(bid_price), t(storage_mw)
@@ -634,16 +641,12 @@ class BatchedDoubleLoop:
             raise ValueError("the day-ahead capacity factors must cover the series, and the series a day")
         self.wind_mw = float(self.bidder.bidding_model_object._wind_pmax_mw)       # the host bidders' wind_mw
         self.battery = self.flowsheet == "wind_battery"                            # p_max = max(w, storage_mw) (FixedParametrizedBidder)
-        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
-        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
-        self.da_curve, self.da_count = i32(B, 24, 4, 2), i32(B, 24)                # three pairs: at most 3 points in the S + 1 = 4 slots of plant_curves
-        self.rt_curve, self.rt_count = i32(B, Tc, 4, 2), i32(B, Tc)
-        self.rt_dispatch = z(B, Tc)
-        self.da_energy_mwh, self.offered_mwh = z(B), z(B)
-        self._hundred = torch.full((), 100.0, dtype=torch.float64, device=dev)
+        self._market_buffers(4)                                                    # three pairs: at most 3 points in the S + 1 = 4 slots of plant_curves
         self.h2_kg = None
         if self.flowsheet == "wind_pem":                                           # MultiPeriodWindPEM._h2_kg_per_hr of the implemented hour
-            self.h2_kg = z(B)
+            self.h2_kg = torch.zeros(self.B, dtype=torch.float64, device=dev)
+            self._zeroed.append(self.h2_kg)
+            self._result_keys.append("h2_kg")
             self.pem_col = int(getattr(tr_model.block, fam)["periods"][0]["pem_elec"].index)
             self._h2_mul = float(prm.pem_electricity_to_mol)
             self._h2_div = torch.full((), float(prm.h2_mols_per_kg), dtype=torch.float64, device=dev)
@@ -663,27 +666,10 @@ class BatchedDoubleLoop:
             ps.h2_mul, ps.h2_div = self._h2_mul, float(self._h2_div.item())
         self._param_state = ps
 
-    def _param(self, phase, k):
-        import ctypes as C
-        import torch
-        rc = self._lib.dsp_loop_param_step(C.byref(self._param_state), C.byref(self._loop_tr), phase, k,
-                                           C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"dsp_loop_param_step failed ({rc})")
-
     def _fused_setup(self):
         from .hip_solver import DspLoopModel, DspLoopState, load_library
         self._lib = load_library()
-
-        def loop_model(m):                             # + what only a dsp_loop_model has: rows, dispatch rows, the state after period 0
-            w = _fill_descriptor(DspLoopModel(), m, len(self.scale))
-            w.rlo, w.rhi, w.m = m.rlo.data_ptr(), m.rhi.data_ptr(), m.lp.m
-            track = m.track_rows.cpu().tolist() if m.track_rows is not None else []
-            for t in range(len(w.track_rows)):
-                w.track_rows[t] = int(track[t]) if t < len(track) else -1
-            for j in range(len(w.state_real)):
-                w.state_real[j] = m.state_real[j] if m.state_real is not None and j < len(m.state_real) else 0
-            return w
+        loop_model = lambda m: _describe(DspLoopModel, m, len(self.scale))
         st = DspLoopState()
         st.B, st.N = self.B, self.N
         st.start, st.hour = self.start.data_ptr(), self.hour_t.data_ptr()
@@ -724,7 +710,7 @@ class BatchedDoubleLoop:
             setattr(mk, name, getattr(self._loop_state, name))
         mk.p_min_cents = self.p_min_cents
         self._mk_state = mk
-        self._mk_da, self._mk_rt = (_fill_descriptor(DspLoopMarketModel(), m, len(self.scale)) for m in (self.da, self.rt))
+        self._mk_da, self._mk_rt = (_describe(DspLoopMarketModel, m, len(self.scale)) for m in (self.da, self.rt))
         if self.self_schedule:
             # the coupled rows: one block described, blocks S * n1 apart; c0 / status / flags one entry per plant.  Everything but the
             # day-ahead fan-out runs on an S = 1 state (scenario 0 = the most recent backcast day): pairs priced at 0, curves in the
@@ -741,27 +727,33 @@ class BatchedDoubleLoop:
             bid.rt_history_lag_days = 1
             self._mk_bid = bid
 
-    def _market(self, fn, *args, bid=False):
-        import ctypes as C
-        import torch
-        rc = fn(C.byref(self._mk_bid if bid else self._mk_state), *args, C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"{fn.__name__} failed ({rc})")
-
+    # -- the kernels (C ABI, on the current stream: _call) ------------------------------------------------------------------------------
     def _fused(self, phase, k):
         import ctypes as C
-        import torch
-        rc = self._lib.dsp_loop_update(C.byref(self._loop_state), C.byref(self._loop_rt), C.byref(self._loop_tr), phase, k,
-                                       C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"dsp_loop_update failed ({rc})")
+        self._call(self._lib.dsp_loop_update, C.byref(self._loop_state), C.byref(self._loop_rt), C.byref(self._loop_tr), phase, k)
 
-    # -- pieces of a step (all capturable: persistent tensors, the clock read on the device) ---------------------------------------
-    def _window(self, series, T, offset=0):
-        import torch
-        clock = self._clk + offset if offset else self._clk
-        return series[(self.start[:, None] + clock + torch.arange(T, device=self.dev)[None, :]) % self.N]
+    def _param(self, phase, k):
+        import ctypes as C
+        self._call(self._lib.dsp_loop_param_step, C.byref(self._param_state), C.byref(self._loop_tr), phase, k)
 
+    def _project(self, phase, j):
+        import ctypes as C
+        self._call(self._lib.dsp_loop_project, C.byref(self._proj_state_c), C.byref(self._loop_pj), phase, j)
+
+    def _market_prepare(self, m, k, bid=False):
+        """objective, bounds, state and constant of bidding model m's rows at hour k of the day (-1: the day-ahead bid; bid: the one
+        made at the RUC hour)"""
+        import ctypes as C
+        self._call(self._lib.dsp_loop_market_prepare, C.byref(self._mk_bid if bid else self._mk_state), C.byref(m), k)
+
+    def _market_clear(self, m, tr, k, T, dispatch, curve, count, bid=False):
+        """curves of the T periods from m's solution, cleared into `dispatch` (status / flags of the solve: folded into bad / uncertified
+        by the kernel); tr: the tracker whose LP the clearing lanes also write, or None"""
+        import ctypes as C
+        self._call(self._lib.dsp_loop_market_clear, C.byref(self._mk_bid if bid else self._mk_state), C.byref(m), None if tr is None else C.byref(tr), k, T,
+                   *(C.c_void_p(v.data_ptr()) for v in (dispatch, curve, count)))
+
+    # -- pieces of a step (all capturable: persistent tensors, the clock read on the device; windows, curves, clearing: _DeviceLoop) ------
     def _set_prices(self, m, da, rt):
         """c = base - RT . dP_T/dx - (DA - RT) on day_ahead_power ; c0 = base - RT . PT_const (Bidder._pass_price_forecasts)"""
         m.c.copy_(m.base_c - rt @ m.PT)
@@ -786,18 +778,13 @@ class BatchedDoubleLoop:
             m.ub[:, cols] = avail
             m.c0 += per_kw * avail.sum(1)
 
-    def _check(self, out):
-        self.bad |= (out["status"] != 0).any()
-        if out.get("flags") is not None:
-            self.uncertified += ((out["flags"] & 1) != 0).sum()
-
+    # -- the deterministic loop: perfect forecast, stub market ----------------------------------------------------------------------------
     def _day_ahead_step(self, bid=False):
         """bid: the bid made at the RUC hour for the next day (clock and state are the bid's, self._clk / self._st; the pending buffers)"""
         m = self.da
         da, rt = self._window(self.da_series, m.T), self._window(self.rt_series, m.T)
         self._set_state(m, self._set_prices(m, da, rt))
-        m.lb.index_fill_(1, m.pda_cols, 0.0)
-        m.ub.index_fill_(1, m.pda_cols, float("inf"))
+        self._free_day_ahead_power(m)
         out = m.solve(self.B)
         self._check(out)
         (self.pend_offer if bid else self.da_offer).copy_(out["x"][:, m.pda_cols][:, :24])
@@ -818,12 +805,9 @@ class BatchedDoubleLoop:
         known = min(m.T, 24 - k)                                          # hours of the horizon inside the cleared day
         da[:, :known] = self.da_prices[:, k:k + known]
         self._set_state(m, self._set_prices(m, da, rt))
-        m.lb.index_fill_(1, m.pda_cols, 0.0)
-        m.ub.index_fill_(1, m.pda_cols, float("inf"))
-        m.lb[:, m.pda_cols[:known]] = self.da_offer[:, k:k + known]
-        m.ub[:, m.pda_cols[:known]] = self.da_offer[:, k:k + known]
+        self._free_day_ahead_power(m, k)
         hour = k if self.simplex_warm else None
-        out = m.solve(self.B, hour=hour) if m.opts is not None else m.solve(self.B)
+        out = m.solve(self.B, hour=hour)
         self._check(out)
         offer = m.power_output(out["x"])                                  # real-time offer = SCED dispatch in the stub market
         tr = self.tr
@@ -831,7 +815,7 @@ class BatchedDoubleLoop:
         rhs = offer[:, :tr.T] - tr.PT_const
         tr.rlo[:, tr.track_rows] = rhs
         tr.rhi[:, tr.track_rows] = rhs
-        out = tr.solve(self.B, hour=hour) if tr.opts is not None else tr.solve(self.B)
+        out = tr.solve(self.B, hour=hour)
         self._check(out)
         self._hand_off(out["x"], rt[:, 0], k, exact=False)
 
@@ -857,26 +841,6 @@ class BatchedDoubleLoop:
         self.hour_t += 1
 
     # -- stochastic mode: backcast scenarios, bid curves from p_min, market clearing (semantics: rolling.py, generalised over the descriptor) --
-    def _forecast(self, series, T, hod, lag_days=0):
-        """[B, S, T] price scenarios asked at hour-of-day `hod` of the current day: Backcaster._forecast over the D whole days before
-        the current day of every plant's own circular series (rolling.py::_forecast).  lag_days: the history ends that many days
-        earlier (the real-time prices of a bid made at the RUC hour)"""
-        import torch
-        if self.forecaster == "perfect":
-            return self._window(series, T)[:, None, :]
-        D = self.D
-        d = torch.div(self._clk, 24, rounding_mode="floor")
-        if lag_days:
-            d = d - lag_days
-        i, t = torch.arange(self.S, device=self.dev)[:, None], torch.arange(T, device=self.dev)[None, :]
-        pos = (24 * (D - 1 - i) + hod + t) % (24 * D)
-        return series[(self.start[:, None, None] + 24 * (d - D) + pos[None]) % self.N]
-
-    def _rows(self, v, m=None):
-        """per-plant values [B, ...] -> per-row [B * S, ...] (a plant's S rows are adjacent; m.per_plant: that model's rows per plant)"""
-        per = self.S if m is None or m.per_plant is None else m.per_plant
-        return v if per == 1 else v.repeat_interleave(per, dim=0)
-
     def _avail(self, m, offset=0):
         """wind availability of the window [B, T] and its sum accumulated in the order of t (the kernels' order: bit-identical constants)"""
         cols, _, per_kw = m.wind
@@ -929,108 +893,85 @@ class BatchedDoubleLoop:
         else:
             m.c0.fill_(m.base_c0)
 
-    def _curves(self, power, price, status):
-        """power, price [B, S, Tc]; status [B * S] -> (U, M [S + 1, B * Tc] int64 cents, count [B * Tc]) - workflow/market.py::plant_curves"""
-        import torch
-        from .workflow.market import plant_curves
-        B, S, Tc = power.shape
-        lanes = lambda a: a.expand(B, S, Tc).permute(1, 0, 2).reshape(S, B * Tc)
-        return plant_curves(torch, lanes(power), lanes(price), lanes((status == 0).reshape(B, S, 1)), p_min_cents=self.p_min_cents)
+    def _day_ahead_buffers(self, bid=False):
+        """(offer, curve, count, prices) a day-ahead step writes: the current day's, or - the bid made at the RUC hour - the pending ones"""
+        if bid:
+            return self.pend_offer, self.pend_curve, self.pend_count, self.pend_prices
+        return self.da_offer, self.da_curve, self.da_count, self.da_prices
 
-    def _clear(self, U, M, count, lmp):
-        import torch
-        from .workflow.market import clear_curves
-        return clear_curves(torch, U, M, count, lmp.reshape(-1), self._hundred, price_taker=self.market == "price_taker").reshape(lmp.shape)
-
-    def _store_curves(self, curve, cnt, U, M, count):
-        import torch
-        B, Tc, slots, _ = curve.shape
-        if U.shape[0] < slots:                        # (a self-schedule's one-pair curve in the loop's S + 1 slots: the rest stays 0)
-            pad = torch.zeros((slots - U.shape[0], U.shape[1]), dtype=U.dtype, device=U.device)
-            U, M = torch.cat([U, pad]), torch.cat([M, pad])
-        curve.copy_(torch.stack([U.t().reshape(B, Tc, slots), M.t().reshape(B, Tc, slots)], dim=3))
-        cnt.copy_(count.reshape(B, Tc))
+    def _day_ahead_market(self, curves=None, bid=False):
+        """the tail of every day-ahead step with curves: (U, M, count) of the day's 24 hours cleared at the realised day-ahead price and
+        stored (None: the kernels have done that), then the day's sums - which, for a pending bid, wait for midnight"""
+        if curves is not None:
+            offer, curve, cnt, prices = self._day_ahead_buffers(bid)
+            realised = self._window(self.da_series, 24)
+            offer.copy_(self._clear(*curves, realised))
+            prices.copy_(realised)
+            self._store_curves(curve, cnt, *curves)
+        if not bid:
+            self._account_day_ahead()
 
     def _day_ahead_step_stochastic(self, bid=False):
         """B * S day-ahead LPs (row b * S + i on scenario i's prices, plant b's state and wind, day_ahead_power free), one curve per
         plant-hour from the S day_ahead_power values and day-ahead forecasts, cleared at the realised day-ahead price.
         bid: the bid made at the RUC hour for the next day - clock and state are the bid's (self._clk / self._st), the real-time
         history is one day older, and offers, prices, curves and counts go to the pending buffers; the day's sums wait for midnight"""
-        import ctypes as C
-        import torch
         m, B, S = self.da, self.B, self.S
-        offer, prices = (self.pend_offer, self.pend_prices) if bid else (self.da_offer, self.da_prices)
-        curve, count_ = (self.pend_curve, self.pend_count) if bid else (self.da_curve, self.da_count)
         if self.use_fused:
-            self._market(self._lib.dsp_loop_market_prepare, C.byref(self._mk_da), -1, bid=bid)
-        else:
-            da = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T)
-            rt = self._forecast(self.rt_series, m.T, 0, lag_days=int(bid)).expand(B, S, m.T)
-            self._set_rows(m, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
-            m.lb.index_fill_(1, m.pda_cols, 0.0)
-            m.ub.index_fill_(1, m.pda_cols, float("inf"))
+            self._market_prepare(self._mk_da, -1, bid)
+            m.solve(B * S)
+            self._market_clear(self._mk_da, None, -1, 24, *self._day_ahead_buffers(bid)[:3], bid=bid)
+            return self._day_ahead_market(None, bid)
+        da = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T)
+        rt = self._forecast(self.rt_series, m.T, 0, lag_days=int(bid)).expand(B, S, m.T)
+        self._set_rows(m, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
+        self._free_day_ahead_power(m)
         out = m.solve(B * S)
-        if self.use_fused:                            # (status / flags of the solve: folded into bad / uncertified by the kernel)
-            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_da), None, -1, 24, C.c_void_p(offer.data_ptr()),
-                         C.c_void_p(curve.data_ptr()), C.c_void_p(count_.data_ptr()), bid=bid)
-        else:
-            self._check(out)
-            power = out["x"][:, m.pda_cols[:24]].reshape(B, S, 24)
-            U, M, count = self._curves(power, self._forecast(self.da_series, 24, 0), out["status"])
-            realised = self._window(self.da_series, 24)
-            offer.copy_(self._clear(U, M, count, realised))
-            prices.copy_(realised)
-            self._store_curves(curve, count_, U, M, count)
-        if not bid:
-            self._account_day_ahead()
+        self._check(out)
+        power = out["x"][:, m.pda_cols[:24]].reshape(B, S, 24)
+        self._day_ahead_market(self._curves(power, self._forecast(self.da_series, 24, 0), out["status"]), bid)
 
-    def _account_day_ahead(self):
-        """the day's sums of the bid that is current: cleared and offered day-ahead energy (ruc_hour: when the bid BECOMES current)"""
+    def _hour_step_bid(self, k):
+        """Hour k of the day with a bidding LP and a curve - the stochastic mode's B * S real-time LPs, or the B of a self-schedule,
+        which bids on scenario 0 alone (the most recent backcast day; inside the cleared day the coupled hourly problem separates):
+        scenario i = the real-time backcast at hour-of-day k; realised day-ahead prices and the cleared day_ahead_power inside the cleared
+        day; one curve per plant and tracked period from the pairs (P_T, real-time forecast) - a schedule: the one pair (P_T, 0) -,
+        cleared at the realised price for the hour at hand and at scenario 0's forecast for the look-ahead periods; tracking of the
+        cleared dispatch (B LPs); state hand-off, revenue and clock as _hour_step."""
         import torch
-        self.da_energy_mwh += self.da_offer.sum(1)
-        last = torch.gather(self.da_curve[:, :, :, 0], 2, (self.da_count.to(torch.int64) - 1)[:, :, None])[:, :, 0]
-        self.offered_mwh += (last.to(torch.float64) / self._hundred).sum(1)
-
-    def _hour_step_stochastic(self, k):
-        """Hour k of the day: B * S real-time LPs (scenario i = the real-time backcast at hour-of-day k; realised day-ahead prices and the
-        cleared day_ahead_power inside the cleared day), one curve per plant and tracked period from (P_T, real-time forecast), cleared
-        at the realised price for the hour at hand and at scenario 0's forecast for the look-ahead periods; tracking of the cleared
-        dispatch (B LPs); state hand-off, revenue and clock as _hour_step."""
-        import ctypes as C
-        import torch
-        m, tr, B, S = self.rt, self.tr, self.B, self.S
+        m, tr, B = self.rt, self.tr, self.B
+        per = m.per_plant or self.S                                       # rows per plant
         hour = k if self.simplex_warm else None
         if self.use_fused:
-            self._market(self._lib.dsp_loop_market_prepare, C.byref(self._mk_rt), k)
-            m.solve(B * S, hour=hour)
-            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_rt), C.byref(self._loop_tr), k, tr.T, C.c_void_p(self.rt_dispatch.data_ptr()),
-                         C.c_void_p(self.rt_curve.data_ptr()), C.c_void_p(self.rt_count.data_ptr()))
+            self._market_prepare(self._mk_rt, k)
+            m.solve(B * per, hour=hour)
+            self._market_clear(self._mk_rt, self._loop_tr, k, tr.T, self.rt_dispatch, self.rt_curve, self.rt_count)
             tr.solve(B, hour=hour)
             self._fused(2, k)                         # delivered power, state hand-off, revenue, energy, clock: unchanged (reads the tracker only)
             return
-        rt_f = self._forecast(self.rt_series, m.T, k).expand(B, S, m.T)
-        da_f = self._forecast(self.da_series, m.T, k).expand(B, S, m.T).clone()
+        rt_f = self._forecast(self.rt_series, m.T, k)[:, :per].expand(B, per, m.T)
+        da_f = self._forecast(self.da_series, m.T, k)[:, :per].expand(B, per, m.T).clone()
         known = min(m.T, 24 - k)                                          # hours of the horizon inside the cleared day
         da_f[:, :, :known] = self.da_prices[:, None, k:k + known]
-        self._set_rows(m, da_f.reshape(B * S, m.T), rt_f.reshape(B * S, m.T))
-        m.lb.index_fill_(1, m.pda_cols, 0.0)
-        m.ub.index_fill_(1, m.pda_cols, float("inf"))
-        m.lb[:, m.pda_cols[:known]] = self._rows(self.da_offer[:, k:k + known])
-        m.ub[:, m.pda_cols[:known]] = self._rows(self.da_offer[:, k:k + known])
-        out = m.solve(B * S, hour=hour) if m.opts is not None else m.solve(B * S)
+        self._set_rows(m, da_f.reshape(B * per, m.T), rt_f.reshape(B * per, m.T))
+        self._free_day_ahead_power(m, k, per)
+        out = m.solve(B * per, hour=hour)
         self._check(out)
         x, Tc = out["x"], tr.T
         power = (x[:, m.pt_a[:Tc]] * m.pt_ca[:Tc] + x[:, m.pt_b[:Tc]] * m.pt_cb[:Tc]) + m.PT_const[:Tc]      # two-term elementwise form, not a matmul
-        U, M, count = self._curves(power.reshape(B, S, Tc), rt_f[:, :, :Tc], out["status"])
+        if self.self_schedule:
+            U, M, count = self._schedule_curves(power, out["status"])
+        else:
+            U, M, count = self._curves(power.reshape(B, per, Tc), rt_f[:, :, :Tc], out["status"])
         rt0 = self._window(self.rt_series, 1)
         self.rt_dispatch.copy_(self._clear(U, M, count, torch.cat([rt0, rt_f[:, 0, 1:Tc]], dim=1)))
         self._store_curves(self.rt_curve, self.rt_count, U, M, count)
         self._set_tracker()
-        out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
+        out = tr.solve(B, hour=hour)
         self._check(out)
         self._hand_off(out["x"], rt0[:, 0], k, exact=self.exact)
 
-    # -- self-scheduling: one coupled day-ahead LP per plant, the schedule offered at cost 0 (module docstring) ----------------------------
+    # -- self-scheduling: one coupled day-ahead LP per plant, the schedule offered at cost 0 (module docstring); its hours: _hour_step_bid --
     def _schedule_curves(self, power, status):
         """power [B, Tc] MW, status [B] -> the curves of the ONE pair (power, 0 $/MWh) per plant and period (plant_curves with S = 1)"""
         import torch
@@ -1041,74 +982,24 @@ class BatchedDoubleLoop:
         (what _set_rows gives row b * S + i), tied by the static coupling rows; c0[b] = sum_i c0(b, i) in the order of i.  The
         schedule - block 0's day_ahead_power - is offered at cost 0 and cleared at the realised day-ahead price."""
         import ctypes as C
-        import torch
         m, blk, B, S = self.da, self.da_block, self.B, self.S
         if self.use_fused:
-            rc = self._lib.dsp_loop_schedule_prepare(C.byref(self._mk_sched), C.byref(self._mk_da), C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"dsp_loop_schedule_prepare failed ({rc})")
-        else:
-            da = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T)
-            rt = self._forecast(self.rt_series, m.T, 0).expand(B, S, m.T)
-            self._set_rows(blk, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
-            blk.lb.index_fill_(1, m.pda_cols, 0.0)
-            blk.ub.index_fill_(1, m.pda_cols, float("inf"))
-            each = blk.c0.view(B, S)
-            total = each[:, 0]
-            for i in range(1, S):
-                total = total + each[:, i]
-            m.c0.copy_(total)
+            self._call(self._lib.dsp_loop_schedule_prepare, C.byref(self._mk_sched), C.byref(self._mk_da))
+            m.solve(B)
+            self._market_clear(self._mk_da, None, -1, 24, *self._day_ahead_buffers()[:3])
+            return self._day_ahead_market()
+        da = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T)
+        rt = self._forecast(self.rt_series, m.T, 0).expand(B, S, m.T)
+        self._set_rows(blk, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
+        self._free_day_ahead_power(blk)
+        each = blk.c0.view(B, S)
+        total = each[:, 0]
+        for i in range(1, S):
+            total = total + each[:, i]
+        m.c0.copy_(total)
         out = m.solve(B)
-        if self.use_fused:
-            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_da), None, -1, 24, C.c_void_p(self.da_offer.data_ptr()),
-                         C.c_void_p(self.da_curve.data_ptr()), C.c_void_p(self.da_count.data_ptr()))
-        else:
-            self._check(out)
-            U, M, count = self._schedule_curves(out["x"][:, m.pda_cols[:24]], out["status"])      # (block 0: the block-relative columns)
-            realised = self._window(self.da_series, 24)
-            self.da_offer.copy_(self._clear(U, M, count, realised))
-            self.da_prices.copy_(realised)
-            self._store_curves(self.da_curve, self.da_count, U, M, count)
-        self._account_day_ahead()
-
-    def _hour_step_self_schedule(self, k):
-        """Hour k of the day: B real-time LPs on scenario 0 (the most recent backcast day; realised day-ahead prices and the cleared
-        day_ahead_power inside the cleared day - where the coupled hourly problem separates), the one-pair curve (P_T[t], 0) per
-        tracked period cleared at the realised price (t = 0) / scenario 0's forecast (t >= 1); tracking, hand-off, revenue, clock as
-        _hour_step_stochastic."""
-        import ctypes as C
-        import torch
-        m, tr, B = self.rt, self.tr, self.B
-        hour = k if self.simplex_warm else None
-        if self.use_fused:
-            self._market(self._lib.dsp_loop_market_prepare, C.byref(self._mk_rt), k)
-            m.solve(B, hour=hour)
-            self._market(self._lib.dsp_loop_market_clear, C.byref(self._mk_rt), C.byref(self._loop_tr), k, tr.T, C.c_void_p(self.rt_dispatch.data_ptr()),
-                         C.c_void_p(self.rt_curve.data_ptr()), C.c_void_p(self.rt_count.data_ptr()))
-            tr.solve(B, hour=hour)
-            self._fused(2, k)
-            return
-        rt_f = self._forecast(self.rt_series, m.T, k)[:, 0].expand(B, m.T)
-        da_f = self._forecast(self.da_series, m.T, k)[:, 0].expand(B, m.T).clone()
-        known = min(m.T, 24 - k)                                          # hours of the horizon inside the cleared day
-        da_f[:, :known] = self.da_prices[:, k:k + known]
-        self._set_rows(m, da_f, rt_f)
-        m.lb.index_fill_(1, m.pda_cols, 0.0)
-        m.ub.index_fill_(1, m.pda_cols, float("inf"))
-        m.lb[:, m.pda_cols[:known]] = self.da_offer[:, k:k + known]
-        m.ub[:, m.pda_cols[:known]] = self.da_offer[:, k:k + known]
-        out = m.solve(B, hour=hour) if m.opts is not None else m.solve(B)
         self._check(out)
-        x, Tc = out["x"], tr.T
-        power = (x[:, m.pt_a[:Tc]] * m.pt_ca[:Tc] + x[:, m.pt_b[:Tc]] * m.pt_cb[:Tc]) + m.PT_const[:Tc]      # two-term elementwise form, not a matmul
-        U, M, count = self._schedule_curves(power, out["status"])
-        rt0 = self._window(self.rt_series, 1)
-        self.rt_dispatch.copy_(self._clear(U, M, count, torch.cat([rt0, rt_f[:, 1:Tc]], dim=1)))
-        self._store_curves(self.rt_curve, self.rt_count, U, M, count)
-        self._set_tracker()
-        out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
-        self._check(out)
-        self._hand_off(out["x"], rt0[:, 0], k, exact=True)
+        self._day_ahead_market(self._schedule_curves(out["x"][:, m.pda_cols[:24]], out["status"]))      # (block 0: the block-relative columns)
 
     # -- parametrized mode: two-tier closed-form curves (workflow/parametrized_bidder.py), no bidding LP ---------------------------------
     def _param_curves(self, cf):
@@ -1129,13 +1020,8 @@ class BatchedDoubleLoop:
         """one curve per plant-hour from the day-ahead capacity factors, cleared at the realised day-ahead price; no LP"""
         if self.use_fused:
             self._param(0, -1)
-        else:
-            U, M, count = self._param_curves(self._window(self.da_cf_series, 24))
-            realised = self._window(self.da_series, 24)
-            self.da_offer.copy_(self._clear(U, M, count, realised))
-            self.da_prices.copy_(realised)
-            self._store_curves(self.da_curve, self.da_count, U, M, count)
-        self._account_day_ahead()
+            return self._day_ahead_market()
+        self._day_ahead_market(self._param_curves(self._window(self.da_cf_series, 24)))
 
     def _param_dispatch(self, k):
         """the first half of hour k: curves of the tracked periods, their clearing, and the tracker's LP on the cleared dispatch"""
@@ -1164,7 +1050,7 @@ class BatchedDoubleLoop:
         tr, B = self.tr, self.B
         hour = k if self.simplex_warm else None
         self._param_dispatch(k)
-        out = tr.solve(B, hour=hour) if tr.opts is not None else tr.solve(B)
+        out = tr.solve(B, hour=hour)
         self._param_hydrogen(k)
         if self.use_fused:
             self._fused(2, k)                         # delivered power, state hand-off, revenue, energy, clock: unchanged (reads the tracker only)
@@ -1172,20 +1058,6 @@ class BatchedDoubleLoop:
         self._check(out)
         self._hand_off(out["x"], self._window(self.rt_series, 1)[:, 0], k, exact=True)
 
-    def _run(self, key, fn):
-        import torch
-        if not self.use_graphs or not self._warm:
-            fn()
-            return
-        g = self._graphs.get(key)
-        if g is None:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
-            self._graphs[key] = g
-        g.replay()
-
-    # -- the loop ----------------------------------------------------------------------------------------------------------------------
     # -- bidding at the RUC hour (ruc_hour=H): projection tracker, pending bid, activation at midnight ----------------------------------
     def _ruc_setup(self, pj):
         """the projection tracker (a _Model of its own on the tracker's template: own buffers, own handle, own simplex basis - the
@@ -1201,17 +1073,10 @@ class BatchedDoubleLoop:
         self.proj_state, self.proj_real, self.proj_obj = z(L + 1, B, ns), z(L, B, ns), z(L, B)
         self.pend_offer, self.pend_prices = z(B, 24), z(B, 24)
         self.bid_hour_t = torch.zeros((), dtype=torch.int64, device=dev)   # the bid clock: hour 0 of the day the pending bid is for
+        self._zeroed += [self.proj_state, self.proj_real, self.proj_obj, self.pend_offer, self.pend_prices, self.bid_hour_t]
         if self.stochastic:
             self.pend_curve, self.pend_count = torch.zeros_like(self.da_curve), torch.zeros_like(self.da_count)
-        self._pending = False
-
-    def _project(self, phase, j):
-        import ctypes as C
-        import torch
-        rc = self._lib.dsp_loop_project(C.byref(self._proj_state_c), C.byref(self._loop_pj), phase, j,
-                                        C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"dsp_loop_project failed ({rc})")
+            self._zeroed += [self.pend_curve, self.pend_count]
 
     def _project_write(self, j):
         """the projection tracker's LP of chain step j (the window that starts at clock + j): dispatch rows inside the day on the
@@ -1253,15 +1118,12 @@ class BatchedDoubleLoop:
             for j in range(24 - H):
                 self._project_write(j)
                 hour = (0 if j == 0 else 1) if self.simplex_warm else None         # step 0 from the slack basis, then from the step before
-                out = pj.solve(B, hour=hour) if pj.opts is not None else pj.solve(B)
+                out = pj.solve(B, hour=hour)
                 self._project_hand_off(j, out)
         torch.add(self.hour_t, 24 - H, out=self.bid_hour_t)
         self._clk, self._st = self.bid_hour_t, self.proj_state[-1]
         try:
-            if self.stochastic:
-                self._day_ahead_step_stochastic(bid=True)
-            else:
-                self._day_ahead_step(bid=True)
+            self._da_step(bid=True)
         finally:
             self._clk, self._st = self.hour_t, self.state
 
@@ -1278,79 +1140,47 @@ class BatchedDoubleLoop:
         if self.stochastic:
             self._account_day_ahead()
 
+    # -- the loop (run_day: _DeviceLoop; the mode's steps and solve counts were bound by __init__) -------------------------------------------
     def day_ahead(self):
         self.day_start = self.hour
-        if self.ruc_hour is not None and self._pending:                    # day d >= 1: nothing to solve, yesterday's bid takes over
+        if self._pending:                              # ruc_hour, day d >= 1: nothing to solve, yesterday's bid takes over
             self._run("activate", self._activate)
             self._pending = False
             return self.da_offer.clone()
-        if self.parametrized:
-            self._run("da", self._day_ahead_step_parametrized)
-            return self.da_offer.clone()
-        if self.self_schedule:
-            # A coupled LP beyond the register / LDS-resident kernels (wind + battery: 582 columns, 408 rows at 24 h) runs in the solver's
-            # HBM-resident streaming form, which is driven from the host (it polls the scenarios' completion between check periods): it
-            # cannot be a node of a captured graph, and the step stays eager, once per simulated day.  A coupled LP that stays in the
-            # fused kernels (nuclear, wind + PEM at S = 3) is captured and replayed like the stochastic mode's.  Which of the two a handle
-            # is, the first - eager - day's solve reports (dsp_stats::streaming).
-            if self._da_capturable is None and self._warm:
-                self._da_capturable = self.use_graphs and not self.da.dlp.last_stats.streaming
-            if self._da_capturable:
-                self._run("da", self._day_ahead_step_self_schedule)
-            else:
-                self._day_ahead_step_self_schedule()
-            self.solves += self.B
-            return self.da_offer.clone()
-        self._run("da", self._day_ahead_step_stochastic if self.stochastic else self._day_ahead_step)
-        self.solves += self.B * self.S
+        # A self-schedule's coupled LP beyond the register / LDS-resident kernels (wind + battery: 582 columns, 408 rows at 24 h) runs in
+        # the solver's HBM-resident streaming form, which is driven from the host (it polls the scenarios' completion between check
+        # periods): it cannot be a node of a captured graph, and the step stays eager, once per simulated day.  A coupled LP that stays
+        # in the fused kernels (nuclear, wind + PEM at S = 3) is captured and replayed like the stochastic mode's.  Which of the two a
+        # handle is, the first - eager - day's solve reports (dsp_stats::streaming).
+        if self.self_schedule and self._da_capturable is None and self._warm:
+            self._da_capturable = self.use_graphs and not self.da.dlp.last_stats.streaming
+        if self.self_schedule and not self._da_capturable:
+            self._da_step()
+        else:
+            self._run("da", self._da_step)
+        self.solves += self._n_da
         return self.da_offer.clone()
 
     def hour_step(self):
         k = self.hour - self.day_start
-        if self.parametrized:
-            self._run(k, lambda: self._hour_step_parametrized(k))
-            self.solves += self.B
-        elif self.self_schedule:
-            self._run(k, lambda: self._hour_step_self_schedule(k))
-            self.solves += 2 * self.B
+        if k == self.ruc_hour:                         # the projection chain and tomorrow's bid in front of this hour's step
+            self._run(k, lambda: (self._ruc_step(), self._hour(k)))
+            self.solves += self._n_da + (self.B * (24 - k) if len(self.scale) else 0)
+            self._pending = True
         else:
-            step = (lambda: self._hour_step_stochastic(k)) if self.stochastic else (lambda: self._hour_step(k))
-            if k == self.ruc_hour:
-                self._run(k, lambda: (self._ruc_step(), step()))
-                self.solves += self.B * self.S + (self.B * (24 - k) if len(self.scale) else 0)
-                self._pending = True
-            else:
-                self._run(k, step)
-            self.solves += self.B * self.S + self.B
+            self._run(k, lambda: self._hour(k))
+        self.solves += self._n_hour
         self.hour += 1
         return self.delivered.clone()
 
-    def run_day(self):
-        self.day_ahead()
-        for _ in range(24):
-            self.hour_step()
-        self._warm = True
-
     def reset(self):
-        for t in (self.state, self.revenue, self.energy_mwh, self.delivered, self.da_offer, self.da_prices, self.hour_t, self.uncertified):
+        for t in self._zeroed:
             t.zero_()
-        self.bad.zero_()
-        if self.stochastic:
-            self.da_energy_mwh.zero_(), self.offered_mwh.zero_()
-        if self.parametrized and self.h2_kg is not None:
-            self.h2_kg.zero_()
-        if self.ruc_hour is not None:
-            for t in (self.proj_state, self.proj_real, self.proj_obj, self.pend_offer, self.pend_prices, self.bid_hour_t):
-                t.zero_()
-            if self.stochastic:
-                self.pend_curve.zero_(), self.pend_count.zero_()
-            self._pending = False
+        self._pending = False
         self.hour = self.solves = 0
 
     def results(self):
         res = dict(obj=self.revenue, energy_mwh=self.energy_mwh, state=self.state)
-        if self.stochastic:                            # what the market left on the table: offered (the curves' last points) against cleared
-            res.update(da_energy_mwh=self.da_energy_mwh, offered_mwh=self.offered_mwh)
-        if self.parametrized and self.h2_kg is not None:
-            res["h2_kg"] = self.h2_kg
+        res.update((key, getattr(self, key)) for key in self._result_keys)
         return res, not bool(self.bad.item())
+
