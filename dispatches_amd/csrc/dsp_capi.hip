@@ -454,6 +454,7 @@ static bool loop_market_state_ok(const dsp_loop_market_state *st) {
   if (st->rt_history_lag_days < 0 || (st->backcast && 24ll * ((long long)st->D + st->rt_history_lag_days) > st->N)) return false;      // (ABI 17)
   if (st->self_schedule < 0 || st->self_schedule > 1) return false;                                                                     // (ABI 18)
   if (st->curve_slots != 0 && (st->curve_slots < st->S + 1 || st->curve_slots > DSP_MARKET_MAX_S + 1)) return false;
+  if (st->coupled < 0 || st->coupled > 1 || (st->coupled && st->self_schedule)) return false;                                           // (ABI 19)
   return st->start && st->hour && st->da_series && st->rt_series;
 }
 static bool loop_market_model_ok(const dsp_loop_market_model *m) {
@@ -488,9 +489,23 @@ int dsp_loop_schedule_prepare(const dsp_loop_market_state *st, const dsp_loop_ma
   return DSP_OK;
 }
 
+// the coupled day-ahead LP of a plant that bids a monotone curve (ABI 19): the blocks as above, and the bounds of the P T ordered-pair
+// rows [first_coupling_row, first_coupling_row + P T) of rlo / rhi [B][m_rows], P = S (S - 1) / 2
+int dsp_loop_monotone_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, double *rlo, double *rhi, int32_t m_rows,
+                              int32_t first_coupling_row, void *hipStream) {
+  if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || !rlo || !rhi || st->S < 2 || first_coupling_row < 0) return DSP_ERR_INVALID;
+  if ((long long)m->row_stride < (long long)st->S * m->n) return DSP_ERR_INVALID;
+  if ((long long)first_coupling_row + (long long)(st->S * (st->S - 1) / 2) * m->T > (long long)m_rows) return DSP_ERR_INVALID;
+  if (!loop_market_prepare_ok(st, m) || m->wind_kw_plant || m->c0_base_plant) return DSP_ERR_INVALID;
+  if (st->B == 0) return DSP_OK;
+  HIP_TRY(launch_loop_monotone_prepare(*st, *m, rlo, rhi, (int)m_rows, (int)first_coupling_row, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
 int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market_model *m, const dsp_loop_model *tr, int32_t k, int32_t T,
                           double *dispatch, int32_t *curve, int32_t *count, void *hipStream) {
   if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < -1 || k > 23 || T < 1 || T > m->T) return DSP_ERR_INVALID;
+  if (st->coupled && (long long)m->row_stride < (long long)st->S * m->n) return DSP_ERR_INVALID;      // (ABI 19: the S blocks of a row)
   if (!m->x || !m->status || !dispatch || !curve || !count) return DSP_ERR_INVALID;
   if (k < 0 ? (T > 24 || !st->da_prices || tr) : T > DSP_LOOP_MAX_T) return DSP_ERR_INVALID;
   if (!plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return DSP_ERR_INVALID;

@@ -15,8 +15,12 @@
 //                           pass over the sorted registers, which also clears the curve at the price that occurs.
 //
 //   loop_schedule_prepare_kernel   the coupled day-ahead LP of a self-scheduling plant (dsp_loop_schedule_prepare): S scenario blocks in
-//                           ONE row per plant, one lane per (plant, scenario), the row's constant summed in the order of i by one lane.
-//                           A block is written once, by lmk_write_block, for this kernel and for loop_market_prepare_kernel.
+//                           ONE row per plant, one lane per (plant, scenario), the row's constant summed in the order of i by one lane
+//                           (lmk_coupled_block).  A block is written once, by lmk_write_block, for every prepare kernel of the loop.
+//   loop_monotone_prepare_kernel   the coupled day-ahead LP of a plant whose bid curve is monotone across its scenarios
+//                           (dsp_loop_monotone_prepare, idaes' Bidder): the same blocks through the same lmk_coupled_block, and the
+//                           bounds of the S (S - 1) / 2 * T ordered-pair rows from the order of the day-ahead scenario prices, one lane
+//                           per (plant, pair, period).  The clearing reads such a row with dsp_loop_market_state::coupled = 1.
 //   loop_market_prepare_kernel / loop_market_clear_kernel   the same two for ANY flowsheet, by descriptor (dsp_loop_market_*; rolling_flowsheets.py):
 //                           power P_T = (x[a] ca + x[b] cb) + const, curves that start at the generator's p_min, <= 2 state columns,
 //                           optional wind; the clearing lanes also write the tracker's LP (a dsp_loop_model).  VGPRs / scratch of every
@@ -253,13 +257,11 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
   m.c0[r] = lmk_c0(c0_base, sums.price, wind, wind ? loop_opaque(__dmul_rn(m.waste_per_kw, sums.avail)) : 0.0);
 }
 
-// The coupled day-ahead LP of a self-scheduling plant (dsp_loop_schedule_prepare, ABI 18): S scenario blocks of m.n columns side by side
-// in row b (m.row_stride doubles apart), one lane per (plant, scenario).  Block i is the block that loop_market_prepare_kernel writes
-// into row b * S + i with k = -1; the lane of scenario 0 also sums the S objective constants in the order of i - alone, so that the
-// order is the tensor form's (BatchedDoubleLoop._day_ahead_step_self_schedule).
-__global__ void __launch_bounds__(256) loop_schedule_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= s.B * s.S) return;
+// Lane r = b * S + i of a coupled day-ahead LP: S scenario blocks of m.n columns side by side in row b (m.row_stride doubles apart).
+// Block i is the block that loop_market_prepare_kernel writes into row b * S + i with k = -1; the lane of scenario 0 also sums the S
+// objective constants in the order of i - alone, so that the order is the tensor form's (BatchedDoubleLoop._coupled_blocks).  One
+// block writer and one constant summer for the self-schedule's rows and the monotone Bidder's.
+__device__ __forceinline__ void lmk_coupled_block(const dsp_loop_market_state &s, const dsp_loop_market_model &m, int r) {
   const int b = r / s.S, i = r - b * s.S;
   const bool wind = m.wind_cols[0] >= 0;
   const size_t at0 = (size_t)b * m.row_stride + (size_t)i * m.n;
@@ -274,6 +276,44 @@ __global__ void __launch_bounds__(256) loop_schedule_prepare_kernel(dsp_loop_mar
     total = j ? __dadd_rn(total, c0) : c0;
   }
   m.c0[b] = total;
+}
+
+// The coupled day-ahead LP of a self-scheduling plant (dsp_loop_schedule_prepare, ABI 18): one lane per (plant, scenario); its coupling
+// rows are static (bounds 0, 0, written once by the caller).
+__global__ void __launch_bounds__(256) loop_schedule_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= s.B * s.S) return;
+  lmk_coupled_block(s, m, r);
+}
+
+// The coupled day-ahead LP of a plant that bids a MONOTONE curve (dsp_loop_monotone_prepare, ABI 19; idaes' Bidder): the same S blocks,
+// tied by P = S (S - 1) / 2 rows pda[k, t] - pda[j, t] per period (pairs j < k, k fastest; row first + p * T + t) whose BOUNDS follow
+// the order of plant b's day-ahead scenario prices: with d = da[k, t] - da[j, t], rlo = 0 if d > 0 else -inf, rhi = 0 if d < 0 else +inf
+// (CoupledScenarioModel.load).  One launch over two lane ranges: lanes [0, B * S) write the blocks and the constant as above, the next
+// B * P * T lanes one (b, p, t) each, t fastest - a wave's stores to a row of rlo / rhi are consecutive.  No atomics, no cross-lane
+// traffic; every lane writes addresses of its own.
+__global__ void __launch_bounds__(256) loop_monotone_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m, double *rlo, double *rhi,
+                                                                    int m_rows, int first) {
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int S = s.S, T = m.T;
+  const long long blocks = (long long)s.B * S;
+  if (g < blocks) {
+    lmk_coupled_block(s, m, (int)g);
+    return;
+  }
+  const int per_plant = S * (S - 1) / 2 * T;
+  const long long q = g - blocks;
+  if (q >= (long long)s.B * per_plant) return;
+  const int b = (int)(q / per_plant), pt = (int)(q - (long long)b * per_plant);
+  const int p = pt / T, t = pt - p * T;
+  int j = 0, rest = p;                           // p -> (j, k): pairs (0, 1) .. (0, S - 1), (1, 2) ..: at most 15 values of j
+  while (rest >= S - 1 - j) { rest -= S - 1 - j; ++j; }
+  const int k = j + 1 + rest;
+  const long long h = *s.hour, st0 = s.start[b];
+  const double d = __dsub_rn(s.da_series[loop_scenario_index(s, st0, h, k, 0, t)], s.da_series[loop_scenario_index(s, st0, h, j, 0, t)]);
+  const size_t at = (size_t)b * m_rows + first + pt;
+  rlo[at] = d > 0.0 ? 0.0 : -INFINITY;
+  rhi[at] = d < 0.0 ? 0.0 : INFINITY;
 }
 
 template <int SP>
@@ -296,9 +336,10 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
   for (int i = 0; i < SP; ++i) {
     long long key = kBidDrop;
     if (i < S) {
-      const size_t row = (size_t)b * S + i;
+      // (ABI 19, coupled: scenario i of plant b is block i of row b, one status / flags entry per plant; ABI 18: block 0 of a coupled row)
+      const size_t row = s.coupled ? (size_t)b : (size_t)b * S + i;
       if (m.status[row] == 0) {
-        const double *x = m.x + row * (size_t)(m.row_stride ? m.row_stride : m.n);      // (ABI 18: block 0 of a coupled row)
+        const double *x = m.x + row * (size_t)(m.row_stride ? m.row_stride : m.n) + (s.coupled ? (size_t)i * m.n : 0);
         double power;
         if (k < 0) {
           power = x[ca];
@@ -314,7 +355,7 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
       } else {
         any_bad = true;
       }
-      if (t == 0 && m.flags && s.uncertified && (m.flags[row] & DSP_FLAG_OBJ_WAIVED))
+      if (t == 0 && (i == 0 || !s.coupled) && m.flags && s.uncertified && (m.flags[row] & DSP_FLAG_OBJ_WAIVED))      // (coupled: a plant once)
         atomicAdd(reinterpret_cast<unsigned long long *>(s.uncertified), 1ull);
     }
     keys[i] = key;
@@ -349,6 +390,13 @@ hipError_t launch_loop_market_prepare(const dsp_loop_market_state &st, const dsp
 hipError_t launch_loop_schedule_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, hipStream_t stream) {
   const long long rows = (long long)st.B * st.S;
   hipLaunchKernelGGL(loop_schedule_prepare_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, st, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_loop_monotone_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, double *rlo, double *rhi, int m_rows,
+                                        int first, hipStream_t stream) {
+  const long long lanes = (long long)st.B * st.S + (long long)st.B * (st.S * (st.S - 1) / 2) * m.T;
+  hipLaunchKernelGGL(loop_monotone_prepare_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, st, m, rlo, rhi, m_rows, first);
   return hipGetLastError();
 }
 

@@ -109,10 +109,10 @@ EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_
                     "dsp_get_scaling", "dsp_destroy", "dsp_strerror", "dsp_last_hip_error", "dsp_version",
                     "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
                     "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step", "dsp_loop_project",
-                    "dsp_loop_schedule_prepare")
+                    "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare")
 
 
-ABI_VERSION = 18         # DSP_VERSION of the include/dsp_hip.h these structures mirror
+ABI_VERSION = 19         # DSP_VERSION of the include/dsp_hip.h these structures mirror
 
 
 BID_MAX_HOURS, BID_MAX_SCENARIOS = 64, 16384
@@ -158,13 +158,13 @@ class DspLoopMarketModel(C.Structure):
 
 
 class DspLoopMarketState(C.Structure):
-    """include/dsp_hip.h: dsp_loop_market_state (ABI 14; self_schedule, curve_slots: ABI 18)"""
+    """include/dsp_hip.h: dsp_loop_market_state (ABI 14; self_schedule, curve_slots: ABI 18; coupled: ABI 19)"""
     _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("D", C.c_int32), ("N", C.c_int32), ("backcast", C.c_int32), ("price_taker", C.c_int32),
                 ("start", C.c_void_p), ("hour", C.c_void_p),
                 ("da_series", C.c_void_p), ("rt_series", C.c_void_p), ("cf_series", C.c_void_p),
                 ("state", C.c_void_p), ("da_offer", C.c_void_p), ("da_prices", C.c_void_p),
                 ("bad", C.c_void_p), ("uncertified", C.c_void_p), ("p_min_cents", C.c_int64),
-                ("rt_history_lag_days", C.c_int32), ("self_schedule", C.c_int32), ("curve_slots", C.c_int32), ("reserved", C.c_int32)]
+                ("rt_history_lag_days", C.c_int32), ("self_schedule", C.c_int32), ("curve_slots", C.c_int32), ("coupled", C.c_int32)]
 
 
 class DspLoopParamState(C.Structure):
@@ -278,6 +278,8 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_market_clear.restype = C.c_int
     lib.dsp_loop_schedule_prepare.argtypes = [C.POINTER(DspLoopMarketState), C.POINTER(DspLoopMarketModel), vp]
     lib.dsp_loop_schedule_prepare.restype = C.c_int
+    lib.dsp_loop_monotone_prepare.argtypes = [C.POINTER(DspLoopMarketState), C.POINTER(DspLoopMarketModel), vp, vp, i32, i32, vp]
+    lib.dsp_loop_monotone_prepare.restype = C.c_int
     lib.dsp_loop_param_step.argtypes = [C.POINTER(DspLoopParamState), C.POINTER(DspLoopModel), i32, i32, vp]
     lib.dsp_loop_param_step.restype = C.c_int
     lib.dsp_loop_project.argtypes = [C.POINTER(DspLoopProjectState), C.POINTER(DspLoopModel), i32, i32, vp]

@@ -61,7 +61,26 @@ rows are vacuous and the coupled LP separates: the hourly step solves B real-tim
 in the last T_rt - 1 hours of a day the look-ahead periods past midnight have a free day_ahead_power which the host would still tie
 across scenarios; this loop does not.  `_day_ahead_step_self_schedule` / `_hour_step_bid` (the one hourly bidding step, here with
 one row per plant and pairs priced at 0) are the specification as tensor operations; csrc/dsp_market.hip (dsp_loop_schedule_prepare; dsp_loop_market_prepare / _clear on an S = 1 state with
-row_stride / self_schedule / curve_slots) is the same arithmetic, bit for bit."""
+row_stride / self_schedule / curve_slots) is the same arithmetic, bit for bit.
+
+Monotone bid curves (bidder="lp", scenario_coupling="monotone"; the reference's published double loops - wind + battery, nuclear - bid with
+idaes' Bidder, n_scenario = 3 on a Backcaster; our host restatement is workflow/bidder.py::Bidder(scenario_coupling="monotone") on
+workflow/coupling.py::CoupledScenarioModel): that bidder does not solve its price scenarios one by one, it orders every pair of them in
+every period, (day_ahead_power[k, t] - day_ahead_power[j, t]) (price[k, t] - price[j, t]) >= 0.  Day-ahead: ONE coupled LP per plant - B rows
+of S * n1 columns, the blocks of the self-schedule (same template col_scale, tiled) plus S (S - 1) / 2 * T static rows
+pda[k, t] - pda[j, t], pair order CoupledScenarioModel.pairs (j < k, k fastest), row S * m1 + p * T + t.  Per day only the BOUNDS of
+those rows change, with plant b's day-ahead scenario prices (the backcast index rule of the blocks' objective): d = da[k, t] - da[j, t],
+rlo = 0 if d > 0 else -inf, rhi = 0 if d < 0 else +inf - CoupledScenarioModel.load.  Blocks, state, wind and c0[b] = sum_i c0(b, i) (in the
+order of i) are the self-schedule's.  Bid: the S pairs of a plant and period are block i's day_ahead_power and scenario i's day-ahead
+forecast, through the unchanged curve and clearing rules (integer cents, the p_min point, S + 1 slots); status and flags of plant b's ONE
+solve stand for all its S pairs, `uncertified` counts a flagged plant once.  Real time: inside the cleared day every day_ahead_power
+column is fixed to the same cleared offer in all scenarios, and the host's coupled real-time problem puts its rows on those columns: they
+are vacuous there, so the hourly step is the stochastic mode's `_hour_step_bid` with B * S rows, unchanged.  OURS (the self-schedule's
+third choice again): in the last T_rt - 1 hours of a day the look-ahead periods past midnight have a free day_ahead_power, which the host
+would still order across scenarios; this loop does not.  Not settled here: whether upstream idaes additionally orders the real-time power
+output across scenarios - idaes is not available to this project; the loop follows this project's host Bidder.
+`_day_ahead_step_monotone` (on `_coupled_blocks`, shared with the self-schedule) is the specification as tensor operations;
+csrc/dsp_market.hip (dsp_loop_monotone_prepare; dsp_loop_market_clear on a state with coupled = 1) is the same arithmetic, bit for bit."""
 from __future__ import annotations
 
 import numpy as np
@@ -133,30 +152,33 @@ class _Model:
             self.base_c0 -= float(per_kw) * float(template_sum)           # the template's curtailment constant leaves; the window's enters
         attach_solver(self, B, dev, device_index, getattr(model, "solver_hints", None), lp_backend, solved)      # (solved=False: parametrized mode never solves its bidding templates)
 
-    def couple(self, model, S, B, dev, device_index, lp_backend):
-        """-> the COUPLED day-ahead model of a self-scheduling batch built on this one-row block model (of `model`, the day-ahead
-        template): B rows of the LP of CoupledScenarioModel(model, "non_anticipative") - S blocks of this LP side by side, (S - 1) T
-        coupling rows pda[s, t] - pda[0, t] with bounds 0, 0 written here, once, like the blocks' static bounds.  Afterwards THIS
-        model is the [B * S, n1] view of the coupled rows' c / lb / ub (block i of row b = its row b * S + i), which _set_rows writes;
-        its c0 [B * S] holds the scenario constants that the coupled c0 sums."""
+    def couple(self, model, S, B, dev, device_index, lp_backend, mode="non_anticipative"):
+        """-> the COUPLED day-ahead model of a batch built on this one-row block model (of `model`, the day-ahead template): B rows of
+        the LP of CoupledScenarioModel(model, mode) - S blocks of this LP side by side and its coupling rows from row
+        `first_coupling_row` = S * m1 on.  mode "non_anticipative" (a self-schedule): (S - 1) T rows pda[s, t] - pda[0, t] with bounds
+        0, 0 written here, once, like the blocks' static bounds.  mode "monotone" (the Bidder's ordered curve): S (S - 1) / 2 * T rows
+        pda[k, t] - pda[j, t] over `pairs` (j < k, k fastest), free here - the day-ahead step writes their bounds every day, from the
+        order of the day's scenario prices.  Afterwards THIS model is the [B * S, n1] view of the coupled rows' c / lb / ub (block i
+        of row b = its row b * S + i), which _set_rows writes; its c0 [B * S] holds the scenario constants that the coupled c0 sums."""
         import types
         import torch
         from .workflow.coupling import CoupledScenarioModel
         shim = types.SimpleNamespace(lp=model.lp, n_scenario=S, HOUR=model.HOUR, pda_cols=model.pda_cols, block=model.block,
                                      solver_hints=getattr(model, "solver_hints", None))
-        coupled = CoupledScenarioModel(shim, "non_anticipative")
+        coupled = CoupledScenarioModel(shim, mode)
         cm = _Model.__new__(_Model)
         cm.__dict__.update(self.__dict__)                                 # block data: base_c, PT, state / wind / day-ahead columns (block-relative)
         cm.lp, cm.S, cm.n1 = coupled.lp, S, self.lp.n
+        cm.pairs, cm.first_coupling_row = coupled.pairs, S * self.lp.m
         if getattr(self.lp, "col_scale", None) is not None:               # the blocks keep the template's column scaling (DeviceLP reads it):
             cm.lp.col_scale = np.tile(np.asarray(self.lp.col_scale, np.float64), S)      # wind + battery columns span 200 .. 1e9
-        n1, m1, Tc = self.lp.n, self.lp.m, (S - 1) * self.T
+        n1, m1, Tc = self.lp.n, self.lp.m, len(coupled.pairs) * self.T
         cm.c = self.base_c.repeat(S).repeat(B, 1)
         cm.c0 = torch.zeros(B, dtype=torch.float64, device=dev)
         cm.lb, cm.ub = self.lb[0].repeat(S).repeat(B, 1), self.ub[0].repeat(S).repeat(B, 1)
-        zeros = torch.zeros(Tc, dtype=torch.float64, device=dev)
-        cm.rlo = torch.cat([self.rlo[0, :m1].repeat(S), zeros]).repeat(B, 1)
-        cm.rhi = torch.cat([self.rhi[0, :m1].repeat(S), zeros]).repeat(B, 1)
+        side = lambda v: torch.full((Tc,), 0.0 if mode == "non_anticipative" else v, dtype=torch.float64, device=dev)
+        cm.rlo = torch.cat([self.rlo[0, :m1].repeat(S), side(float("-inf"))]).repeat(B, 1)
+        cm.rhi = torch.cat([self.rhi[0, :m1].repeat(S), side(float("inf"))]).repeat(B, 1)
         attach_solver(cm, B, dev, device_index, coupled.solver_hints, lp_backend)      # (a day-ahead horizon: a T > 16 model's options)
         self.c,self.lb, self.ub = (v.view(B * S, n1) for v in (cm.c, cm.lb, cm.ub))
         self.c0 = torch.zeros(B * S, dtype=torch.float64, device=dev)
@@ -366,7 +388,7 @@ class BatchedDoubleLoop(_DeviceLoop):
     def __init__(self, flowsheet, n_scenarios, device=0, first_scenario=0, day_ahead_horizon=48, tracking_horizon=4, lp_backend=None,
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
                  market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
-                 battery_mwh=None, ruc_hour=None):
+                 battery_mwh=None, ruc_hour=None, scenario_coupling="independent"):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -403,14 +425,25 @@ class BatchedDoubleLoop(_DeviceLoop):
         LPs on scenario 0.  results() has the stochastic mode's keys.  The hourly steps replay from graphs; so does the day-ahead step
         where the coupled LP stays in the fused kernels (nuclear, wind + PEM) - a coupled LP that the solver streams (wind + battery)
         is solved from the host and its step stays eager (day_ahead()).  Refused (ValueError): ruc_hour, per-plant sizes (wind_mw,
-        battery_mw, battery_mwh), bid_price / storage_mw."""
+        battery_mw, battery_mwh), bid_price / storage_mw.
+        scenario_coupling: "independent" (the default: the loops above, bit for bit - the LP bidder solves its B * S scenario LPs one by
+        one and the running maximum of the curve repairs their order) or "monotone" (bidder="lp", forecaster="backcast",
+        n_price_scenarios = S >= 2; all three flowsheets, both markets): the reference's stochastic Bidder (module docstring, "Monotone
+        bid curves").  ONE coupled day-ahead LP per plant (self.da: B rows of S * n1 columns, S (S - 1) / 2 * T ordered-pair rows whose
+        bounds follow the day's scenario prices; self.da_block is its [B * S, n1] view); the S pairs of a plant-hour are block i's
+        day_ahead_power and scenario i's forecast, through the unchanged curve and clearing rules; status and flags of the plant's one
+        solve stand for its S pairs and `uncertified` counts a flagged plant once.  The hourly steps, results() and reset() are the
+        stochastic mode's.  The day-ahead step replays from a graph where the coupled LP stays in the fused kernels, as the
+        self-schedule's.  Refused (ValueError): another value, bidder other than "lp", ruc_hour, per-plant sizes, bid_price /
+        storage_mw, forecaster="perfect", n_price_scenarios=1 (no pairs: that is the independent loop)."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
         self.S = S = int(n_price_scenarios)
         self.D = D = int(max_historical_days)
         bid_price, storage_mw, ruc_hour, sizes, plant_windows = self._validate(
-            forecaster, market, bidder, tracking_horizon, bid_price, storage_mw, ruc_hour, wind_mw, battery_mw, battery_mwh, plant_windows)
+            forecaster, market, bidder, tracking_horizon, bid_price, storage_mw, ruc_hour, wind_mw, battery_mw, battery_mwh, plant_windows,
+            scenario_coupling)
         self.ruc_hour, self.sized = ruc_hour, sizes is not None
         self.forecaster, self.market = forecaster, market
         self.stochastic = forecaster != "perfect" or market != "stub" or self.parametrized or self.self_schedule
@@ -448,12 +481,13 @@ class BatchedDoubleLoop(_DeviceLoop):
             cols = [p["wind"].index for p in f["periods"]]
             return cols, f["wind_kw"], d["per_kw"], f["wind_kw"] * float(np.sum(cf_s[:len(cols)]))
         mk = lambda model, nb, solved=True: _Model(model, fam, nb, dev, device, power, d["init"](model.block), wind_of(model), lp_backend, solved)
-        if self.self_schedule:                        # ONE coupled day-ahead LP per plant; the hourly LPs are scenario 0's (module docstring)
+        if self.coupled_da:                           # ONE coupled day-ahead LP per plant (module docstring)
             self.da_block = mk(da_model, 1, False)
             self.da_block.pda_cols = idx(da_model.pda_cols)
-            self.da = self.da_block.couple(da_model, S, B, dev, device, lp_backend)
-            self.rt, self.tr = mk(rt_model, B), mk(tr_model, B)
-            self.rt.per_plant = 1
+            self.da = self.da_block.couple(da_model, S, B, dev, device, lp_backend, "monotone" if self.monotone else "non_anticipative")
+            self.rt, self.tr = mk(rt_model, B if self.self_schedule else B * S), mk(tr_model, B)
+            if self.self_schedule:                    # its hourly LPs are scenario 0's; the monotone Bidder's are the stochastic mode's B * S
+                self.rt.per_plant = 1
         else:
             self.da, self.rt, self.tr = mk(da_model, rows, not self.parametrized), mk(rt_model, rows, not self.parametrized), mk(tr_model, B)
         self.da.pda_cols, self.rt.pda_cols = idx(da_model.pda_cols), idx(rt_model.pda_cols)
@@ -474,9 +508,9 @@ class BatchedDoubleLoop(_DeviceLoop):
         self.use_graphs = bool(use_graphs) and lp_backend is None
         self.simplex_warm = bool(simplex_warm) and lp_backend is None
         self._graphs, self._warm, self._pending = {}, False, False
-        self._da_capturable = None                    # self-schedule: may the coupled day-ahead step be a graph node (day_ahead)
+        self._da_capturable = None                    # a coupled day-ahead LP: may its step be a graph node (day_ahead)
         self.use_fused = bool(use_fused) and lp_backend is None and self.rt.T <= 16 and self.tr.T <= 16 and len(self.scale) <= 2
-        self.exact = self.sized or self.parametrized or self.self_schedule    # these state phase 2 of dsp_loop_update exactly, sums included (_hand_off)
+        self.exact = self.sized or self.parametrized or self.coupled_da       # these state phase 2 of dsp_loop_update exactly, sums included (_hand_off)
         # what reset() zeroes and what results() reports beyond obj / energy_mwh / state: every setup below adds its own
         self._zeroed = [self.state, self.revenue, self.energy_mwh, self.delivered, self.da_offer, self.da_prices, self.hour_t, self.uncertified, self.bad]
         self._result_keys = []
@@ -488,7 +522,7 @@ class BatchedDoubleLoop(_DeviceLoop):
             self._parametrized_setup(d, bid_price, storage_mw, tr_model, fam)
         elif self.stochastic:
             self.p_min_cents = int(round(float(bidder.bidding_model_object.model_data.p_min) * 100.0))     # Bidder._assemble_bids: p_min of the generator
-            for m in ((self.da_block if self.self_schedule else self.da), self.rt):
+            for m in ((self.da_block if self.coupled_da else self.da), self.rt):
                 cols = m.set_terms(dev)
                 if set(cols[cols >= 0].tolist()) & set(m.pda_cols.cpu().tolist()):
                     raise ValueError("a column is both a term of the power output and day_ahead_power: the prices' objective entries would collide")
@@ -506,6 +540,8 @@ class BatchedDoubleLoop(_DeviceLoop):
             self._da_step, self._hour, self._n_da, self._n_hour = self._day_ahead_step_parametrized, self._hour_step_parametrized, 0, B
         elif self.self_schedule:
             self._da_step, self._hour, self._n_da, self._n_hour = self._day_ahead_step_self_schedule, self._hour_step_bid, B, 2 * B
+        elif self.monotone:
+            self._da_step, self._hour, self._n_da, self._n_hour = self._day_ahead_step_monotone, self._hour_step_bid, B, B * S + B
         else:
             self._da_step = self._day_ahead_step_stochastic if self.stochastic else self._day_ahead_step
             self._hour = self._hour_step_bid if self.stochastic else self._hour_step
@@ -527,15 +563,32 @@ class BatchedDoubleLoop(_DeviceLoop):
         self._zeroed += [self.da_energy_mwh, self.offered_mwh]
         self._result_keys += ["da_energy_mwh", "offered_mwh"]             # what the market left on the table: offered (the curves' last points) against cleared
 
-    def _validate(self, forecaster, market, bidder, tracking_horizon, bid_price, storage_mw, ruc_hour, wind_mw, battery_mw, battery_mwh, plant_windows):
+    def _validate(self, forecaster, market, bidder, tracking_horizon, bid_price, storage_mw, ruc_hour, wind_mw, battery_mw, battery_mwh, plant_windows,
+                  scenario_coupling="independent"):
         """the arguments' checks that need no template (ValueError; __init__'s docstring) -> the normalised (bid_price, storage_mw,
-        ruc_hour, sizes, plant_windows); sets self.parametrized / self.self_schedule"""
+        ruc_hour, sizes, plant_windows); sets self.parametrized / self.self_schedule / self.monotone / self.coupled_da"""
         flowsheet, B, S = self.flowsheet, self.B, self.S
         self._check_market_arguments(forecaster, market, S, self.D)
         if bidder not in ("lp", "parametrized", "self_schedule"):
             raise ValueError(f"bidder is 'lp', 'parametrized' or 'self_schedule', not {bidder!r}")
         self.parametrized = bidder == "parametrized"
         self.self_schedule = bidder == "self_schedule"
+        if scenario_coupling not in ("independent", "monotone"):
+            raise ValueError(f"scenario_coupling is 'independent' or 'monotone', not {scenario_coupling!r}")
+        self.monotone = scenario_coupling == "monotone"
+        self.coupled_da = self.self_schedule or self.monotone             # ONE coupled day-ahead LP per plant
+        if self.monotone:
+            if bidder != "lp":
+                raise ValueError(f"scenario_coupling='monotone' belongs to bidder='lp': the LP Bidder's curve is what it orders, not {bidder!r}'s")
+            if forecaster != "backcast":
+                raise ValueError("scenario_coupling='monotone' orders the curve across backcast price scenarios: forecaster='backcast'")
+            if S < 2:
+                raise ValueError("scenario_coupling='monotone' needs n_price_scenarios >= 2: one scenario has no pairs to order (that is scenario_coupling='independent')")
+            if ruc_hour is not None:
+                raise ValueError("ruc_hour belongs to scenario_coupling='independent': a monotone bid made at the RUC hour on a projected state is a follow-up (DESIGN 9)")
+            sized = [k for k, v in (("wind_mw", wind_mw), ("battery_mw", battery_mw), ("battery_mwh", battery_mwh)) if v is not None]
+            if sized:
+                raise ValueError(f"{', '.join(sized)}: per-plant sizes belong to scenario_coupling='independent' (a monotone batch of different plants is a follow-up, DESIGN 9)")
         if self.self_schedule:
             if ruc_hour is not None:
                 raise ValueError("ruc_hour belongs to bidder='lp': a self-schedule made at the RUC hour on a projected state is a follow-up (DESIGN 9)")
@@ -711,6 +764,12 @@ class BatchedDoubleLoop(_DeviceLoop):
         mk.p_min_cents = self.p_min_cents
         self._mk_state = mk
         self._mk_da, self._mk_rt = (_describe(DspLoopMarketModel, m, len(self.scale)) for m in (self.da, self.rt))
+        if self.monotone:
+            # the coupled rows: one block described, blocks S * n1 apart; c0 / status / flags one entry per plant.  The day-ahead
+            # clearing reads scenario i of plant b from block i of row b (coupled = 1); the hourly steps run on the ordinary state
+            self._mk_da.row_stride = self.da.lp.n
+            self._mk_coupled = DspLoopMarketState.from_buffer_copy(mk)
+            self._mk_coupled.coupled = 1
         if self.self_schedule:
             # the coupled rows: one block described, blocks S * n1 apart; c0 / status / flags one entry per plant.  Everything but the
             # day-ahead fan-out runs on an S = 1 state (scenario 0 = the most recent backcast day): pairs priced at 0, curves in the
@@ -746,11 +805,11 @@ class BatchedDoubleLoop(_DeviceLoop):
         import ctypes as C
         self._call(self._lib.dsp_loop_market_prepare, C.byref(self._mk_bid if bid else self._mk_state), C.byref(m), k)
 
-    def _market_clear(self, m, tr, k, T, dispatch, curve, count, bid=False):
+    def _market_clear(self, m, tr, k, T, dispatch, curve, count, bid=False, state=None):
         """curves of the T periods from m's solution, cleared into `dispatch` (status / flags of the solve: folded into bad / uncertified
-        by the kernel); tr: the tracker whose LP the clearing lanes also write, or None"""
+        by the kernel); tr: the tracker whose LP the clearing lanes also write, or None; state: a market state of its own"""
         import ctypes as C
-        self._call(self._lib.dsp_loop_market_clear, C.byref(self._mk_bid if bid else self._mk_state), C.byref(m), None if tr is None else C.byref(tr), k, T,
+        self._call(self._lib.dsp_loop_market_clear, C.byref(state or (self._mk_bid if bid else self._mk_state)), C.byref(m), None if tr is None else C.byref(tr), k, T,
                    *(C.c_void_p(v.data_ptr()) for v in (dispatch, curve, count)))
 
     # -- pieces of a step (all capturable: persistent tensors, the clock read on the device; windows, curves, clearing: _DeviceLoop) ------
@@ -977,17 +1036,11 @@ class BatchedDoubleLoop(_DeviceLoop):
         import torch
         return self._curves(power[:, None, :], torch.zeros_like(power)[:, None, :], status)
 
-    def _day_ahead_step_self_schedule(self):
-        """B coupled day-ahead LPs: block i of row b on scenario i's backcast prices, plant b's state and wind, day_ahead_power free
-        (what _set_rows gives row b * S + i), tied by the static coupling rows; c0[b] = sum_i c0(b, i) in the order of i.  The
-        schedule - block 0's day_ahead_power - is offered at cost 0 and cleared at the realised day-ahead price."""
-        import ctypes as C
+    def _coupled_blocks(self):
+        """the S blocks of the B coupled day-ahead rows: block i of row b on scenario i's backcast prices, plant b's state and wind,
+        day_ahead_power free (what _set_rows gives row b * S + i), and c0[b] = sum_i c0(b, i) in the order of i
+        -> the day-ahead scenario prices [B, S, T]"""
         m, blk, B, S = self.da, self.da_block, self.B, self.S
-        if self.use_fused:
-            self._call(self._lib.dsp_loop_schedule_prepare, C.byref(self._mk_sched), C.byref(self._mk_da))
-            m.solve(B)
-            self._market_clear(self._mk_da, None, -1, 24, *self._day_ahead_buffers()[:3])
-            return self._day_ahead_market()
         da = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T)
         rt = self._forecast(self.rt_series, m.T, 0).expand(B, S, m.T)
         self._set_rows(blk, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
@@ -997,9 +1050,52 @@ class BatchedDoubleLoop(_DeviceLoop):
         for i in range(1, S):
             total = total + each[:, i]
         m.c0.copy_(total)
+        return da
+
+    def _day_ahead_step_self_schedule(self):
+        """B coupled day-ahead LPs (_coupled_blocks), tied by the static coupling rows.  The schedule - block 0's day_ahead_power - is
+        offered at cost 0 and cleared at the realised day-ahead price."""
+        import ctypes as C
+        m, B = self.da, self.B
+        if self.use_fused:
+            self._call(self._lib.dsp_loop_schedule_prepare, C.byref(self._mk_sched), C.byref(self._mk_da))
+            m.solve(B)
+            self._market_clear(self._mk_da, None, -1, 24, *self._day_ahead_buffers()[:3])
+            return self._day_ahead_market()
+        self._coupled_blocks()
         out = m.solve(B)
         self._check(out)
         self._day_ahead_market(self._schedule_curves(out["x"][:, m.pda_cols[:24]], out["status"]))      # (block 0: the block-relative columns)
+
+    # -- monotone bid curves: one coupled day-ahead LP per plant, its S pairs per hour ordered by the LP itself (module docstring) --------
+    def _day_ahead_step_monotone(self):
+        """B coupled day-ahead LPs (_coupled_blocks), tied by the ordered-pair rows pda[k, t] - pda[j, t] of m.pairs, row
+        first_coupling_row + p * T + t: with d = da[k, t] - da[j, t] of plant b's day-ahead scenario prices, rlo = 0 if d > 0 else -inf,
+        rhi = 0 if d < 0 else +inf (CoupledScenarioModel.load).  One curve per plant-hour from block i's day_ahead_power and scenario
+        i's day-ahead forecast, cleared at the realised day-ahead price; the status of plant b's one solve stands for its S pairs."""
+        import ctypes as C
+        import torch
+        m, B, S = self.da, self.B, self.S
+        if self.use_fused:
+            self._call(self._lib.dsp_loop_monotone_prepare, C.byref(self._mk_coupled), C.byref(self._mk_da), C.c_void_p(m.rlo.data_ptr()),
+                       C.c_void_p(m.rhi.data_ptr()), m.lp.m, m.first_coupling_row)
+            m.solve(B)
+            self._market_clear(self._mk_da, None, -1, 24, *self._day_ahead_buffers()[:3], state=self._mk_coupled)
+            return self._day_ahead_market()
+        da = self._coupled_blocks()
+        if not hasattr(self, "_pair_j"):              # (persistent operands: a captured step creates no tensor from host data)
+            at = lambda v: torch.as_tensor(v, dtype=torch.int64, device=self.dev)
+            self._pair_j, self._pair_k = at([j for j, _ in m.pairs]), at([k for _, k in m.pairs])
+            self._side = tuple(torch.full((), v, dtype=torch.float64, device=self.dev) for v in (0.0, float("-inf"), float("inf")))
+        zero, below, above = self._side
+        d = (da[:, self._pair_k, :] - da[:, self._pair_j, :]).reshape(B, -1)          # [B, P * T]: pair p, period t at p * T + t
+        rows = slice(m.first_coupling_row, m.first_coupling_row + d.shape[1])
+        m.rlo[:, rows] = torch.where(d > 0, zero, below)
+        m.rhi[:, rows] = torch.where(d < 0, zero, above)
+        out = m.solve(B)
+        self._check(out)
+        power = out["x"].reshape(B, S, m.n1)[:, :, m.pda_cols[:24]]                  # block i: the block-relative columns
+        self._day_ahead_market(self._curves(power, self._forecast(self.da_series, 24, 0), out["status"].repeat_interleave(S)))
 
     # -- parametrized mode: two-tier closed-form curves (workflow/parametrized_bidder.py), no bidding LP ---------------------------------
     def _param_curves(self, cf):
@@ -1147,14 +1243,14 @@ class BatchedDoubleLoop(_DeviceLoop):
             self._run("activate", self._activate)
             self._pending = False
             return self.da_offer.clone()
-        # A self-schedule's coupled LP beyond the register / LDS-resident kernels (wind + battery: 582 columns, 408 rows at 24 h) runs in
+        # A coupled LP (self-schedule, monotone bid curves) beyond the register / LDS-resident kernels (wind + battery: 582 columns, 408 rows at 24 h) runs in
         # the solver's HBM-resident streaming form, which is driven from the host (it polls the scenarios' completion between check
         # periods): it cannot be a node of a captured graph, and the step stays eager, once per simulated day.  A coupled LP that stays
         # in the fused kernels (nuclear, wind + PEM at S = 3) is captured and replayed like the stochastic mode's.  Which of the two a
         # handle is, the first - eager - day's solve reports (dsp_stats::streaming).
-        if self.self_schedule and self._da_capturable is None and self._warm:
+        if self.coupled_da and self._da_capturable is None and self._warm:
             self._da_capturable = self.use_graphs and not self.da.dlp.last_stats.streaming
-        if self.self_schedule and not self._da_capturable:
+        if self.coupled_da and not self._da_capturable:
             self._da_step()
         else:
             self._run("da", self._da_step)

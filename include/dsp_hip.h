@@ -27,6 +27,9 @@
  * ABI 18 adds the self-scheduling plant: dsp_loop_schedule_prepare writes ONE coupled day-ahead LP per plant (S scenario blocks side by
  * side in a row, tied by static non-anticipativity rows) and dsp_loop_market_clear reads block 0 of such a row
  * (dsp_loop_market_model::row_stride) and prices the schedule at 0 (dsp_loop_market_state::self_schedule, curve_slots).
+ * ABI 19 adds the Bidder's monotone bid curves across price scenarios: dsp_loop_monotone_prepare writes ONE coupled day-ahead LP per plant
+ * (the same S blocks, and the bounds of the S (S - 1) / 2 * T ordered-pair rows from the order of the day-ahead scenario prices) and
+ * dsp_loop_market_clear reads scenario i of plant b from block i of row b (dsp_loop_market_state::coupled, was reserved).
  */
 #ifndef DSP_HIP_H
 #define DSP_HIP_H
@@ -39,7 +42,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 18
+#define DSP_VERSION 19
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -563,7 +566,10 @@ typedef struct dsp_loop_market_state {
   int32_t curve_slots;                 /* (ABI 18) points per stored curve in `curve`: 0 = S + 1, as before; otherwise
                                           S + 1 <= curve_slots <= DSP_MARKET_MAX_S + 1 (a loop that clears with an S = 1 state into
                                           buffers sized for its S price scenarios); unused slots are written 0                     */
-  int32_t reserved;
+  int32_t coupled;                     /* (ABI 19; was reserved) dsp_loop_market_clear: 0 = as before, bit for bit; 1 = the S scenarios
+                                          of plant b are the S blocks of ONE coupled row (dsp_loop_monotone_prepare): x of scenario i
+                                          at m->x + b * row_stride + i * n, status / flags one entry per plant at [b], a flagged
+                                          plant counted once in `uncertified`.  Needs row_stride >= S * n and self_schedule = 0      */
 } dsp_loop_market_state;
 
 /* Scenario fan-out of bidding model `m` (B * S rows), one lane per row.  k = -1: the day-ahead LP (day_ahead_power free in every period);
@@ -583,6 +589,11 @@ int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_mark
  * dsp_loop_schedule_prepare that is block 0 of plant r's coupled row, the schedule; st->self_schedule prices every pair at 0 cents and
  * st->curve_slots sets the stride of `curve`.  All three are kernel arguments, uniform over the grid; 0 / 0 / 0 is ABI 17 bit for bit.
  * Refused: 0 < row_stride < n, curve_slots outside {0} and S + 1 .. DSP_MARKET_MAX_S + 1, self_schedule outside 0 / 1.
+ * ABI 19: st->coupled = 1 reads the S pairs of plant b and period t from the S blocks of plant b's ONE coupled row (x at
+ * m->x + b * row_stride + i * n, priced at scenario i's forecast as before); status[b] / flags[b] of the plant's one solve stand for all
+ * its S pairs and a flagged plant is counted once.  A kernel argument, uniform over the grid; 0 is ABI 18 bit for bit.  Refused (by
+ * every dsp_loop_market_* entry point): coupled outside 0 / 1, coupled with self_schedule = 1; by the clearing: coupled with
+ * row_stride < S * n.
  * Per-plant sizes (ABI 16; BatchedDoubleLoop(wind_mw=, battery_mw=, battery_mwh=)): with wind_kw_plant / c0_base_plant the lanes read
  * plant b's wind capacity and objective constant at the very sites that read the scalars - same intrinsics, same order, so that kernel
  * = tensor form = graph replay stays bit for bit.  A size is never a matrix coefficient of these flowsheets: the battery's power and
@@ -607,6 +618,22 @@ int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market
  * or n_state out of range; a used column index outside the block [0, n); n_state > 0 with a NULL state; wind columns with a NULL
  * cf_series); row_stride < S * n; per-plant size pointers (a self-scheduling batch has one plant size). */
 int dsp_loop_schedule_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, void *hipStream);
+
+/* The day-ahead LP of a plant whose BID CURVE IS MONOTONE across its price scenarios (ABI 19; dispatches_amd/rolling_flowsheets.py:
+ * BatchedDoubleLoop with bidder="lp", scenario_coupling="monotone").  idaes' Bidder ties every pair of scenarios j < k in every period,
+ *   (day_ahead_power[k, t] - day_ahead_power[j, t]) * (price[k, t] - price[j, t]) >= 0
+ * (workflow/coupling.py::CoupledScenarioModel, "monotone").  That is one LP per plant: the S blocks of dsp_loop_schedule_prepare - `m`
+ * describes ONE block, row_stride >= S * n, c0 is [B] - plus P T rows pda[k, t] - pda[j, t], P = S (S - 1) / 2, pairs in the order
+ * (0, 1) .. (0, S - 1), (1, 2) .. (k fastest), row first_coupling_row + p * T + t.  Their coefficients are static; their BOUNDS follow
+ * the order of plant b's day-ahead scenario prices (the index rule of the blocks' objective): with d = da[k, t] - da[j, t],
+ *   rlo = 0 if d > 0 else -inf,   rhi = 0 if d < 0 else +inf.
+ * rlo / rhi are the coupled model's row-bound buffers [B][m_rows]; only the P T rows from first_coupling_row on are written.
+ * One launch over two lane ranges: lanes [0, B * S) write the blocks and c0[b] exactly as dsp_loop_schedule_prepare does, the next
+ * B * P * T lanes one (b, p, t) each, t fastest.  No atomics; bit-identical to the tensor form.
+ * DSP_ERR_INVALID, nothing launched and nothing written, for: everything dsp_loop_schedule_prepare refuses; NULL rlo / rhi; S < 2 (no
+ * pairs); first_coupling_row < 0; first_coupling_row + P * T > m_rows. */
+int dsp_loop_monotone_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, double *rlo, double *rhi, int32_t m_rows,
+                              int32_t first_coupling_row, void *hipStream);
 
 /* Parametrized two-tier bidding in the descriptor loop (ABI 15; dispatches_amd/rolling_flowsheets.py: BatchedDoubleLoop with
  * bidder="parametrized").  The reference's wind + PEM and wind + battery sweeps bid without an LP (PEM_parametrized_bidder.py:50-122,
