@@ -90,7 +90,13 @@ struct SolveArgs {
   int trace_scenario;
   int *suspects;               // scenarios the register-resident kernel left DSP_STATUS_SUSPECT (0 = the certificate pass has nothing to do);
                                // suspects[2]: scenarios currently flagged DSP_FLAG_OBJ_WAIVED (0 = the re-certification passes have nothing to do)
+  const double *anchor_w;      // [kAnchorWeights + 1] Halpern anchor weights of the handle, anchor_w[j] = rcp((double)(j + 3)): the weight of
+                               // the iteration that starts j iterations after the last restart (dsp_kernels.hip, anchor_table_shape)
 };
+
+// Weights of SolveArgs::anchor_w a plain segment may use: it reads them from the table when all of them lie inside it; stalls reach
+// larger k, and those segments compute the weight as before.  (One more entry is allocated: the loop loads one weight ahead.)
+constexpr int kAnchorWeights = 4096;
 
 // Layout token of the kernarg buffer: a run-time compiled kernel (dsp_rtc.hpp) receives SolveArgs as raw bytes and is compiled
 // from whatever csrc/ is on disk, so the library and the code object must agree on the structure AND on the development
@@ -126,7 +132,7 @@ constexpr unsigned long long kBuildSwitches = DSP_SW_TRACE | DSP_SW_PROF | DSP_S
 constexpr unsigned long long kSolveArgsToken =
     ((unsigned long long)sizeof(SolveArgs) << 40) ^ ((unsigned long long)__builtin_offsetof(SolveArgs, opt) << 28) ^
     ((unsigned long long)__builtin_offsetof(SolveArgs, queue) << 16) ^ ((unsigned long long)sizeof(DeviceProblem) << 52) ^
-    ((unsigned long long)DSP_VERSION << 8) ^ kBuildSwitches ^
+    ((unsigned long long)DSP_VERSION << 8) ^ kBuildSwitches ^ ((unsigned long long)__builtin_offsetof(SolveArgs, anchor_w) << 4) ^
     ((unsigned long long)rare_lds_bytes(0) << 20);          // (the waves' LDS regions are sized by the library, laid out by the kernel)
 
 // in-wave dense simplex for tiny LPs (dsp_simplex.hip)

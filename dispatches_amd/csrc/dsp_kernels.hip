@@ -214,6 +214,12 @@ __device__ __forceinline__ void stage_entries(Entry *dst, const Entry *__restric
 constexpr bool three_waves_shape(int cpl, int rpl, unsigned wc, unsigned wr, bool qp) {
   return !qp && cpl == 4 && rpl == 2 && wc == 0x1133u && wr == 0x44u;
 }
+// Kernels whose plain iterations READ the Halpern anchor weight 1 / (k + 2) (SolveArgs::anchor_w) instead of computing it in every
+// lane.  The metric kernel alone: at three waves per SIMD it is bound by VALU issue and the LDS pipe, not by a wave's own latency
+// chain, and it is the one this was measured on; every other instantiation keeps its loop instruction for instruction.
+constexpr bool anchor_table_shape(int cpl, int rpl, unsigned wc, unsigned wr, bool qp) {
+  return three_waves_shape(cpl, rpl, wc, wr, qp);
+}
 // The one place that says which first passes are three-wave kernels as the HOST sees a launch (shape of the handle, long vectors, QP):
 // their follow-up passes (certificates, re-certification) run the LIGHT instantiation of the generic kernel of the same <CPL, RPL>,
 // compiled ahead of time for exactly these (light_fn).  Every other first pass holds 256 VGPRs like the generic kernel and keeps it.
@@ -258,6 +264,7 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
   constexpr bool MATREG = WC != 0;
   constexpr bool EARLY_MAT = MATREG && CPL + RPL <= DSP_EARLY_MAT_UPTO;   // restart block: matrix re-read issued ahead of the weight update
   constexpr bool RLDS = MATREG;                                        // rare per-scenario values in LDS (struct Rare)
+  constexpr bool ANCHOR_TABLE = anchor_table_shape(CPL, RPL, WC, WR, QP);  // plain iterations: anchor weight from SolveArgs::anchor_w
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // after a simplex pass that certified every scenario there is nothing to do (one scalar load per wave)
   if (a.skip_solved == 1 && __builtin_amdgcn_readfirstlane(*a.unsolved) == 0) return;
@@ -608,10 +615,11 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
     }                                                                                                       \
   }
 // reflected Halpern step toward the anchor (x0, y0)
-#define DSP_HALPERN_STEP()                                                                                  \
+/* anchor weight 1/(k+2): the bare v_rcp_f64 (no Newton step); Halpern needs the weight, not its last bits */
+#define DSP_ANCHOR_WEIGHT() __builtin_amdgcn_rcp((double)(k + 2))
+#define DSP_HALPERN_STEP(WEIGHT)                                                                            \
   {                                                                                                         \
-    /* anchor weight 1/(k+2): the bare v_rcp_f64 (no Newton step); Halpern needs the weight, not its last bits */ \
-    const double oml = __builtin_amdgcn_rcp((double)(k + 2));                                               \
+    const double oml = WEIGHT;                                                                              \
     _Pragma("unroll") for (int q = 0; q < CPL; ++q) {                                                       \
       const double t = 2.0 * xp[q] - x[q];                                                                  \
       x[q] = fma(oml, x0[q] - t, t);                                                                        \
@@ -647,11 +655,45 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
       // ---- plain iterations up to the next check: two SpMVs + elementwise work, no reduction, no branch --------
       const int plain = min(check_every - 1, max_it - it);
       DSP_PROF_MARK()
-      for (int u = 0; u < plain; ++u) {
-        DSP_PDHG_STEP()
-        ++k;
-        DSP_HALPERN_STEP()
-      }
+      // (today's loop: the anchor weight computed in every lane)
+#define DSP_PLAIN_ITERATIONS()                                                                              \
+  for (int u = 0; u < plain; ++u) {                                                                         \
+    DSP_PDHG_STEP()                                                                                         \
+    ++k;                                                                                                    \
+    DSP_HALPERN_STEP(DSP_ANCHOR_WEIGHT())                                                                   \
+  }
+      if constexpr (ANCHOR_TABLE) {
+        // (a flag, not if / else: written as else-branch the fallback loop gives the whole kernel another register allocation -
+        //  392 B of scratch instead of 384 - which is not the one that was measured; profiles/r83a_kernel_resources.txt)
+        bool computed = true;
+        // Every weight of the segment lies in the table (a wave-uniform choice): the plain iterations read it through the scalar data
+        // cache at a uniform address - no v_cvt_f64_i32 + v_rcp_f64, a quarter-rate VALU slot in all 64 lanes for one number per wave.
+        // The weights are the bits DSP_ANCHOR_WEIGHT() gives (anchor_weight_kernel, dsp_capi.hip).
+        // Scalar loads return through the counter of the LDS gathers, out of order: where the compiler knows one to be in flight it
+        // turns every counted wait of a product's FMA chain into a wait for ALL its gathers, and left to itself it issues the load
+        // right in front of its use.  So the load of the NEXT iteration's weight is written as the instruction, tied behind the
+        // second product's last result and in front of every use of this iteration's weight: it runs under the Halpern step and is
+        // waited for at the bottom of the body, where no gather is in flight (anchor_w has kAnchorWeights + 1 entries: the last
+        // iteration loads one it does not use).
+        if (k + plain <= kAnchorWeights) {
+          computed = false;
+          using cdbl = const __attribute__((address_space(4))) double;
+          cdbl *aw = (cdbl *)a.anchor_w + k;
+          double wk = aw[0];
+          asm volatile("" : "+s"(wk));                 // (waited for HERE: in flight at the loop's entry it costs the first product its counted waits)
+          for (int u = 0; u < plain; ++u) {
+            DSP_PDHG_STEP()
+            double wn;
+            asm volatile("s_load_dwordx2 %0, %2, 0x0" : "=&s"(wn), "+s"(wk) : "s"(aw + u + 1), "v"(yp[RPL - 1]));
+            DSP_HALPERN_STEP(wk)
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(wn), "+v"(y[RPL - 1]));
+            wk = wn;
+          }
+          k += plain;
+        }
+        if (computed) DSP_PLAIN_ITERATIONS()
+      } else DSP_PLAIN_ITERATIONS()
+#undef DSP_PLAIN_ITERATIONS
       DSP_PROF_ADD(0)
       it += plain;
       DSP_TRACE("[trace] it=%d k=%d\n", it, k);
@@ -1046,7 +1088,7 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
         }
       }
       ++it;
-      if (!moved) DSP_HALPERN_STEP()
+      if (!moved) DSP_HALPERN_STEP(DSP_ANCHOR_WEIGHT())
       DSP_PROF_ADD(5)
     }
 #undef DSP_PDHG_STEP
@@ -1054,6 +1096,7 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
 #undef DSP_SET_SCALARS
 #undef DSP_SET_MATRICES
 #undef DSP_HALPERN_STEP
+#undef DSP_ANCHOR_WEIGHT
 
     DSP_TRACE("[trace] store status=%d it=%d\n", status, it);
     if constexpr (!MATREG) if (a.skip_solved == 3) {
