@@ -1,4 +1,4 @@
-// dsp_capi.hip — the C ABI of include/dsp_hip.h: handle management, host-side preparation, launch geometry.
+// dsp_capi.hip — the solver handle of the C ABI (include/dsp_hip.h): dsp_create in pieces, launch geometry, dsp_solve in passes
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -6,27 +6,16 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
-#include "dsp_device.hpp"
-#include "dsp_loop_device.hpp"
+#include "dsp_capi_internal.hpp"
 #include "dsp_prepare.hpp"
 #include "dsp_rtc.hpp"
 #include "dsp_stream.hpp"
 
 using namespace dsp;
-
-static thread_local int g_last_hip_error = 0;
-
-#define HIP_TRY(expr)                                  \
-  do {                                                 \
-    hipError_t _e = (expr);                            \
-    if (_e != hipSuccess) {                            \
-      g_last_hip_error = (int)_e;                      \
-      return DSP_ERR_HIP;                              \
-    }                                                  \
-  } while (0)
 
 struct Geometry { int wpb = 1, blocks_per_cu = 1; size_t lds = 0; };
 
@@ -92,28 +81,21 @@ static int upload(dsp_handle *h, const std::vector<T> &v, const T **out) {
   return DSP_OK;
 }
 
-// pack a lane-major ELL (values + element indices) into the 16-byte device entries (byte offsets)
+// pack an ELL into the 16-byte device entries (byte offsets): from the element indices of the lane-major ELL, the offsets of the slot ELL
 static void pack_entries(const std::vector<double> &val, const std::vector<uint16_t> &idx, std::vector<Entry> &out) {
   out.resize(val.size());
   for (size_t i = 0; i < val.size(); ++i) { out[i].v = val[i]; out[i].off = (uint32_t)idx[i] * 8u; out[i].pad = 0; }
 }
-
 static void pack_entries(const std::vector<double> &val, const std::vector<uint32_t> &off, std::vector<Entry> &out) {
   out.resize(val.size());
   for (size_t i = 0; i < val.size(); ++i) { out[i].v = val[i]; out[i].off = off[i]; out[i].pad = 0; }
 }
 
-static int fill_long(LongList &L, const SlotELL &E) {
-  if ((int)E.long_owner_pos.size() > kMaxLong) return DSP_ERR_TOO_LARGE;
-  L.count = (int)E.long_owner_pos.size();
-  for (int i = 0; i < L.count; ++i) { L.owner[i] = E.long_owner_pos[i]; L.start[i] = E.long_start[i]; L.len[i] = E.long_len[i]; }
-  return DSP_OK;
-}
-
-static int fill_long(LongList &L, const LaneELL &E) {
-  if ((int)E.long_owner.size() > kMaxLong) return DSP_ERR_TOO_LARGE;
-  L.count = (int)E.long_owner.size();
-  for (int i = 0; i < L.count; ++i) { L.owner[i] = E.long_owner[i]; L.start[i] = E.long_start[i]; L.len[i] = E.long_len[i]; }
+template <class E>      // the long vectors of a layout (owners: vector ids in the lane ELL, positions in the slot ELL)
+static int fill_long(LongList &L, const std::vector<int32_t> &owner, const E &ell) {
+  if ((int)owner.size() > kMaxLong) return DSP_ERR_TOO_LARGE;
+  L.count = (int)owner.size();
+  for (int i = 0; i < L.count; ++i) { L.owner[i] = owner[i]; L.start[i] = ell.long_start[i]; L.len[i] = ell.long_len[i]; }
   return DSP_OK;
 }
 
@@ -152,10 +134,8 @@ static int solve_geometry(dsp_handle *h, int requested, int B, Geometry *g, int 
       size_t l = lds_bytes(h->P, wpb, matreg, h->cpl, h->rpl);
       if (l > (size_t)h->lds_limit) continue;
       int nb = 0;
-      hipError_t e = h->rtc_state[qp] == 1
-                         ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, h->rtc[qp].fn, 64 * wpb, l)
-                         : occupancy_solve(h->cpl, h->rpl, probe, 64 * wpb, l, &nb);
-      if (e != hipSuccess) { g_last_hip_error = (int)e; return DSP_ERR_HIP; }
+      HIP_TRY(h->rtc_state[qp] == 1 ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&nb, h->rtc[qp].fn, 64 * wpb, l)
+                                    : occupancy_solve(h->cpl, h->rpl, probe, 64 * wpb, l, &nb));
       if (nb * wpb > best_waves) { best_waves = nb * wpb; best.wpb = wpb; best.blocks_per_cu = nb; best.lds = l; }
     }
     if (best_waves <= 0) return DSP_ERR_TOO_LARGE;
@@ -170,77 +150,6 @@ static int solve_geometry(dsp_handle *h, int requested, int B, Geometry *g, int 
     if (wpb != g->wpb) { g->wpb = wpb; g->lds = lds_bytes(h->P, wpb, matreg, h->cpl, h->rpl); g->blocks_per_cu = std::max(1, per_cu / wpb); }
   }
   return DSP_OK;
-}
-
-// ---- rolling-horizon hand-off of the wind + battery double loop: one thread per plant ------------------------------------------
-// Every product is made opaque to the optimiser before it is added (loop_opaque, dsp_loop_device.hpp: no FMA contraction - the _rn
-// intrinsics are plain operators to the compiler and `#pragma clang fp contract(off)` did not keep it from fusing them): the results are
-// bit-identical to the element-wise tensor operations this kernel replaces (dispatches_amd/rolling.py, use_fused=False),
-// which is how it is tested.
-// outcome of the solve that has just finished, folded into the loop's device-side flags (what six tensor launches per solve did)
-template <class M, class S>
-__device__ __forceinline__ void loop_check(const S &s, const M &m, int b) {
-  if (m.status && s.bad && m.status[b] != 0) *s.bad = 1;
-  if (m.flags && s.uncertified && (m.flags[b] & DSP_FLAG_OBJ_WAIVED)) atomicAdd(reinterpret_cast<unsigned long long *>(s.uncertified), 1ull);
-}
-
-__global__ void __launch_bounds__(256) wb_rolling_kernel(dsp_wb_state s, dsp_wb_model rt, dsp_wb_model tr, int phase, int k) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= s.B) return;
-  const long long h = *s.hour, st0 = s.start[b];
-  auto win = [&](const double *series, int t) { return series[(st0 + h + t) % s.N]; };
-  if (phase == 0) {
-    const dsp_wb_model &m = rt;
-    const int known = min(m.T, 24 - k);
-    double *c = m.c + (size_t)b * m.n, *lb = m.lb + (size_t)b * m.n, *ub = m.ub + (size_t)b * m.n;
-    double avail_sum = 0.0;
-    for (int t = 0; t < m.T; ++t) {
-      const double rtp = win(s.rt_series, t);
-      const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : win(s.da_series, t);
-      const double r3 = loop_opaque(__dmul_rn(1e-3, rtp));
-      c[m.pt_cols[t][0]] = __dsub_rn(m.base_c[m.pt_cols[t][0]], r3);
-      c[m.pt_cols[t][1]] = __dsub_rn(m.base_c[m.pt_cols[t][1]], r3);
-      c[m.pda_cols[t]] = __dsub_rn(m.base_c[m.pda_cols[t]], loop_opaque(__dsub_rn(dap, rtp)));
-      const double avail = __dmul_rn(m.wind_kw, win(s.cf_series, t));
-      ub[m.wind_cols[t]] = avail;
-      avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
-      const double fix = t < known ? s.da_offer[(size_t)b * 24 + k + t] : 0.0;
-      lb[m.pda_cols[t]] = fix;
-      ub[m.pda_cols[t]] = t < known ? fix : INFINITY;
-    }
-    if (m.c0) m.c0[b] = __dadd_rn(m.c0_base, loop_opaque(__dmul_rn(m.waste_per_kw, avail_sum)));
-    lb[m.soc_init] = s.soc[b]; ub[m.soc_init] = s.soc[b];
-    lb[m.thr_init] = s.thr[b]; ub[m.thr_init] = s.thr[b];
-  } else if (phase == 1) {
-    loop_check(s, rt, b);
-    const double *xr = rt.x + (size_t)b * rt.n;
-    double *lb = tr.lb + (size_t)b * tr.n, *ub = tr.ub + (size_t)b * tr.n;
-    double *rlo = tr.rlo + (size_t)b * tr.m, *rhi = tr.rhi + (size_t)b * tr.m;
-    double avail_sum = 0.0;
-    for (int t = 0; t < tr.T; ++t) {
-      const double offer = __dmul_rn(1e-3, loop_opaque(__dadd_rn(xr[rt.pt_cols[t][0]], xr[rt.pt_cols[t][1]])));
-      rlo[tr.track_rows[t]] = offer;
-      rhi[tr.track_rows[t]] = offer;
-      const double avail = __dmul_rn(tr.wind_kw, win(s.cf_series, t));
-      ub[tr.wind_cols[t]] = avail;
-      avail_sum = t ? __dadd_rn(avail_sum, avail) : avail;
-    }
-    if (tr.c0) tr.c0[b] = __dadd_rn(tr.c0_base, loop_opaque(__dmul_rn(tr.waste_per_kw, avail_sum)));
-    lb[tr.soc_init] = s.soc[b]; ub[tr.soc_init] = s.soc[b];
-    lb[tr.thr_init] = s.thr[b]; ub[tr.thr_init] = s.thr[b];
-  } else {
-    loop_check(s, tr, b);
-    const double *x = tr.x + (size_t)b * tr.n;
-    const double delivered = loop_opaque(__dmul_rn(1e-3, loop_opaque(__dadd_rn(x[tr.pt_cols[0][0]], x[tr.pt_cols[0][1]]))));
-    const double rt0 = win(s.rt_series, 0);
-    s.delivered[b] = delivered;
-    s.soc[b] = __ddiv_rn(rint(loop_opaque(__dmul_rn(x[tr.soc0], 100.0))), 100.0);
-    s.thr[b] = __ddiv_rn(rint(loop_opaque(__dmul_rn(x[tr.thr0], 100.0))), 100.0);
-    const double dao = s.da_offer[(size_t)b * 24 + k], dap = s.da_prices[(size_t)b * 24 + k];
-    const double t1 = loop_opaque(__dmul_rn(delivered, rt0)), t2 = loop_opaque(__dmul_rn(dao, loop_opaque(__dsub_rn(dap, rt0))));
-    s.revenue[b] = __dadd_rn(s.revenue[b], loop_opaque(__dadd_rn(t1, t2)));
-    s.energy_mwh[b] = __dadd_rn(s.energy_mwh[b], delivered);
-  }
 }
 
 // Zeroes the few ints of a work-queue slot before a solve.  A KERNEL, not hipMemsetAsync: captured into a hipGraph (the rolling loop
@@ -258,315 +167,375 @@ __global__ void __launch_bounds__(256) anchor_weight_kernel(double *w, int count
   for (int j = threadIdx.x; j < count; j += blockDim.x) w[j] = __builtin_amdgcn_rcp((double)(j + 1 + 2));
 }
 
-// the clock advances AFTER every plant has read it (own launch: stream order is the barrier)
-__global__ void wb_clock_kernel(long long *hour) { *hour += 1; }
+// ---- dsp_create in pieces that return a DSP_* code (dsp_create alone decides what becomes of the handle).  First the CSR, before any HIP call
+static bool desc_ok(const dsp_lp_desc *d) {
+  if (!d || d->n <= 0 || d->m < 0 || d->nnz < 0 || !d->A_rowptr || (d->nnz && (!d->A_colidx || !d->A_val))) return false;
+  if (d->A_rowptr[0] != 0 || d->A_rowptr[d->m] != d->nnz) return false;
+  for (int i = 0; i < d->m; ++i) {
+    if (d->A_rowptr[i + 1] < d->A_rowptr[i]) return false;
+    for (int p = d->A_rowptr[i]; p < d->A_rowptr[i + 1]; ++p) {
+      if (d->A_colidx[p] < 0 || d->A_colidx[p] >= d->n) return false;
+      if (p > d->A_rowptr[i] && d->A_colidx[p] <= d->A_colidx[p - 1]) return false;
+      if (!std::isfinite(d->A_val[p])) return false;
+    }
+  }
+  if (d->col_scale)
+    for (int j = 0; j < d->n; ++j)
+      if (!(d->col_scale[j] > 0.0) || !std::isfinite(d->col_scale[j])) return false;
+  return true;
+}
 
-// ---- the same hand-off for a flowsheet given by a descriptor (include/dsp_hip.h: dsp_loop_model / dsp_loop_state) ------------------------
-__device__ __forceinline__ double loop_power(const dsp_loop_model &m, const double *x, int t) {
-  double p = m.pt_const[t];
-  if (m.pt_cols[t][0] >= 0) p = fma(m.pt_coef[t][0], x[m.pt_cols[t][0]], p);
-  if (m.pt_cols[t][1] >= 0) p = fma(m.pt_coef[t][1], x[m.pt_cols[t][1]], p);
-  return p;
+// LP beyond the register/LDS-resident kernels (n > 640 or m > 384): HBM-resident PDLP
+static int create_streaming(dsp_handle *h, const HostCSR &A, const HostCSR &AT) {
+  int rc;
+  h->streaming = 1; h->cpl = h->rpl = 0; h->P.n = h->n; h->P.m = h->m;
+  if ((rc = upload(h, h->dc, &h->P.col_scale)) != DSP_OK || (rc = upload(h, h->dr, &h->P.row_scale)) != DSP_OK) return rc;
+  hipError_t se = stream_create(A, AT, h->P.col_scale, h->P.row_scale, &h->stream);
+  if (se != hipSuccess) { g_last_hip_error = (int)se; return se == hipErrorInvalidValue ? DSP_ERR_TOO_LARGE : DSP_ERR_HIP; }
+  return DSP_OK;
 }
-__device__ __forceinline__ void loop_state_and_wind(const dsp_loop_state &s, const dsp_loop_model &m, int b, long long h, long long st0, double c0) {
-  double *lb = m.lb + (size_t)b * m.n, *ub = m.ub + (size_t)b * m.n;
-  for (int j = 0; j < m.n_state; ++j) {
-    const double v = s.state[(size_t)b * m.n_state + j];
-    lb[m.state_init[j]] = v; ub[m.state_init[j]] = v;
+
+// fused kernels: lane ELL, sorted layout with its slot ELLs, kernel choice, slot permutation, then the device copies in the order of h->P's fields
+static int create_fused(dsp_handle *h, const HostCSR &A, const HostCSR &AT, const HostCSR &Au, const HostCSR &ATu) {
+  const int cpl = h->cpl, rpl = h->rpl;
+  LaneELL Er = build_lane_ell(A, rpl), Ec = build_lane_ell(AT, cpl);
+  // unscaled values in the SAME layout (same sparsity => same W / long split)
+  LaneELL Eru = build_lane_ell(Au, rpl), Ecu = build_lane_ell(ATu, cpl);
+  DeviceProblem &P = h->P;
+  P.n = h->n; P.m = h->m; P.n_pad = cpl * 64; P.m_pad = rpl * 64; P.Wc = Ec.W; P.Wr = Er.W;
+  P.ellc_entries = (int)Ec.val.size(); P.ellr_entries = (int)Er.val.size();
+  P.tailc_entries = (int)Ec.tail_val.size(); P.tailr_entries = (int)Er.tail_val.size();
+  int rc;
+  if ((rc = fill_long(P.long_c, Ec.long_owner, Ec)) || (rc = fill_long(P.long_r, Er.long_owner, Er))) return rc;
+  // register-resident-matrix layout: ownership sorted by length, per-slot widths, position space
+  SortedLayout Lc = sorted_layout(AT, cpl, Ec.long_owner), Lr = sorted_layout(A, rpl, Er.long_owner);
+  SlotELL Sc = build_slot_ell(AT, Lc, Lr, Ec.long_owner), Sr = build_slot_ell(A, Lr, Lc, Er.long_owner);
+  const bool has_long = P.long_c.count > 0 || P.long_r.count > 0; int pad_w = 0;
+  // no ahead-of-time specialisation for this shape: compile the tight one now (hiprtc, disk-cached).  Limits: RegEll packs
+  // at most 8 slots of width <= 15, and beyond ~32 register-resident entries per lane the kernel would live in scratch.
+  const bool aot_lp = matreg_available(cpl, rpl, Sc.pack, Sr.pack, has_long) != 0;
+  const bool aot_qp = matreg_available(cpl, rpl, Sc.pack, Sr.pack, has_long, true) != 0;
+  int wmax = 0;                                     // the widest slot of the tight layout
+  for (int q = 0; q < Sc.slots; ++q) wmax = std::max(wmax, Sc.width[q]);
+  for (int q = 0; q < Sr.slots; ++q) wmax = std::max(wmax, Sr.width[q]);
+  bool rtc_ok = false;
+  if (!h->opt.no_matreg && !h->opt.no_rtc && !aot_lp && cpl <= 8 && rpl <= 8 && Sc.total + Sr.total <= 32 && wmax <= 15) {
+    rtc_ok = rtc_get_kernel(h->device, cpl, rpl, has_long, Sc.pack, Sr.pack, false, &h->rtc[0], &h->rtc_why);
+    if (rtc_ok) { h->rtc_state[0] = 1; h->rtc_long = has_long; if (!aot_qp && !has_long) h->rtc_state[1] = -1; }
   }
-  if (m.wind_cols[0] >= 0) {
-    const double kw = m.wind_kw_plant ? m.wind_kw_plant[b] : m.wind_kw;     // per-plant size (ABI 16) at the site of the scalar
-    double sum = 0.0;
-    for (int t = 0; t < m.T; ++t) {
-      const double avail = kw * s.cf_series[(st0 + h + t) % s.N];
-      ub[m.wind_cols[t]] = avail;
-      sum += avail;
-    }
-    c0 = fma(m.waste_per_kw, sum, c0);
+  // no tight specialisation for this shape: the PADDED one (every slot kPadWidth wide) if the LP fits it
+  if (!h->opt.no_matreg && !aot_lp && !aot_qp && !rtc_ok && !has_long && wmax <= kPadWidth &&
+      matreg_available(cpl, rpl, uniform_pack(cpl, kPadWidth), uniform_pack(rpl, kPadWidth), false)) {
+    pad_w = kPadWidth;
+    Sc = build_slot_ell(AT, Lc, Lr, Ec.long_owner, pad_w);
+    Sr = build_slot_ell(A, Lr, Lc, Er.long_owner, pad_w);
   }
-  m.c0[b] = c0;
+  // the unscaled matrix in the same position-space layout (same sparsity): streaming SpMV step
+  SlotELL Scu = build_slot_ell(ATu, Lc, Lr, Ec.long_owner, pad_w), Sru = build_slot_ell(Au, Lr, Lc, Er.long_owner, pad_w);
+  // bank-conflict-minimising slot permutation of each exchange buffer: the y buffer is gathered by the A^T entries
+  // (Sc), the x buffer by the A entries (Sr)
+  const bool shared_slots = shared_slot_maps(cpl, rpl);
+  SlotMap My = optimise_slots(Sc, P.m_pad, 4000, shared_slots), Mx = optimise_slots(Sr, P.n_pad, 4000, shared_slots);
+  h->lds_conflicts[0] = My.cost_identity; h->lds_conflicts[1] = My.cost_final;
+  h->lds_conflicts[2] = Mx.cost_identity; h->lds_conflicts[3] = Mx.cost_final;
+  apply_slots(Sc, My.slot); apply_slots(Scu, My.slot);
+  apply_slots(Sr, Mx.slot); apply_slots(Sru, Mx.slot);
+  // LDS byte offset of every natural element: column j sits at position Lc.pos[j], whose exchange slot is Mx.slot[...]
+  std::vector<int32_t> nat_x((size_t)P.n_pad, 0), nat_y((size_t)P.m_pad, 0);
+  for (int j = 0; j < h->n; ++j) nat_x[j] = 8 * Mx.slot[Lc.pos[j]];
+  for (int i = 0; i < h->m; ++i) nat_y[i] = 8 * My.slot[Lr.pos[i]];
+  P.mr_wc_pack = Sc.pack; P.mr_wr_pack = Sr.pack; P.mr_tailc_entries = (int)Sc.tail_val.size(); P.mr_tailr_entries = (int)Sr.tail_val.size();
+  if ((rc = fill_long(P.mr_long_c, Sc.long_owner_pos, Sc)) || (rc = fill_long(P.mr_long_r, Sr.long_owner_pos, Sr))) return rc;
+  h->matreg = h->opt.no_matreg ? 0 : (rtc_ok ? 1 : matreg_available(cpl, rpl, Sc.pack, Sr.pack, has_long));
+  h->matreg_qp = h->opt.no_matreg ? 0 : matreg_available(cpl, rpl, Sc.pack, Sr.pack, has_long, true);
+  // the uploads: packed entries (ent) and plain vectors (vec); the first failure ends the list
+  std::vector<Entry> pk;
+  auto ent = [&](const std::vector<double> &val, const auto &idx, const Entry **field) {
+    if (rc == DSP_OK) { pack_entries(val, idx, pk); rc = upload(h, pk, field); }
+  };
+  auto vec = [&](const auto &v, auto field) { if (rc == DSP_OK) rc = upload(h, v, field); };
+  ent(Ec.val, Ec.idx, &P.ellc); ent(Er.val, Er.idx, &P.ellr); ent(Ec.tail_val, Ec.tail_idx, &P.tailc); ent(Er.tail_val, Er.tail_idx, &P.tailr);
+  ent(Ecu.val, Ecu.idx, &P.ellc_unscaled); ent(Eru.val, Eru.idx, &P.ellr_unscaled);
+  ent(Ecu.tail_val, Ecu.tail_idx, &P.tailc_unscaled); ent(Eru.tail_val, Eru.tail_idx, &P.tailr_unscaled);
+  vec(h->dc, &P.col_scale); vec(h->dr, &P.row_scale);
+  ent(Sc.val, Sc.off, &P.mr_ellc); ent(Sr.val, Sr.off, &P.mr_ellr); ent(Sc.tail_val, Sc.tail_off, &P.mr_tailc); ent(Sr.tail_val, Sr.tail_off, &P.mr_tailr);
+  vec(Lc.at, &P.mr_colat); vec(Lr.at, &P.mr_rowat); vec(Mx.slot, &P.mr_slot_x); vec(My.slot, &P.mr_slot_y);
+  ent(Scu.val, Scu.off, &P.mr_ellc_unscaled); ent(Sru.val, Sru.off, &P.mr_ellr_unscaled);
+  ent(Scu.tail_val, Scu.tail_off, &P.mr_tailc_unscaled); ent(Sru.tail_val, Sru.tail_off, &P.mr_tailr_unscaled);
+  vec(nat_x, &P.mr_nat_slot_x); vec(nat_y, &P.mr_nat_slot_y);
+  return rc;
 }
-__global__ void __launch_bounds__(256) loop_update_kernel(dsp_loop_state s, dsp_loop_model rt, dsp_loop_model tr, int phase, int k) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= s.B) return;
-  const long long h = *s.hour, st0 = s.start[b];
-  auto win = [&](const double *series, int t) { return series[(st0 + h + t) % s.N]; };
-  if (phase == 0) {
-    const dsp_loop_model &m = rt;
-    const int known = min(m.T, 24 - k);
-    double *c = m.c + (size_t)b * m.n, *lb = m.lb + (size_t)b * m.n, *ub = m.ub + (size_t)b * m.n;
-    double c0 = m.c0_base_plant ? m.c0_base_plant[b] : m.c0_base;
-    for (int t = 0; t < m.T; ++t) {
-      const double rtp = win(s.rt_series, t);
-      const double dap = t < known ? s.da_prices[(size_t)b * 24 + k + t] : win(s.da_series, t);
-      for (int e = 0; e < 2; ++e)
-        if (m.pt_cols[t][e] >= 0) c[m.pt_cols[t][e]] = fma(-rtp, m.pt_coef[t][e], m.base_c[m.pt_cols[t][e]]);
-      c[m.pda_cols[t]] = m.base_c[m.pda_cols[t]] - (dap - rtp);
-      c0 = fma(-rtp, m.pt_const[t], c0);
-      const double fix = t < known ? s.da_offer[(size_t)b * 24 + k + t] : 0.0;
-      lb[m.pda_cols[t]] = fix;
-      ub[m.pda_cols[t]] = t < known ? fix : INFINITY;
+
+// the small device objects of a fused handle: dense matrix for the simplex of tiny LPs, queue ring, anchor-weight table, light follow-up probe
+static int create_device_objects(dsp_handle *h, const HostCSR &A) {
+  if (!h->opt.no_simplex && h->n + h->m <= 128 && h->m <= 64 && h->m >= 1) {
+    h->sx_lds = simplex_lds_bytes(h->n, h->m, &h->sx_row_stride);
+    if (h->sx_lds <= (size_t)h->lds_limit) {
+      std::vector<double> dense((size_t)h->m * h->n, 0.0);
+      for (int i = 0; i < A.m; ++i)
+        for (int p = A.ptr[i]; p < A.ptr[i + 1]; ++p) dense[(size_t)i * h->n + A.idx[p]] = A.val[p];
+      if (int rc = upload(h, dense, &h->A_dense)) return rc;
+      h->simplex = 1;
     }
-    loop_state_and_wind(s, m, b, h, st0, c0);
-  } else if (phase == 1) {
-    loop_check(s, rt, b);
-    const double *xr = rt.x + (size_t)b * rt.n;
-    double *rlo = tr.rlo + (size_t)b * tr.m, *rhi = tr.rhi + (size_t)b * tr.m;
-    for (int t = 0; t < tr.T; ++t) {
-      const double rhs = loop_power(rt, xr, t) - tr.pt_const[t];       // real-time offer = SCED dispatch in the stub market
-      rlo[tr.track_rows[t]] = rhs;
-      rhi[tr.track_rows[t]] = rhs;
-    }
-    loop_state_and_wind(s, tr, b, h, st0, tr.c0_base_plant ? tr.c0_base_plant[b] : tr.c0_base);
-  } else {
-    loop_check(s, tr, b);
-    const double *x = tr.x + (size_t)b * tr.n;
-    const double delivered = loop_power(tr, x, 0);
-    const double rt0 = win(s.rt_series, 0);
-    s.delivered[b] = delivered;
-    for (int j = 0; j < tr.n_state; ++j)                              // implemented profile -> next hour's state, rounded as update_model does
-      s.state[(size_t)b * tr.n_state + j] = rint(x[tr.state_real[j]] * s.state_scale[j]) / s.state_scale[j];
-    const double dao = s.da_offer[(size_t)b * 24 + k], dap = s.da_prices[(size_t)b * 24 + k];
-    s.revenue[b] += delivered * rt0 + dao * (dap - rt0);
-    s.energy_mwh[b] += delivered;
   }
+  const size_t ring = sizeof(int) * kQueueRing * kQueueStride;
+  if (hipMalloc((void **)&h->queue, ring) != hipSuccess || hipMemset(h->queue, 0, ring) != hipSuccess) return DSP_ERR_HIP;
+  // (+ 1: the table loop loads the weight of the iteration after its last one, dsp_kernels.hip)
+  void *aw = nullptr;
+  if (hipMalloc(&aw, sizeof(double) * (kAnchorWeights + 1)) != hipSuccess) return DSP_ERR_HIP;
+  h->allocs.push_back(aw); h->anchor_w = (const double *)aw;
+  hipLaunchKernelGGL(anchor_weight_kernel, dim3(1), dim3(256), 0, (hipStream_t)0, (double *)aw, kAnchorWeights + 1);
+  // (solves run on the caller's streams, which need not wait for the null stream)
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize((hipStream_t)0) != hipSuccess) return DSP_ERR_HIP;
+  if (h->matreg && h->rtc_state[0] != 1) {
+    // follow-up passes behind a three-wave first pass: the runtime's occupancy answer for a one-wave block of the light kernel with the
+    // LDS matrix decides (on the 24-h LP about 27 KB, beside eleven first-pass blocks of about 8 KB in the CU's 160 KB); 0 = as before
+    SolveArgs first{}; first.P = h->P; first.matreg = 1; first.qp = 0;
+    const size_t l = lds_bytes(h->P, 1, 0, h->cpl, h->rpl);
+    if (l <= (size_t)h->lds_limit && light_followup_blocks(h->cpl, h->rpl, first, l) > 0) h->light_lds = l;
+  }
+  return DSP_OK;
+}
+
+// ---- dsp_solve in passes, none of which allocates per solve.  First the options this solve runs under (a->opt, a->eta, a->qp)
+static int resolve_options(const dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, SolveArgs *a) {
+  a->P = h->P; a->b = *batch; a->anchor_w = h->anchor_w;
+  a->opt = opt ? *opt : h->opt;
+  const dsp_options &o = a->opt;
+  if (o.max_iter < 1 || o.check_every < 0 || o.kkt_every < 0 || !(o.kkt_gate >= 0) || o.stall_rescue < 0 || o.polish_patience < 0 || !(o.jump_rel >= 0) ||
+      !(o.eps_rel > 0) || !(o.eps_obj >= 0) || !(o.eps_infeasible >= 0) || !(o.pid_kp >= 0) || !(o.restart_artificial >= 0) || !(o.step_scale > 0))
+    return DSP_ERR_INVALID;
+  a->eta = o.step_scale * h->eta_unit;
+  a->qp = batch->row_compliance != nullptr;
+  // 0 = automatic (include/dsp_hip.h): the fused float64 kernels restart their Halpern epochs earlier and steer the primal
+  // weight more gently than the HBM-resident and float32 paths, which keep the values they were tuned with
+  const bool fused64 = !h->streaming && o.precision == 0;
+  if (o.restart_artificial == 0.0) a->opt.restart_artificial = fused64 ? (a->qp ? 0.3 : 0.2) : 0.36;
+  if (o.pid_kp == 0.0) a->opt.pid_kp = fused64 ? 0.6 : 0.7;
+  if (o.precision != 0 && o.precision != 1) return DSP_ERR_INVALID;
+  // float32 iterates exist in the fused kernels only; soft rows in the fused kernels without long vectors and in the
+  // HBM-resident streaming form
+  const bool has_long = h->P.long_c.count > 0 || h->P.long_r.count > 0;
+  if (o.precision && (h->streaming || has_long)) return DSP_ERR_INVALID;
+  if (a->qp && !h->streaming && has_long) return DSP_ERR_INVALID;
+  return DSP_OK;
+}
+
+// the one read-back, for a caller that waits for the statistics: synchronise, kernel time between the handle's events, status / iteration tallies
+static int finish_stats(dsp_handle *h, const dsp_batch *batch, dsp_stats *stats, bool timed, hipStream_t st) {
+  if (!timed) return DSP_OK;
+  const int B = batch->B;
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, h->ev0, h->ev1));
+  std::vector<int32_t> hs(B), hi(B);
+  HIP_TRY(hipMemcpy(hs.data(), batch->status, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (batch->iters) HIP_TRY(hipMemcpy(hi.data(), batch->iters, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int i = 0; i < B; ++i) {
+    stats->n_optimal += hs[i] == DSP_STATUS_OPTIMAL;
+    if (batch->iters) { stats->total_iterations += hi[i]; stats->max_iterations = std::max(stats->max_iterations, hi[i]); }
+  }
+  return DSP_OK;
+}
+
+// block size of the follow-up passes (certificates, re-certification; the generic kernel): a few waves per block share the LDS matrix (the
+// passes are rare, not tuned), or one-wave blocks of its light instantiation.  wpb = 0: no geometry fits
+struct Followup { bool light = false; int wpb = 0; size_t lds = 0; };
+static Followup followup_geometry(const dsp_handle *h, bool light) {
+  Followup f{light};
+  for (int wpb = 1; wpb <= 4 && !light; ++wpb) {
+    const size_t l = lds_bytes(h->P, wpb, 0, h->cpl, h->rpl);
+    if (l <= (size_t)h->lds_limit) { f.wpb = wpb; f.lds = l; }
+  }
+  if (light) { f.wpb = 1; f.lds = h->light_lds; }
+  return f;
+}
+static hipError_t launch_followup(const dsp_handle *h, Followup f, const SolveArgs &first, const SolveArgs &c, int grid, hipStream_t st) {
+  return f.light ? launch_solve_light(h->cpl, h->rpl, first, c, grid, f.lds, st)
+                 : launch_solve(h->cpl, h->rpl, c, dim3(grid), dim3(64 * f.wpb), f.lds, st);
+}
+
+// the next slot of the handle's ring, its first `ints` ints zeroed on the stream: one per solve of the float32 and fused paths
+static int *claim_queue_slot(dsp_handle *h, hipStream_t st, int ints) {
+  int *q = h->queue + (size_t)(h->queue_next.fetch_add(1u) % kQueueRing) * kQueueStride;
+  hipLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, st, q, ints);
+  return q;
+}
+
+static int solve_streaming(dsp_handle *h, const dsp_batch *batch, const SolveArgs &a, dsp_stats *stats, bool timed, hipStream_t st) {
+  if (timed) HIP_TRY(hipEventRecord(h->ev0, st));
+  int periods = 0;
+  HIP_TRY(stream_solve(&h->stream, *batch, a.opt, a.eta, st, &periods));
+  if (timed) HIP_TRY(hipEventRecord(h->ev1, st));
+  stats->streaming = 1; stats->quadratic = a.qp;
+  stats->grid_blocks = (std::max(h->n, h->m) + 255) / 256; stats->block_threads = 256;
+  stats->stream_bytes_per_iteration = (int64_t)stream_bytes_per_iteration(&h->stream);
+  stats->stream_form = h->stream.last_form;
+  stats->stream_phases = (h->stream.last_form == DSP_STREAM_FORM_LANE || h->stream.last_form == DSP_STREAM_FORM_IPM) ? h->stream.last_phases : 0;
+  stats->ipm_solved = h->stream.last_ipm_solved;
+  return finish_stats(h, batch, stats, timed, st);
+}
+
+// float32 iterates (tolerance sweep of BASELINE config 5): its own kernel, one scenario per wave, LDS-resident matrix
+static int solve_f32(dsp_handle *h, const dsp_batch *batch, SolveArgs &a, dsp_stats *stats, bool timed, hipStream_t st) {
+  a.queue = claim_queue_slot(h, st, 2);
+  if (timed) HIP_TRY(hipEventRecord(h->ev0, st));
+  int grid = 0, threads = 0; size_t lds = 0;
+  HIP_TRY(launch_solve_f32(h->cpl, h->rpl, a, h->num_cus, (size_t)h->lds_limit, st, &grid, &threads, &lds));
+  if (timed) HIP_TRY(hipEventRecord(h->ev1, st));
+  stats->grid_blocks = grid; stats->block_threads = threads; stats->lds_bytes = (int)lds;
+  stats->cols_per_lane = h->cpl; stats->rows_per_lane = h->rpl; stats->quadratic = a.qp; stats->precision = 1;
+  return finish_stats(h, batch, stats, timed, st);
+}
+
+// (allocated outside any stream capture: the rolling loops run their first day eagerly)
+static int grow_simplex_warm(dsp_handle *h, int B) {
+  const size_t N = (size_t)h->n + h->m;
+  double *t = nullptr; int *bs = nullptr, *vl = nullptr; unsigned char *up = nullptr;
+  HIP_TRY(hipMalloc((void **)&t, (size_t)B * h->m * N * sizeof(double))); h->sx_warm_allocs.push_back(t);
+  HIP_TRY(hipMalloc((void **)&bs, (size_t)B * h->m * sizeof(int))); h->sx_warm_allocs.push_back(bs);
+  HIP_TRY(hipMalloc((void **)&up, (size_t)B * N)); h->sx_warm_allocs.push_back(up);
+  HIP_TRY(hipMalloc((void **)&vl, (size_t)B * sizeof(int))); h->sx_warm_allocs.push_back(vl);
+  HIP_TRY(hipMemset(vl, 0, (size_t)B * sizeof(int)));
+  h->sx_warm_T = t; h->sx_warm_basis = bs; h->sx_warm_upper = up; h->sx_warm_valid = vl; h->sx_warm_cap = B;
+  return DSP_OK;
+}
+
+// simplex pass: certified vertices get their final status; DSP_STATUS_UNSOLVED marks what the PDLP kernel still has to do
+static int simplex_pass(dsp_handle *h, SolveArgs &a, hipStream_t st) {
+  if (!h->simplex || a.qp) return DSP_OK;
+  const int B = a.b.B;
+  SimplexArgs sa{};
+  sa.n = h->n; sa.m = h->m; sa.row_stride = h->sx_row_stride; sa.max_pivots = 20 * (h->n + h->m);
+  sa.A_dense = h->A_dense; sa.col_scale = h->P.col_scale; sa.row_scale = h->P.row_scale; sa.b = a.b;
+  sa.tol_p = 1e-10; sa.tol_d = 1e-12; sa.tol_piv = 1e-9; sa.unsolved = a.queue + 1;
+  { static const char *tp = getenv("DSP_SX_TOLP"); if (tp) sa.tol_p = atof(tp); }      // (development)
+  if (a.opt.simplex_warm == 1 || a.opt.simplex_warm == 2) {
+    if (B > h->sx_warm_cap)
+      if (int rc = grow_simplex_warm(h, B)) return rc;
+    sa.warm = a.opt.simplex_warm;
+    sa.warm_T = h->sx_warm_T; sa.warm_basis = h->sx_warm_basis; sa.warm_upper = h->sx_warm_upper; sa.warm_valid = h->sx_warm_valid;
+  }
+  static const int sx_debug = getenv("DSP_SX_DEBUG") ? atoi(getenv("DSP_SX_DEBUG")) : 0;
+  sa.debug_keep = sx_debug;
+  const int per_cu = std::max<int>(1, std::min<int>(32, (int)((size_t)h->lds_limit / h->sx_lds)));
+  HIP_TRY(launch_simplex(sa, std::min(B, h->num_cus * per_cu), h->sx_lds, st));
+  a.skip_solved = 1;
+  return DSP_OK;
+}
+
+// first pass: the run-time compiled module where the shape has one, the ahead-of-time kernels otherwise
+static hipError_t first_pass(dsp_handle *h, SolveArgs &a, int grid, size_t lds, hipStream_t st) {
+  if (!(h->rtc_state[a.qp] == 1 && a.matreg)) return launch_solve(h->cpl, h->rpl, a, dim3(grid), dim3(64 * a.waves_per_block), lds, st);
+  size_t arg_size = sizeof(a);
+  void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &arg_size, HIP_LAUNCH_PARAM_END};
+  return hipModuleLaunchKernel(h->rtc[a.qp].fn, grid, 1, 1, 64 * a.waves_per_block, 1, 1, (unsigned)lds, st, nullptr, config);
+}
+
+// Certificate pass: the register-resident kernels only WATCH for scenarios whose objectives keep drifting apart and leave them
+// DSP_STATUS_SUSPECT; the generic kernel - which evaluates the infeasibility / unboundedness certificates at its restarts -
+// continues those from their iterate (x0 / y0 = the outputs of the first pass).  One more launch per solve that returns at
+// its first line when the device-side count of suspects is 0: every feasible batch.
+static int certificate_pass(dsp_handle *h, const SolveArgs &a, Followup f, bool host_waits, hipStream_t st) {
+  if (!a.matreg || !(a.opt.eps_infeasible > 0.0)) return DSP_OK;
+  SolveArgs c = a;
+  c.matreg = 0; c.skip_solved = 2; c.queue = a.queue + 3;
+  c.b.x0 = a.b.x; c.b.y0 = a.b.y; c.waves_per_block = f.wpb;
+  // How many blocks: a caller that waits for the statistics anyway (sync_stats) lets the host read the count of suspects after the
+  // first pass - no launch at all on a feasible batch, one block per suspect otherwise.  Asynchronous callers (pipelined batches,
+  // the rolling loop's graphs) get a launch of 8 blocks that returns at its first line when there is no suspect: with one block
+  // per CU it cost the pipelined metric batch 1.2 % (every block needs a free 256-VGPR wave slot before it can even return), with
+  // 8 blocks 0.5 %, without the pass 0 (profiles/r51d_cert_pass_cost.log); 32 waves are plenty for the rare suspect.
+  static const int cert_grid_env = getenv("DSP_CERT_GRID") ? atoi(getenv("DSP_CERT_GRID")) : 0;      // development: blocks of the pass
+  int nsus = -1;
+  if (host_waits) {
+    HIP_TRY(hipMemcpyAsync(&nsus, a.suspects, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if (nsus == 0) return DSP_OK;
+  const int want = nsus > 0 ? (nsus + f.wpb - 1) / f.wpb : (cert_grid_env > 0 ? cert_grid_env : 8);
+  HIP_TRY(launch_followup(h, f, a, c, std::max(1, std::min(std::min((a.b.B + f.wpb - 1) / f.wpb, want), 2 * h->num_cus)), st));
+  return DSP_OK;
+}
+
+// Re-certification passes (dsp_options::recertify_passes): scenarios the passes above accepted with DSP_FLAG_OBJ_WAIVED - the objective-error
+// bound stuck within 10 eps_obj while the objective itself had stopped - are solved again from a cold start under another restart
+// cadence / weight controller, on the device, by the generic kernel; a certified optimum replaces the flagged point, anything else
+// leaves it (and its flag) in place.  Each pass returns at its first line when the device-side count of flagged scenarios is 0:
+// almost every batch (one flagged solve in the 147 M of a simulated year of the rolling loop).  What HipPdlpSolver._recertify does
+// from the host for synchronous callers, for callers that never look (hipGraph replays, pipelined batches).
+static int recertify_passes(dsp_handle *h, const SolveArgs &a, Followup f, hipStream_t st) {
+  if (!(a.opt.recertify_passes > 0 && a.b.flags)) return DSP_OK;
+  static const struct { double pid_kp, restart_artificial; int check_every; } kRecertify[3] = {{0.45, 0.3, 0}, {0.8, 0.15, 0}, {0.3, 0.5, 12}};
+  for (int v = 0; f.wpb && v < std::min(a.opt.recertify_passes, 3); ++v) {
+    SolveArgs c = a;
+    c.matreg = 0; c.skip_solved = 3; c.queue = a.queue + 5 + v;
+    c.b.x0 = nullptr; c.b.y0 = nullptr; c.waves_per_block = f.wpb;
+    c.opt.pid_kp = kRecertify[v].pid_kp; c.opt.restart_artificial = kRecertify[v].restart_artificial;
+    if (kRecertify[v].check_every) c.opt.check_every = kRecertify[v].check_every;
+    c.opt.polish_patience = std::max(c.opt.polish_patience, 1024);       // (a pass that waives as readily as the first certifies nothing)
+    HIP_TRY(launch_followup(h, f, a, c, std::max(1, std::min((a.b.B + f.wpb - 1) / f.wpb, 64)), st));
+  }
+  return DSP_OK;
+}
+
+static int solve_fused(dsp_handle *h, const dsp_batch *batch, SolveArgs &a, dsp_stats *stats, bool timed, hipStream_t st) {
+  const int B = batch->B, qp = a.qp;
+  if (qp && h->rtc_state[1] == -1) {
+    // first QP solve on a run-time specialised shape: compile its QP instantiation (the layout is the tight one already)
+    h->rtc_state[1] = rtc_get_kernel(h->device, h->cpl, h->rpl, false, h->P.mr_wc_pack, h->P.mr_wr_pack, true, &h->rtc[1], &h->rtc_why) ? 1 : 0;
+    if (h->rtc_state[1] == 1) h->matreg_qp = 1;
+  }
+  Geometry geo;
+  int rc = solve_geometry(h, a.opt.waves_per_block, B, &geo, qp);
+  if (rc != DSP_OK) return rc;
+  a.waves_per_block = geo.wpb; a.queue = claim_queue_slot(h, st, 8);
+  a.queue_base = 0u; a.unsolved = a.queue + 1;
+  a.suspects = a.queue + 2;                          // (+ 3: the work-queue head of the certificate pass; + 4: count of scenarios flagged
+                                                     //  DSP_FLAG_OBJ_WAIVED; + 5 .. 7: heads of the re-certification passes)
+  a.matreg = qp ? h->matreg_qp : h->matreg;
+#ifdef DSP_KKT_TRACE
+  const char *trace_env = getenv("DSP_TRACE_SCENARIO");
+  double *trace_dev = nullptr;
+  if (trace_env) {
+    HIP_TRY(hipMalloc((void **)&trace_dev, 4096 * 12 * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(trace_dev, 0, 4096 * 12 * sizeof(double), st));
+    a.trace = trace_dev; a.trace_scenario = atoi(trace_env);
+  }
+#endif
+  const int grid = std::min((B + geo.wpb - 1) / geo.wpb, h->num_cus * geo.blocks_per_cu);
+  // geometry of the follow-up passes, fixed BEFORE the first pass runs: a register-resident kernel may only leave scenarios
+  // DSP_STATUS_SUSPECT if the generic kernel that takes them over can be launched (it always can for an LP of the fused path - it is
+  // the fallback of every shape -; if not, the first pass keeps every scenario and the certificates are off for this call)
+  // Behind a three-wave first pass (168 VGPRs a wave, 504 of a SIMD's 512) the follow-up passes - certificates and re-certification -
+  // are one-wave blocks of the light instantiation: each fits the registers ONE leaving first-pass wave sets free.  A 256-VGPR wave
+  // needs two of a SIMD's three gone with none dispatched in between, a block of four that on one CU four times over - which happens
+  // only while the GPU drains, and the packets queued behind the pass on its hardware queue wait with it (profiles/HISTORY.md, r82a).
+  const Followup f = followup_geometry(h, a.matreg && !qp && h->rtc_state[0] != 1 && h->light_lds > 0);
+  if (a.matreg && a.opt.eps_infeasible > 0.0 && !f.wpb) a.opt.eps_infeasible = 0.0;
+  if (timed) HIP_TRY(hipEventRecord(h->ev0, st));
+  if ((rc = simplex_pass(h, a, st)) != DSP_OK) return rc;
+  HIP_TRY(first_pass(h, a, grid, geo.lds, st));
+  if ((rc = certificate_pass(h, a, f, timed, st)) != DSP_OK || (rc = recertify_passes(h, a, f, st)) != DSP_OK) return rc;
+  if (timed) HIP_TRY(hipEventRecord(h->ev1, st));
+#ifdef DSP_KKT_TRACE
+  if (trace_dev) {
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<double> tr(4096 * 12);
+    HIP_TRY(hipMemcpy(tr.data(), trace_dev, tr.size() * sizeof(double), hipMemcpyDeviceToHost));
+    (void)hipFree(trace_dev);
+    const char *path = getenv("DSP_TRACE_FILE");
+    if (FILE *f = fopen(path ? path : "dsp_trace.bin", "wb")) { fwrite(tr.data(), sizeof(double), tr.size(), f); fclose(f); }
+  }
+#endif
+  stats->grid_blocks = grid; stats->block_threads = 64 * a.waves_per_block; stats->lds_bytes = (int)geo.lds;
+  stats->cols_per_lane = h->cpl; stats->rows_per_lane = h->rpl; stats->matreg = a.matreg; stats->simplex = h->simplex && !qp;
+  stats->quadratic = qp; stats->rtc = (h->rtc_state[qp] == 1 && a.matreg) ? 1 : 0;
+  stats->lds_conflicts_identity = h->lds_conflicts[0] + h->lds_conflicts[2];
+  stats->lds_conflicts_chosen = a.matreg ? h->lds_conflicts[1] + h->lds_conflicts[3] : stats->lds_conflicts_identity;
+  return finish_stats(h, batch, stats, timed, st);
 }
 
 extern "C" {
-
-int dsp_wb_rolling_update(const dsp_wb_state *st, const dsp_wb_model *rt, const dsp_wb_model *tr, int32_t phase, int32_t k,
-                          void *hipStream) {
-  if (!st || !rt || !tr || st->B < 0 || phase < 0 || phase > 2 || k < 0 || k > 23 || rt->T < 1 || rt->T > 8 || tr->T < 1 || tr->T > 8)
-    return DSP_ERR_INVALID;
-  if (st->B == 0) return DSP_OK;
-  hipStream_t s = (hipStream_t)hipStream;
-  hipLaunchKernelGGL(wb_rolling_kernel, dim3((st->B + 255) / 256), dim3(256), 0, s, *st, *rt, *tr, (int)phase, (int)k);
-  if (phase == 2) hipLaunchKernelGGL(wb_clock_kernel, dim3(1), dim3(1), 0, s, (long long *)st->hour);
-  HIP_TRY(hipGetLastError());
-  return DSP_OK;
-}
-
-// ---- descriptors checked on the host: every index a lane would use lies inside its buffer, nothing is launched otherwise ----
-static bool market_col_ok(int32_t col, int32_t n) { return col >= 0 && col < n; }
-static bool loop_cols_ok(const int32_t *cols, int count, int32_t n) {
-  for (int i = 0; i < count; ++i)
-    if (!market_col_ok(cols[i], n)) return false;
-  return true;
-}
-// the <= 2 terms of the power output of T periods: a column of the LP, or -1 for "no such term"
-static bool loop_terms_ok(const int32_t (*pt_cols)[2], int T, int32_t n) {
-  for (int t = 0; t < T; ++t)
-    for (int e = 0; e < 2; ++e)
-      if (pt_cols[t][e] != -1 && !market_col_ok(pt_cols[t][e], n)) return false;
-  return true;
-}
-// wind columns of T periods (none: wind_cols[0] < 0) need the capacity factors
-static bool loop_wind_ok(const int32_t *wind_cols, int T, int32_t n, const void *cf_series) {
-  return wind_cols[0] < 0 || (cf_series && loop_cols_ok(wind_cols, T, n));
-}
-// per-plant sizes (ABI 16): both pointers or neither, and only on a model that has wind columns
-static bool plant_sizes_ok(const double *wind_kw_plant, const double *c0_base_plant, int32_t wind_col0) {
-  if (!wind_kw_plant != !c0_base_plant) return false;
-  return !wind_kw_plant || wind_col0 >= 0;
-}
-// the indices of a tracker of horizon T whose dispatch rows and plant half (loop_tracker_plant) a kernel writes
-static bool loop_tracker_cols_ok(const dsp_loop_model *tr, int T, const void *state, const void *cf_series) {
-  if (tr->n_state < 0 || tr->n_state > 2 || (tr->n_state > 0 && !state)) return false;
-  return loop_cols_ok(tr->state_init, tr->n_state, tr->n) && loop_cols_ok(tr->track_rows, T, tr->m) && loop_wind_ok(tr->wind_cols, T, tr->n, cf_series) &&
-         plant_sizes_ok(tr->wind_kw_plant, tr->c0_base_plant, tr->wind_cols[0]);
-}
-// ... and its buffers: safe to launch a kernel that writes the tracker's LP
-static bool loop_tracker_ok(const dsp_loop_model *tr, int T, const void *state, const void *cf_series) {
-  if (!tr || T < 1 || T > DSP_LOOP_MAX_T || tr->T != T || tr->n < 1 || tr->m < 1) return false;
-  if (!tr->lb || !tr->ub || !tr->rlo || !tr->rhi || !tr->c0) return false;
-  return loop_tracker_cols_ok(tr, T, state, cf_series);
-}
-
-int dsp_loop_update(const dsp_loop_state *st, const dsp_loop_model *rt, const dsp_loop_model *tr, int32_t phase, int32_t k, void *hipStream) {
-  if (!st || !rt || !tr || st->B < 0 || phase < 0 || phase > 2 || k < 0 || k > 23 || rt->T < 1 || rt->T > DSP_LOOP_MAX_T || tr->T < 1 ||
-      tr->T > DSP_LOOP_MAX_T || rt->n_state < 0 || rt->n_state > 2 || tr->n_state != rt->n_state || !rt->c0 || !tr->c0)
-    return DSP_ERR_INVALID;
-  // per-plant sizes (ABI 16): both pointers or neither on each model, the two models together, only with wind columns
-  if (!plant_sizes_ok(rt->wind_kw_plant, rt->c0_base_plant, rt->wind_cols[0]) || !rt->wind_kw_plant != !tr->wind_kw_plant) return DSP_ERR_INVALID;
-  // every index of the three phases.  The tracker follows the first tr->T periods of the real-time offer (phase 2 reads the tracker
-  // alone: the parametrized mode, which has no real-time LP, calls it with tracking horizons beyond the real-time one)
-  if ((phase < 2 && tr->T > rt->T) || !loop_tracker_cols_ok(tr, tr->T, st->state, st->cf_series) || !loop_cols_ok(tr->state_real, tr->n_state, tr->n) ||
-      !loop_terms_ok(tr->pt_cols, tr->T, tr->n))
-    return DSP_ERR_INVALID;
-  if (!loop_cols_ok(rt->pda_cols, rt->T, rt->n) || !loop_terms_ok(rt->pt_cols, rt->T, rt->n) || !loop_cols_ok(rt->state_init, rt->n_state, rt->n) ||
-      !loop_wind_ok(rt->wind_cols, rt->T, rt->n, st->cf_series))
-    return DSP_ERR_INVALID;
-  if (st->B == 0) return DSP_OK;
-  hipStream_t s = (hipStream_t)hipStream;
-  hipLaunchKernelGGL(loop_update_kernel, dim3((st->B + 255) / 256), dim3(256), 0, s, *st, *rt, *tr, (int)phase, (int)k);
-  if (phase == 2) hipLaunchKernelGGL(wb_clock_kernel, dim3(1), dim3(1), 0, s, (long long *)st->hour);
-  HIP_TRY(hipGetLastError());
-  return DSP_OK;
-}
-
-int dsp_bid_points(const dsp_bid_request *rq, void *hipStream) {
-  if (!rq || rq->B < 0 || rq->T < 0 || rq->terms < 0 || rq->terms > 2 || rq->ldx < 1 || rq->ldp < rq->T) return DSP_ERR_INVALID;
-  if (rq->B > DSP_BID_MAX_SCENARIOS || rq->T > DSP_BID_MAX_HOURS) return DSP_ERR_TOO_LARGE;
-  if (rq->T == 0) return DSP_OK;
-  if (!rq->out || (rq->B > 0 && (!rq->x || !rq->price))) return DSP_ERR_INVALID;
-  for (int t = 0; t < rq->T; ++t)
-    for (int e = 0; e < (rq->terms == 2 ? 2 : 1); ++e)
-      if (rq->col[t][e] < 0 || rq->col[t][e] >= rq->ldx) return DSP_ERR_INVALID;
-  HIP_TRY(launch_bid_points(*rq, (hipStream_t)hipStream));
-  return DSP_OK;
-}
-
-// arguments of the stochastic mode's entry points, checked on the host: nothing is launched on a bad descriptor
-static bool market_state_ok(const dsp_market_state *st) {
-  if (!st || st->B < 0 || st->N < 1 || st->S < 1 || st->S > DSP_MARKET_MAX_S) return false;
-  if (st->backcast ? (st->D < 1 || st->S > st->D || 24ll * st->D > st->N) : st->S != 1) return false;
-  return st->start && st->hour && st->da_series && st->rt_series;
-}
-int dsp_market_prepare(const dsp_market_state *st, const dsp_market_model *m, int32_t k, void *hipStream) {
-  if (!market_state_ok(st) || !m || k < -1 || k > 23 || m->n < 1 || m->T < 1 || m->T > DSP_MARKET_MAX_T) return DSP_ERR_INVALID;
-  if (!st->cf_series || !st->soc || !st->thr || !m->c || !m->lb || !m->ub || !m->base_c) return DSP_ERR_INVALID;
-  if (k >= 0 && (!st->da_offer || !st->da_prices)) return DSP_ERR_INVALID;
-  if (!market_col_ok(m->soc_init, m->n) || !market_col_ok(m->thr_init, m->n)) return DSP_ERR_INVALID;
-  for (int t = 0; t < m->T; ++t)
-    if (!market_col_ok(m->wind_cols[t], m->n) || !market_col_ok(m->pt_cols[t][0], m->n) || !market_col_ok(m->pt_cols[t][1], m->n) ||
-        !market_col_ok(m->pda_cols[t], m->n))
-      return DSP_ERR_INVALID;
-  if (st->B == 0) return DSP_OK;
-  HIP_TRY(launch_market_prepare(*st, *m, (int)k, (hipStream_t)hipStream));
-  return DSP_OK;
-}
-
-int dsp_market_clear(const dsp_market_state *st, const dsp_market_model *m, const dsp_wb_model *tr, int32_t k, int32_t T,
-                     double *dispatch, int32_t *curve, int32_t *count, void *hipStream) {
-  if (!market_state_ok(st) || !m || k < -1 || k > 23 || m->n < 1 || m->T < 1 || m->T > DSP_MARKET_MAX_T || T < 1 || T > m->T) return DSP_ERR_INVALID;
-  if (!m->x || !m->status || !dispatch || !curve || !count) return DSP_ERR_INVALID;
-  if (k < 0 ? (T > 24 || !st->da_prices || tr) : T > 8) return DSP_ERR_INVALID;
-  for (int t = 0; t < T; ++t)
-    if (k < 0 ? !market_col_ok(m->pda_cols[t], m->n) : (!market_col_ok(m->pt_cols[t][0], m->n) || !market_col_ok(m->pt_cols[t][1], m->n)))
-      return DSP_ERR_INVALID;
-  if (tr) {
-    if (tr->T != T || tr->n < 1 || tr->m < 1 || !tr->lb || !tr->ub || !tr->rlo || !tr->rhi || !st->cf_series || !st->soc || !st->thr) return DSP_ERR_INVALID;
-    if (!market_col_ok(tr->soc_init, tr->n) || !market_col_ok(tr->thr_init, tr->n)) return DSP_ERR_INVALID;
-    for (int t = 0; t < T; ++t)
-      if (!market_col_ok(tr->wind_cols[t], tr->n) || !market_col_ok(tr->track_rows[t], tr->m)) return DSP_ERR_INVALID;
-  }
-  if (st->B == 0) return DSP_OK;
-  HIP_TRY(launch_market_clear(*st, *m, tr, (int)k, (int)T, dispatch, curve, count, (hipStream_t)hipStream));
-  return DSP_OK;
-}
-
-// ... and of the descriptor loop's (dsp_loop_market_*): every index a kernel would use is checked here, nothing is launched otherwise
-static bool loop_market_state_ok(const dsp_loop_market_state *st) {
-  if (!st || st->B < 0 || st->N < 1 || st->S < 1 || st->S > DSP_MARKET_MAX_S || st->p_min_cents < 0 || st->p_min_cents > 2000000000ll) return false;
-  if (st->backcast ? (st->D < 1 || st->S > st->D || 24ll * st->D > st->N) : st->S != 1) return false;
-  if (st->rt_history_lag_days < 0 || (st->backcast && 24ll * ((long long)st->D + st->rt_history_lag_days) > st->N)) return false;      // (ABI 17)
-  if (st->self_schedule < 0 || st->self_schedule > 1) return false;                                                                     // (ABI 18)
-  if (st->curve_slots != 0 && (st->curve_slots < st->S + 1 || st->curve_slots > DSP_MARKET_MAX_S + 1)) return false;
-  if (st->coupled < 0 || st->coupled > 1 || (st->coupled && st->self_schedule)) return false;                                           // (ABI 19)
-  return st->start && st->hour && st->da_series && st->rt_series;
-}
-static bool loop_market_model_ok(const dsp_loop_market_model *m) {
-  return m && m->n >= 1 && m->T >= 1 && m->T <= DSP_MARKET_MAX_T && m->n_state >= 0 && m->n_state <= 2 &&
-         (m->row_stride == 0 || m->row_stride >= m->n);                                                                                 // (ABI 18)
-}
-// the checks dsp_loop_market_prepare and dsp_loop_schedule_prepare share: every buffer and column index a lane writes through
-static bool loop_market_prepare_ok(const dsp_loop_market_state *st, const dsp_loop_market_model *m) {
-  if (!m->c || !m->lb || !m->ub || !m->base_c || !m->c0) return false;
-  if ((m->n_state > 0 && !st->state) || !loop_cols_ok(m->state_init, m->n_state, m->n)) return false;
-  if (!loop_wind_ok(m->wind_cols, m->T, m->n, st->cf_series) || !plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return false;
-  return loop_cols_ok(m->pda_cols, m->T, m->n) && loop_terms_ok(m->pt_cols, m->T, m->n);
-}
-
-int dsp_loop_market_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, int32_t k, void *hipStream) {
-  if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < -1 || k > 23) return DSP_ERR_INVALID;
-  if (m->row_stride != 0 && m->row_stride != m->n) return DSP_ERR_INVALID;      // (ABI 18: its rows are n apart)
-  if (k >= 0 && (!st->da_offer || !st->da_prices)) return DSP_ERR_INVALID;
-  if (!loop_market_prepare_ok(st, m)) return DSP_ERR_INVALID;
-  if (st->B == 0) return DSP_OK;
-  HIP_TRY(launch_loop_market_prepare(*st, *m, (int)k, (hipStream_t)hipStream));
-  return DSP_OK;
-}
-
-// the coupled day-ahead LP of a self-scheduling plant (ABI 18): `m` describes one of the S blocks of a row of row_stride doubles
-int dsp_loop_schedule_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, void *hipStream) {
-  if (!loop_market_state_ok(st) || !loop_market_model_ok(m)) return DSP_ERR_INVALID;
-  if ((long long)m->row_stride < (long long)st->S * m->n) return DSP_ERR_INVALID;
-  if (!loop_market_prepare_ok(st, m) || m->wind_kw_plant || m->c0_base_plant) return DSP_ERR_INVALID;
-  if (st->B == 0) return DSP_OK;
-  HIP_TRY(launch_loop_schedule_prepare(*st, *m, (hipStream_t)hipStream));
-  return DSP_OK;
-}
-
-// the coupled day-ahead LP of a plant that bids a monotone curve (ABI 19): the blocks as above, and the bounds of the P T ordered-pair
-// rows [first_coupling_row, first_coupling_row + P T) of rlo / rhi [B][m_rows], P = S (S - 1) / 2
-int dsp_loop_monotone_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, double *rlo, double *rhi, int32_t m_rows,
-                              int32_t first_coupling_row, void *hipStream) {
-  if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || !rlo || !rhi || st->S < 2 || first_coupling_row < 0) return DSP_ERR_INVALID;
-  if ((long long)m->row_stride < (long long)st->S * m->n) return DSP_ERR_INVALID;
-  if ((long long)first_coupling_row + (long long)(st->S * (st->S - 1) / 2) * m->T > (long long)m_rows) return DSP_ERR_INVALID;
-  if (!loop_market_prepare_ok(st, m) || m->wind_kw_plant || m->c0_base_plant) return DSP_ERR_INVALID;
-  if (st->B == 0) return DSP_OK;
-  HIP_TRY(launch_loop_monotone_prepare(*st, *m, rlo, rhi, (int)m_rows, (int)first_coupling_row, (hipStream_t)hipStream));
-  return DSP_OK;
-}
-
-int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market_model *m, const dsp_loop_model *tr, int32_t k, int32_t T,
-                          double *dispatch, int32_t *curve, int32_t *count, void *hipStream) {
-  if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < -1 || k > 23 || T < 1 || T > m->T) return DSP_ERR_INVALID;
-  if (st->coupled && (long long)m->row_stride < (long long)st->S * m->n) return DSP_ERR_INVALID;      // (ABI 19: the S blocks of a row)
-  if (!m->x || !m->status || !dispatch || !curve || !count) return DSP_ERR_INVALID;
-  if (k < 0 ? (T > 24 || !st->da_prices || tr) : T > DSP_LOOP_MAX_T) return DSP_ERR_INVALID;
-  if (!plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return DSP_ERR_INVALID;
-  if (k < 0 ? !loop_cols_ok(m->pda_cols, T, m->n) : !loop_terms_ok(m->pt_cols, T, m->n)) return DSP_ERR_INVALID;
-  if (tr && (!loop_tracker_ok(tr, T, st->state, st->cf_series) || tr->n_state != m->n_state || !tr->wind_kw_plant != !m->wind_kw_plant)) return DSP_ERR_INVALID;
-  if (st->B == 0) return DSP_OK;
-  HIP_TRY(launch_loop_market_clear(*st, *m, tr, (int)k, (int)T, dispatch, curve, count, (hipStream_t)hipStream));
-  return DSP_OK;
-}
-
-// parametrized bidding of the descriptor loop (dsp_param.hip): every index and pointer a lane would use is checked here
-int dsp_loop_param_step(const dsp_loop_param_state *st, const dsp_loop_model *tr, int32_t phase, int32_t k, void *hipStream) {
-  if (!st || !tr || st->B < 1 || st->N < 24 || tr->T < 1 || tr->T > DSP_LOOP_MAX_T) return DSP_ERR_INVALID;
-  if (phase < 0 || phase > 2 || (phase == 0 ? k != -1 : (k < 0 || k > 23))) return DSP_ERR_INVALID;
-  if (tr->wind_kw_plant || tr->c0_base_plant) return DSP_ERR_INVALID;      // the parametrized bidders take one wind size (wind_mw)
-  if (!st->start || !st->hour || !st->da_series || !st->rt_series || !st->da_cf_series || !st->rt_cf_series || !st->bid_price ||
-      !st->storage_mw)
-    return DSP_ERR_INVALID;
-  if (phase == 0) {
-    if (!st->da_offer || !st->da_prices || !st->da_curve || !st->da_count) return DSP_ERR_INVALID;
-  } else if (phase == 1) {
-    if (!st->rt_dispatch || !st->rt_curve || !st->rt_count) return DSP_ERR_INVALID;
-    if (!loop_tracker_ok(tr, tr->T, st->state, st->rt_cf_series)) return DSP_ERR_INVALID;
-  } else {
-    if (!st->h2_kg || !tr->x || tr->n < 1 || !market_col_ok(st->pem_col, tr->n)) return DSP_ERR_INVALID;
-  }
-  HIP_TRY(launch_loop_param_step(*st, *tr, (int)phase, (hipStream_t)hipStream));
-  return DSP_OK;
-}
-
-// the projection tracker of the descriptor loop (dsp_project.hip): every index and pointer a lane would use is checked here
-int dsp_loop_project(const dsp_loop_project_state *st, const dsp_loop_model *pj, int32_t phase, int32_t j, void *hipStream) {
-  if (!st || st->B < 1 || st->N < 1 || st->ruc_hour < 1 || st->ruc_hour > 23 || phase < 0 || phase > 2) return DSP_ERR_INVALID;
-  if (j < 0 || j >= (phase == 2 ? 1 : 24 - st->ruc_hour)) return DSP_ERR_INVALID;
-  if (phase == 2) {
-    if (!st->da_offer || !st->da_prices || !st->pend_offer || !st->pend_prices || st->slots < 0 || st->slots > DSP_MARKET_MAX_S + 1) return DSP_ERR_INVALID;
-    if (st->slots > 0 && (!st->da_curve || !st->da_count || !st->pend_curve || !st->pend_count)) return DSP_ERR_INVALID;
-    HIP_TRY(launch_loop_project(*st, pj ? *pj : dsp_loop_model{}, 2, 0, (hipStream_t)hipStream));
-    return DSP_OK;
-  }
-  if (!pj || pj->T < 1 || pj->T > DSP_LOOP_MAX_T || pj->n < 1 || pj->m < 1 || pj->n_state < 0 || pj->n_state > 2) return DSP_ERR_INVALID;
-  if (!st->start || !st->hour || (pj->n_state > 0 && (!st->state || !st->proj_state))) return DSP_ERR_INVALID;      // (no state: empty traces may be NULL)
-  if (!plant_sizes_ok(pj->wind_kw_plant, pj->c0_base_plant, pj->wind_cols[0])) return DSP_ERR_INVALID;
-  if (phase == 0) {
-    if (!st->da_offer || !loop_tracker_ok(pj, pj->T, st->state, st->cf_series)) return DSP_ERR_INVALID;
-  } else {
-    if (!pj->x || !pj->status || !pj->c0 || !st->obj || (pj->n_state > 0 && !st->proj_real) || !st->proj_obj) return DSP_ERR_INVALID;
-    for (int e = 0; e < pj->n_state; ++e)
-      if (!market_col_ok(pj->state_real[e], pj->n) || !(st->state_scale[e] > 0.0)) return DSP_ERR_INVALID;
-  }
-  HIP_TRY(launch_loop_project(*st, *pj, (int)phase, (int)j, (hipStream_t)hipStream));
-  return DSP_OK;
-}
 
 void dsp_default_options(dsp_options *o) {
   if (!o) return;
@@ -625,20 +594,7 @@ const char *dsp_strerror(int code) {
 }
 
 int dsp_create(const dsp_lp_desc *d, int device, const dsp_options *opt, dsp_handle **out) {
-  if (!d || !out || d->n <= 0 || d->m < 0 || d->nnz < 0 || !d->A_rowptr || (d->nnz && (!d->A_colidx || !d->A_val)))
-    return DSP_ERR_INVALID;
-  if (d->A_rowptr[0] != 0 || d->A_rowptr[d->m] != d->nnz) return DSP_ERR_INVALID;
-  for (int i = 0; i < d->m; ++i) {
-    if (d->A_rowptr[i + 1] < d->A_rowptr[i]) return DSP_ERR_INVALID;
-    for (int p = d->A_rowptr[i]; p < d->A_rowptr[i + 1]; ++p) {
-      if (d->A_colidx[p] < 0 || d->A_colidx[p] >= d->n) return DSP_ERR_INVALID;
-      if (p > d->A_rowptr[i] && d->A_colidx[p] <= d->A_colidx[p - 1]) return DSP_ERR_INVALID;
-      if (!std::isfinite(d->A_val[p])) return DSP_ERR_INVALID;
-    }
-  }
-  if (d->col_scale)
-    for (int j = 0; j < d->n; ++j)
-      if (!(d->col_scale[j] > 0.0) || !std::isfinite(d->col_scale[j])) return DSP_ERR_INVALID;
+  if (!out || !desc_ok(d)) return DSP_ERR_INVALID;
   static const int kCpl[] = {1, 2, 3, 4, 5, 7, 10};
   static const int kRpl[] = {1, 2, 3, 4, 6};
   int cpl = pick(kCpl, 7, (d->n + 63) / 64);
@@ -651,7 +607,10 @@ int dsp_create(const dsp_lp_desc *d, int device, const dsp_options *opt, dsp_han
   if (device < 0 || device >= ndev) return DSP_ERR_INVALID;
   HIP_TRY(hipSetDevice(device));
 
-  dsp_handle *h = new (std::nothrow) dsp_handle();
+  // whatever fails from here on releases the handle, and all it owns by then, through dsp_destroy
+  struct Destroy { void operator()(dsp_handle *p) const { dsp_destroy(p); } };
+  std::unique_ptr<dsp_handle, Destroy> owner(new (std::nothrow) dsp_handle());
+  dsp_handle *h = owner.get();
   if (!h) return DSP_ERR_ALLOC;
   h->device = device; h->n = d->n; h->m = d->m; h->nnz = d->nnz; h->cpl = cpl; h->rpl = rpl;
   if (opt) h->opt = *opt; else dsp_default_options(&h->opt);
@@ -661,8 +620,7 @@ int dsp_create(const dsp_lp_desc *d, int device, const dsp_options *opt, dsp_han
     h->lds_limit = (int)prop.maxSharedMemoryPerMultiProcessor > 0 ? (int)prop.maxSharedMemoryPerMultiProcessor : 64 * 1024;
   }
 
-  HostCSR A;
-  A.m = d->m; A.n = d->n;
+  HostCSR A; A.m = d->m; A.n = d->n;
   A.ptr.assign(d->A_rowptr, d->A_rowptr + d->m + 1);
   A.idx.assign(d->A_colidx, d->A_colidx + d->nnz);
   A.val.assign(d->A_val, d->A_val + d->nnz);
@@ -670,402 +628,29 @@ int dsp_create(const dsp_lp_desc *d, int device, const dsp_options *opt, dsp_han
   equilibrate(A, h->opt.ruiz_iters, h->dr, h->dc, std::max(0, h->opt.geo_iters), d->col_scale);
   HostCSR AT = transpose(A), ATu = transpose(Au);
   h->eta_unit = 1.0 / spectral_norm(A, AT, 500);
-  if (streaming) {
-    // LP beyond the register/LDS-resident kernels (n > 640 or m > 384): HBM-resident PDLP
-    int rc2;
-    h->streaming = 1; h->cpl = h->rpl = 0;
-    if ((rc2 = upload(h, h->dc, &h->P.col_scale)) != DSP_OK || (rc2 = upload(h, h->dr, &h->P.row_scale)) != DSP_OK) { dsp_destroy(h); return rc2; }
-    h->P.n = d->n; h->P.m = d->m;
-    hipError_t se = stream_create(A, AT, h->P.col_scale, h->P.row_scale, &h->stream);
-    if (se != hipSuccess) { g_last_hip_error = (int)se; dsp_destroy(h); return se == hipErrorInvalidValue ? DSP_ERR_TOO_LARGE : DSP_ERR_HIP; }
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) { dsp_destroy(h); return DSP_ERR_HIP; }
-    *out = h;
-    return DSP_OK;
-  }
-
-  LaneELL Er = build_lane_ell(A, rpl), Ec = build_lane_ell(AT, cpl);
-  // unscaled values in the SAME layout (same sparsity => same W / long split)
-  LaneELL Eru = build_lane_ell(Au, rpl), Ecu = build_lane_ell(ATu, cpl);
-  DeviceProblem &P = h->P;
-  P.n = d->n; P.m = d->m; P.n_pad = cpl * 64; P.m_pad = rpl * 64;
-  P.Wc = Ec.W; P.Wr = Er.W;
-  P.ellc_entries = (int)Ec.val.size(); P.ellr_entries = (int)Er.val.size();
-  P.tailc_entries = (int)Ec.tail_val.size(); P.tailr_entries = (int)Er.tail_val.size();
-  int rc;
-  if ((rc = fill_long(P.long_c, Ec)) || (rc = fill_long(P.long_r, Er))) { delete h; return rc; }
-  // register-resident-matrix layout: ownership sorted by length, per-slot widths, position space
-  SortedLayout Lc = sorted_layout(AT, cpl, Ec.long_owner), Lr = sorted_layout(A, rpl, Er.long_owner);
-  SlotELL Sc = build_slot_ell(AT, Lc, Lr, Ec.long_owner), Sr = build_slot_ell(A, Lr, Lc, Er.long_owner);
-  const bool has_long = P.long_c.count > 0 || P.long_r.count > 0;
-  int pad_w = 0;
-  // no ahead-of-time specialisation for this shape: compile the tight one now (hiprtc, disk-cached).  Limits: RegEll packs
-  // at most 8 slots of width <= 15, and beyond ~32 register-resident entries per lane the kernel would live in scratch.
-  const bool aot_lp = matreg_available(cpl, rpl, Sc.pack, Sr.pack, has_long) != 0;
-  const bool aot_qp = matreg_available(cpl, rpl, Sc.pack, Sr.pack, has_long, true) != 0;
-  bool rtc_ok = false;
-  if (!h->opt.no_matreg && !h->opt.no_rtc && !aot_lp && cpl <= 8 && rpl <= 8 && Sc.total + Sr.total <= 32) {
-    bool wide = false;
-    for (int q = 0; q < Sc.slots; ++q) wide |= Sc.width[q] > 15;
-    for (int q = 0; q < Sr.slots; ++q) wide |= Sr.width[q] > 15;
-    if (!wide) {
-      rtc_ok = rtc_get_kernel(device, cpl, rpl, has_long, Sc.pack, Sr.pack, false, &h->rtc[0], &h->rtc_why);
-      if (rtc_ok) { h->rtc_state[0] = 1; h->rtc_long = has_long; if (!aot_qp && !has_long) h->rtc_state[1] = -1; }
-    }
-  }
-  if (!h->opt.no_matreg && !aot_lp && !aot_qp && !rtc_ok) {
-    // no tight specialisation for this shape: the PADDED one (every slot kPadWidth wide) if the LP fits it
-    int wmax = 0;
-    for (int q = 0; q < Sc.slots; ++q) wmax = std::max(wmax, Sc.width[q]);
-    for (int q = 0; q < Sr.slots; ++q) wmax = std::max(wmax, Sr.width[q]);
-    if (!has_long && wmax <= kPadWidth && matreg_available(cpl, rpl, uniform_pack(cpl, kPadWidth), uniform_pack(rpl, kPadWidth), false)) {
-      pad_w = kPadWidth;
-      Sc = build_slot_ell(AT, Lc, Lr, Ec.long_owner, pad_w);
-      Sr = build_slot_ell(A, Lr, Lc, Er.long_owner, pad_w);
-    }
-  }
-  // the unscaled matrix in the same position-space layout (same sparsity): streaming SpMV step
-  SlotELL Scu = build_slot_ell(ATu, Lc, Lr, Ec.long_owner, pad_w), Sru = build_slot_ell(Au, Lr, Lc, Er.long_owner, pad_w);
-  // bank-conflict-minimising slot permutation of each exchange buffer: the y buffer is gathered by the A^T entries
-  // (Sc), the x buffer by the A entries (Sr)
-  const bool shared_slots = shared_slot_maps(cpl, rpl);
-  SlotMap My = optimise_slots(Sc, P.m_pad, 4000, shared_slots), Mx = optimise_slots(Sr, P.n_pad, 4000, shared_slots);
-  h->lds_conflicts[0] = My.cost_identity; h->lds_conflicts[1] = My.cost_final;
-  h->lds_conflicts[2] = Mx.cost_identity; h->lds_conflicts[3] = Mx.cost_final;
-  apply_slots(Sc, My.slot);
-  apply_slots(Sr, Mx.slot);
-  apply_slots(Scu, My.slot);
-  apply_slots(Sru, Mx.slot);
-  // LDS byte offset of every natural element: column j sits at position Lc.pos[j], whose exchange slot is Mx.slot[...]
-  std::vector<int32_t> nat_x((size_t)P.n_pad, 0), nat_y((size_t)P.m_pad, 0);
-  for (int j = 0; j < d->n; ++j) nat_x[j] = 8 * Mx.slot[Lc.pos[j]];
-  for (int i = 0; i < d->m; ++i) nat_y[i] = 8 * My.slot[Lr.pos[i]];
-  P.mr_wc_pack = Sc.pack; P.mr_wr_pack = Sr.pack;
-  P.mr_tailc_entries = (int)Sc.tail_val.size(); P.mr_tailr_entries = (int)Sr.tail_val.size();
-  if ((rc = fill_long(P.mr_long_c, Sc)) || (rc = fill_long(P.mr_long_r, Sr))) { delete h; return rc; }
-  h->matreg = h->opt.no_matreg ? 0 : (rtc_ok ? 1 : matreg_available(cpl, rpl, Sc.pack, Sr.pack, P.long_c.count > 0 || P.long_r.count > 0));
-  h->matreg_qp = h->opt.no_matreg ? 0 : matreg_available(cpl, rpl, Sc.pack, Sr.pack, P.long_c.count > 0 || P.long_r.count > 0, true);
-  std::vector<Entry> pk;
-#define UPE(val, idx, field) pack_entries(val, idx, pk); if ((rc = upload(h, pk, &P.field)) != DSP_OK) { dsp_destroy(h); return rc; }
-#define UP(vec, field) if ((rc = upload(h, vec, &P.field)) != DSP_OK) { dsp_destroy(h); return rc; }
-  UPE(Ec.val, Ec.idx, ellc) UPE(Er.val, Er.idx, ellr) UPE(Ec.tail_val, Ec.tail_idx, tailc) UPE(Er.tail_val, Er.tail_idx, tailr)
-  UPE(Ecu.val, Ecu.idx, ellc_unscaled) UPE(Eru.val, Eru.idx, ellr_unscaled)
-  UPE(Ecu.tail_val, Ecu.tail_idx, tailc_unscaled) UPE(Eru.tail_val, Eru.tail_idx, tailr_unscaled)
-  UP(h->dc, col_scale) UP(h->dr, row_scale)
-  UPE(Sc.val, Sc.off, mr_ellc) UPE(Sr.val, Sr.off, mr_ellr) UPE(Sc.tail_val, Sc.tail_off, mr_tailc) UPE(Sr.tail_val, Sr.tail_off, mr_tailr)
-  UP(Lc.at, mr_colat) UP(Lr.at, mr_rowat) UP(Mx.slot, mr_slot_x) UP(My.slot, mr_slot_y)
-  UPE(Scu.val, Scu.off, mr_ellc_unscaled) UPE(Sru.val, Sru.off, mr_ellr_unscaled)
-  UPE(Scu.tail_val, Scu.tail_off, mr_tailc_unscaled) UPE(Sru.tail_val, Sru.tail_off, mr_tailr_unscaled)
-  UP(nat_x, mr_nat_slot_x) UP(nat_y, mr_nat_slot_y)
-#undef UP
-#undef UPE
-  // tiny LPs: dense scaled matrix for the in-wave simplex
-  if (!h->opt.no_simplex && d->n + d->m <= 128 && d->m <= 64 && d->m >= 1) {
-    h->sx_lds = simplex_lds_bytes(d->n, d->m, &h->sx_row_stride);
-    if (h->sx_lds <= (size_t)h->lds_limit) {
-      std::vector<double> dense((size_t)d->m * d->n, 0.0);
-      for (int i = 0; i < A.m; ++i)
-        for (int p = A.ptr[i]; p < A.ptr[i + 1]; ++p) dense[(size_t)i * d->n + A.idx[p]] = A.val[p];
-      if ((rc = upload(h, dense, &h->A_dense)) != DSP_OK) { dsp_destroy(h); return rc; }
-      h->simplex = 1;
-    }
-  }
-  void *q = nullptr;
-  if (hipMalloc(&q, sizeof(int) * kQueueRing * kQueueStride) != hipSuccess) { dsp_destroy(h); return DSP_ERR_HIP; }
-  h->queue = (int *)q;
-  if (hipMemset(q, 0, sizeof(int) * kQueueRing * kQueueStride) != hipSuccess) { dsp_destroy(h); return DSP_ERR_HIP; }
-  {
-    // (+ 1: the table loop loads the weight of the iteration after its last one, dsp_kernels.hip)
-    void *aw = nullptr;
-    if (hipMalloc(&aw, sizeof(double) * (kAnchorWeights + 1)) != hipSuccess) { dsp_destroy(h); return DSP_ERR_HIP; }
-    h->allocs.push_back(aw);
-    h->anchor_w = (const double *)aw;
-    hipLaunchKernelGGL(anchor_weight_kernel, dim3(1), dim3(256), 0, (hipStream_t)0, (double *)aw, kAnchorWeights + 1);
-    // (solves run on the caller's streams, which need not wait for the null stream)
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize((hipStream_t)0) != hipSuccess) { dsp_destroy(h); return DSP_ERR_HIP; }
-  }
-  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) { dsp_destroy(h); return DSP_ERR_HIP; }
-  if (h->matreg && h->rtc_state[0] != 1) {
-    // follow-up passes behind a three-wave first pass: the runtime's occupancy answer for a one-wave block of the light kernel with the
-    // LDS matrix decides (on the 24-h LP about 27 KB, beside eleven first-pass blocks of about 8 KB in the CU's 160 KB); 0 = as before
-    SolveArgs first{};
-    first.P = h->P; first.matreg = 1; first.qp = 0;
-    const size_t l = lds_bytes(h->P, 1, 0, h->cpl, h->rpl);
-    if (l <= (size_t)h->lds_limit && light_followup_blocks(h->cpl, h->rpl, first, l) > 0) h->light_lds = l;
-  }
-  *out = h;
+  int rc = streaming ? create_streaming(h, A, AT) : create_fused(h, A, AT, Au, ATu);
+  if (rc == DSP_OK && !streaming) rc = create_device_objects(h, A);
+  if (rc != DSP_OK) return rc;
+  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return DSP_ERR_HIP;
+  *out = owner.release();
   return DSP_OK;
 }
 
-int dsp_solve(dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, dsp_stats *stats, int sync_stats,
-              void *hipStream) {
+int dsp_solve(dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, dsp_stats *stats, int sync_stats, void *hipStream) {
   if (!h || !batch || batch->B < 0) return DSP_ERR_INVALID;
-  const int B = batch->B;
-  if (B == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return DSP_OK; }
+  if (batch->B == 0) { if (stats) std::memset(stats, 0, sizeof(*stats)); return DSP_OK; }
   if (!batch->c || !batch->x || !batch->y || !batch->obj || !batch->status) return DSP_ERR_INVALID;
   hipStream_t st = (hipStream_t)hipStream;
   HIP_TRY(hipSetDevice(h->device));
   SolveArgs a{};
-  a.P = h->P; a.b = *batch;
-  a.anchor_w = h->anchor_w;
-  a.opt = opt ? *opt : h->opt;
-  if (a.opt.max_iter < 1 || a.opt.check_every < 0 || a.opt.kkt_every < 0 || !(a.opt.kkt_gate >= 0) || a.opt.stall_rescue < 0 || a.opt.polish_patience < 0 || !(a.opt.jump_rel >= 0) || !(a.opt.eps_rel > 0) || !(a.opt.eps_obj >= 0) || !(a.opt.eps_infeasible >= 0) ||
-      !(a.opt.pid_kp >= 0) || !(a.opt.restart_artificial >= 0) || !(a.opt.step_scale > 0))
-    return DSP_ERR_INVALID;
-  a.eta = a.opt.step_scale * h->eta_unit;
-  const int qp = batch->row_compliance != nullptr;
-  // 0 = automatic (include/dsp_hip.h): the fused float64 kernels restart their Halpern epochs earlier and steer the primal
-  // weight more gently than the HBM-resident and float32 paths, which keep the values they were tuned with
-  {
-    const bool fused64 = !h->streaming && a.opt.precision == 0;
-    if (a.opt.restart_artificial == 0.0) a.opt.restart_artificial = fused64 ? (qp ? 0.3 : 0.2) : 0.36;
-    if (a.opt.pid_kp == 0.0) a.opt.pid_kp = fused64 ? 0.6 : 0.7;
-  }
-  if (a.opt.precision != 0 && a.opt.precision != 1) return DSP_ERR_INVALID;
-  // float32 iterates exist in the fused kernels only; soft rows in the fused kernels without long vectors and in the
-  // HBM-resident streaming form
-  if (a.opt.precision && (h->streaming || h->P.long_c.count > 0 || h->P.long_r.count > 0)) return DSP_ERR_INVALID;
-  if (qp && !h->streaming && (h->P.long_c.count > 0 || h->P.long_r.count > 0)) return DSP_ERR_INVALID;
-  if (h->streaming) {
-    const bool timed_s = stats && sync_stats;
-    if (timed_s) HIP_TRY(hipEventRecord(h->ev0, st));
-    int periods = 0;
-    HIP_TRY(stream_solve(&h->stream, *batch, a.opt, a.eta, st, &periods));
-    if (timed_s) HIP_TRY(hipEventRecord(h->ev1, st));
-    if (stats) {
-      std::memset(stats, 0, sizeof(*stats));
-      stats->streaming = 1;
-      stats->quadratic = qp;
-      stats->grid_blocks = (std::max(h->n, h->m) + 255) / 256; stats->block_threads = 256;
-      stats->stream_bytes_per_iteration = (int64_t)stream_bytes_per_iteration(&h->stream);
-      stats->stream_form = h->stream.last_form;
-      stats->stream_phases = (h->stream.last_form == DSP_STREAM_FORM_LANE || h->stream.last_form == DSP_STREAM_FORM_IPM) ? h->stream.last_phases : 0;
-      stats->ipm_solved = h->stream.last_ipm_solved;
-      if (sync_stats) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, h->ev0, h->ev1));
-        std::vector<int32_t> hs(B), hi(B);
-        HIP_TRY(hipMemcpy(hs.data(), batch->status, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (batch->iters) HIP_TRY(hipMemcpy(hi.data(), batch->iters, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int i = 0; i < B; ++i) {
-          stats->n_optimal += hs[i] == DSP_STATUS_OPTIMAL;
-          if (batch->iters) { stats->total_iterations += hi[i]; stats->max_iterations = std::max(stats->max_iterations, hi[i]); }
-        }
-      }
-    }
-    return DSP_OK;
-  }
-  if (a.opt.precision == 1) {
-    // float32 iterates (tolerance sweep of BASELINE config 5): its own kernel, one scenario per wave, LDS-resident matrix
-    const unsigned slot32 = h->queue_next.fetch_add(1u) % kQueueRing;
-    a.queue = h->queue + (size_t)slot32 * kQueueStride;
-    a.qp = qp;
-    hipLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, st, a.queue, 2);
-    const bool timed32 = stats && sync_stats;
-    if (timed32) HIP_TRY(hipEventRecord(h->ev0, st));
-    int grid32 = 0, threads32 = 0;
-    size_t lds32 = 0;
-    HIP_TRY(launch_solve_f32(h->cpl, h->rpl, a, h->num_cus, (size_t)h->lds_limit, st, &grid32, &threads32, &lds32));
-    if (timed32) HIP_TRY(hipEventRecord(h->ev1, st));
-    if (stats) {
-      std::memset(stats, 0, sizeof(*stats));
-      stats->grid_blocks = grid32; stats->block_threads = threads32; stats->lds_bytes = (int)lds32;
-      stats->cols_per_lane = h->cpl; stats->rows_per_lane = h->rpl; stats->quadratic = qp; stats->precision = 1;
-      if (sync_stats) {
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, h->ev0, h->ev1));
-        std::vector<int32_t> hs(B), hi(B);
-        HIP_TRY(hipMemcpy(hs.data(), batch->status, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (batch->iters) HIP_TRY(hipMemcpy(hi.data(), batch->iters, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int i = 0; i < B; ++i) {
-          stats->n_optimal += hs[i] == DSP_STATUS_OPTIMAL;
-          if (batch->iters) { stats->total_iterations += hi[i]; stats->max_iterations = std::max(stats->max_iterations, hi[i]); }
-        }
-      }
-    }
-    return DSP_OK;
-  }
-  if (qp && h->rtc_state[1] == -1) {
-    // first QP solve on a run-time specialised shape: compile its QP instantiation (the layout is the tight one already)
-    h->rtc_state[1] = rtc_get_kernel(h->device, h->cpl, h->rpl, false, h->P.mr_wc_pack, h->P.mr_wr_pack, true, &h->rtc[1], &h->rtc_why) ? 1 : 0;
-    if (h->rtc_state[1] == 1) h->matreg_qp = 1;
-  }
-  Geometry geo;
-  int grc = solve_geometry(h, a.opt.waves_per_block, B, &geo, qp);
-  if (grc != DSP_OK) return grc;
-  a.waves_per_block = geo.wpb;
-  const size_t lds = geo.lds;
-  const unsigned slot = h->queue_next.fetch_add(1u) % kQueueRing;
-  a.queue = h->queue + (size_t)slot * kQueueStride;
-  a.queue_base = 0u;
-  a.unsolved = a.queue + 1;
-  a.suspects = a.queue + 2;                          // (+ 3: the work-queue head of the certificate pass; + 4: count of scenarios flagged
-                                                     //  DSP_FLAG_OBJ_WAIVED; + 5 .. 7: heads of the re-certification passes)
-  hipLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, st, a.queue, 8);
-  a.matreg = qp ? h->matreg_qp : h->matreg;
-  a.qp = qp;
-#ifdef DSP_KKT_TRACE
-  const char *trace_env = getenv("DSP_TRACE_SCENARIO");
-  double *trace_dev = nullptr;
-  if (trace_env) {
-    HIP_TRY(hipMalloc((void **)&trace_dev, 4096 * 12 * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(trace_dev, 0, 4096 * 12 * sizeof(double), st));
-    a.trace = trace_dev; a.trace_scenario = atoi(trace_env);
-  }
-#endif
-  int grid = std::min((B + geo.wpb - 1) / geo.wpb, h->num_cus * geo.blocks_per_cu);
-  // geometry of the certificate pass (below), fixed BEFORE the first pass runs: a register-resident kernel may only leave scenarios
-  // DSP_STATUS_SUSPECT if the generic kernel that takes them over can be launched (it always can for an LP of the fused path - it is
-  // the fallback of every shape -; if not, the first pass keeps every scenario and the certificates are off for this call)
-  // Behind a three-wave first pass (168 VGPRs a wave, 504 of a SIMD's 512) the follow-up passes - certificates and re-certification -
-  // are one-wave blocks of the light instantiation: each fits the registers ONE leaving first-pass wave sets free.  A 256-VGPR wave
-  // needs two of a SIMD's three gone with none dispatched in between, a block of four that on one CU four times over - which happens
-  // only while the GPU drains, and the packets queued behind the pass on its hardware queue wait with it (profiles/HISTORY.md, r82a).
-  const bool light = a.matreg && !qp && h->rtc_state[0] != 1 && h->light_lds > 0;
-  int cert_wpb = 0;
-  size_t cert_lds = 0;
-  if (a.matreg && a.opt.eps_infeasible > 0.0) {
-    for (int wpb = 1; wpb <= 4 && !light; ++wpb) {    // a few waves per block share the LDS matrix; the pass is rare, not tuned
-      const size_t l = lds_bytes(h->P, wpb, 0, h->cpl, h->rpl);
-      if (l <= (size_t)h->lds_limit) { cert_wpb = wpb; cert_lds = l; }
-    }
-    if (light) { cert_wpb = 1; cert_lds = h->light_lds; }
-    if (!cert_wpb) a.opt.eps_infeasible = 0.0;
-  }
+  if (int rc = resolve_options(h, batch, opt, &a)) return rc;
+  dsp_stats lent;                                   // (the paths always fill a struct; `timed`: the caller waits for it)
   const bool timed = stats && sync_stats;
-  if (timed) HIP_TRY(hipEventRecord(h->ev0, st));
-  if (h->simplex && !qp) {
-    // simplex pass: certified vertices get their final status; DSP_STATUS_UNSOLVED marks what the PDLP kernel still has to do
-    SimplexArgs sa{};
-    sa.n = h->n; sa.m = h->m; sa.row_stride = h->sx_row_stride; sa.max_pivots = 20 * (h->n + h->m);
-    sa.A_dense = h->A_dense; sa.col_scale = h->P.col_scale; sa.row_scale = h->P.row_scale; sa.b = *batch;
-    sa.tol_p = 1e-10; sa.tol_d = 1e-12; sa.tol_piv = 1e-9;
-    { static const char *tp = getenv("DSP_SX_TOLP"); if (tp) sa.tol_p = atof(tp); }      // (development)
-    sa.unsolved = a.queue + 1;
-    if (a.opt.simplex_warm == 1 || a.opt.simplex_warm == 2) {
-      if (B > h->sx_warm_cap) {
-        // (allocated outside any stream capture: the rolling loops run their first day eagerly)
-        const size_t N = (size_t)h->n + h->m;
-        double *t = nullptr; int *bs = nullptr, *vl = nullptr; unsigned char *up = nullptr;
-        HIP_TRY(hipMalloc((void **)&t, (size_t)B * h->m * N * sizeof(double)));
-        h->sx_warm_allocs.push_back(t);
-        HIP_TRY(hipMalloc((void **)&bs, (size_t)B * h->m * sizeof(int)));
-        h->sx_warm_allocs.push_back(bs);
-        HIP_TRY(hipMalloc((void **)&up, (size_t)B * N));
-        h->sx_warm_allocs.push_back(up);
-        HIP_TRY(hipMalloc((void **)&vl, (size_t)B * sizeof(int)));
-        h->sx_warm_allocs.push_back(vl);
-        HIP_TRY(hipMemset(vl, 0, (size_t)B * sizeof(int)));
-        h->sx_warm_T = t; h->sx_warm_basis = bs; h->sx_warm_upper = up; h->sx_warm_valid = vl; h->sx_warm_cap = B;
-      }
-      sa.warm = a.opt.simplex_warm;
-      sa.warm_T = h->sx_warm_T; sa.warm_basis = h->sx_warm_basis; sa.warm_upper = h->sx_warm_upper; sa.warm_valid = h->sx_warm_valid;
-    }
-    static const int sx_debug = getenv("DSP_SX_DEBUG") ? atoi(getenv("DSP_SX_DEBUG")) : 0;
-    sa.debug_keep = sx_debug;
-    const int per_cu = std::max<int>(1, std::min<int>(32, (int)((size_t)h->lds_limit / h->sx_lds)));
-    const int sgrid = std::min(B, h->num_cus * per_cu);
-    HIP_TRY(launch_simplex(sa, sgrid, h->sx_lds, st));
-    a.skip_solved = 1;
-  }
-  if (h->rtc_state[qp] == 1 && a.matreg) {
-    size_t arg_size = sizeof(a);
-    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &arg_size, HIP_LAUNCH_PARAM_END};
-    HIP_TRY(hipModuleLaunchKernel(h->rtc[qp].fn, grid, 1, 1, 64 * a.waves_per_block, 1, 1, (unsigned)lds, st, nullptr, config));
-  } else {
-    HIP_TRY(launch_solve(h->cpl, h->rpl, a, dim3(grid), dim3(64 * a.waves_per_block), lds, st));
-  }
-  if (a.matreg && a.opt.eps_infeasible > 0.0) {
-    // Certificate pass: the register-resident kernels only WATCH for scenarios whose objectives keep drifting apart and leave them
-    // DSP_STATUS_SUSPECT; the generic kernel - which evaluates the infeasibility / unboundedness certificates at its restarts -
-    // continues those from their iterate (x0 / y0 = the outputs of the first pass).  One more launch per solve that returns at
-    // its first line when the device-side count of suspects is 0: every feasible batch.
-    SolveArgs c = a;
-    c.matreg = 0;
-    c.skip_solved = 2;
-    c.queue = a.queue + 3;
-    c.b.x0 = a.b.x; c.b.y0 = a.b.y;
-    c.waves_per_block = cert_wpb;
-    // How many blocks: a caller that waits for the statistics anyway (sync_stats) lets the host read the count of suspects after the
-    // first pass - no launch at all on a feasible batch, one block per suspect otherwise.  Asynchronous callers (pipelined batches,
-    // the rolling loop's graphs) get a launch of 8 blocks that returns at its first line when there is no suspect: with one block
-    // per CU it cost the pipelined metric batch 1.2 % (every block needs a free 256-VGPR wave slot before it can even return), with
-    // 8 blocks 0.5 %, without the pass 0 (profiles/r51d_cert_pass_cost.log); 32 waves are plenty for the rare suspect.
-    static const int cert_grid_env = getenv("DSP_CERT_GRID") ? atoi(getenv("DSP_CERT_GRID")) : 0;      // development: blocks of the pass
-    int nsus = -1;
-    if (stats && sync_stats) {
-      HIP_TRY(hipMemcpyAsync(&nsus, a.suspects, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (nsus != 0) {
-      const int want = nsus > 0 ? (nsus + cert_wpb - 1) / cert_wpb : (cert_grid_env > 0 ? cert_grid_env : 8);
-      const int grid2 = std::max(1, std::min(std::min((B + cert_wpb - 1) / cert_wpb, want), 2 * h->num_cus));
-      HIP_TRY(light ? launch_solve_light(h->cpl, h->rpl, a, c, grid2, cert_lds, st)
-                    : launch_solve(h->cpl, h->rpl, c, dim3(grid2), dim3(64 * cert_wpb), cert_lds, st));
-    }
-  }
-  if (a.opt.recertify_passes > 0 && batch->flags) {
-    // Re-certification passes (dsp_options::recertify_passes): scenarios the passes above accepted with DSP_FLAG_OBJ_WAIVED - the objective-error
-    // bound stuck within 10 eps_obj while the objective itself had stopped - are solved again from a cold start under another restart
-    // cadence / weight controller, on the device, by the generic kernel; a certified optimum replaces the flagged point, anything else
-    // leaves it (and its flag) in place.  Each pass returns at its first line when the device-side count of flagged scenarios is 0:
-    // almost every batch (one flagged solve in the 147 M of a simulated year of the rolling loop).  What HipPdlpSolver._recertify does
-    // from the host for synchronous callers, for callers that never look (hipGraph replays, pipelined batches).
-    static const struct { double pid_kp, restart_artificial; int check_every; } kRecertify[3] = {{0.45, 0.3, 0}, {0.8, 0.15, 0}, {0.3, 0.5, 12}};
-    int rwpb = 0;
-    size_t rlds = 0;
-    for (int wpb = 1; wpb <= 4 && !light; ++wpb) {
-      const size_t l = lds_bytes(h->P, wpb, 0, h->cpl, h->rpl);
-      if (l <= (size_t)h->lds_limit) { rwpb = wpb; rlds = l; }
-    }
-    if (light) { rwpb = 1; rlds = h->light_lds; }            // (one-wave blocks of the light kernel: above)
-    for (int v = 0; rwpb && v < std::min(a.opt.recertify_passes, 3); ++v) {
-      SolveArgs c = a;
-      c.matreg = 0;
-      c.skip_solved = 3;
-      c.queue = a.queue + 5 + v;
-      c.b.x0 = nullptr; c.b.y0 = nullptr;
-      c.waves_per_block = rwpb;
-      c.opt.pid_kp = kRecertify[v].pid_kp;
-      c.opt.restart_artificial = kRecertify[v].restart_artificial;
-      if (kRecertify[v].check_every) c.opt.check_every = kRecertify[v].check_every;
-      c.opt.polish_patience = std::max(c.opt.polish_patience, 1024);       // (a pass that waives as readily as the first certifies nothing)
-      const int rgrid = std::max(1, std::min((B + rwpb - 1) / rwpb, 64));
-      HIP_TRY(light ? launch_solve_light(h->cpl, h->rpl, a, c, rgrid, rlds, st)
-                    : launch_solve(h->cpl, h->rpl, c, dim3(rgrid), dim3(64 * rwpb), rlds, st));
-    }
-  }
-  if (timed) HIP_TRY(hipEventRecord(h->ev1, st));
-#ifdef DSP_KKT_TRACE
-  if (trace_dev) {
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<double> tr(4096 * 12);
-    HIP_TRY(hipMemcpy(tr.data(), trace_dev, tr.size() * sizeof(double), hipMemcpyDeviceToHost));
-    (void)hipFree(trace_dev);
-    const char *path = getenv("DSP_TRACE_FILE");
-    if (FILE *f = fopen(path ? path : "dsp_trace.bin", "wb")) { fwrite(tr.data(), sizeof(double), tr.size(), f); fclose(f); }
-  }
-#endif
-  if (stats) {
-    std::memset(stats, 0, sizeof(*stats));
-    stats->grid_blocks = grid; stats->block_threads = 64 * a.waves_per_block; stats->lds_bytes = (int)lds;
-    stats->cols_per_lane = h->cpl; stats->rows_per_lane = h->rpl; stats->matreg = a.matreg; stats->simplex = h->simplex && !qp;
-    stats->quadratic = qp;
-    stats->rtc = (h->rtc_state[qp] == 1 && a.matreg) ? 1 : 0;
-    stats->lds_conflicts_identity = h->lds_conflicts[0] + h->lds_conflicts[2];
-    stats->lds_conflicts_chosen = a.matreg ? h->lds_conflicts[1] + h->lds_conflicts[3] : stats->lds_conflicts_identity;
-    if (sync_stats) {
-      HIP_TRY(hipStreamSynchronize(st));
-      HIP_TRY(hipEventElapsedTime(&stats->kernel_ms, h->ev0, h->ev1));
-      std::vector<int32_t> hs(B), hi(B);
-      HIP_TRY(hipMemcpy(hs.data(), batch->status, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-      if (batch->iters) HIP_TRY(hipMemcpy(hi.data(), batch->iters, B * sizeof(int32_t), hipMemcpyDeviceToHost));
-      for (int i = 0; i < B; ++i) {
-        stats->n_optimal += hs[i] == DSP_STATUS_OPTIMAL;
-        if (batch->iters) { stats->total_iterations += hi[i]; stats->max_iterations = std::max(stats->max_iterations, hi[i]); }
-      }
-    }
-  }
-  return DSP_OK;
+  stats = stats ? stats : &lent;
+  std::memset(stats, 0, sizeof(*stats));
+  if (h->streaming) return solve_streaming(h, batch, a, stats, timed, st);
+  if (a.opt.precision == 1) return solve_f32(h, batch, a, stats, timed, st);
+  return solve_fused(h, batch, a, stats, timed, st);
 }
 
 int dsp_spmv_step(dsp_handle *h, int32_t B, const double *X, const double *Y, double *AX, double *ATY, void *hipStream) {

@@ -1,4 +1,4 @@
-// dsp_device.hpp — plain structs shared by the kernels (dsp_kernels.hip) and the C ABI (dsp_capi.hip).
+// dsp_device.hpp — plain structs shared by the kernels (dsp_kernels.hip) and the C ABI (dsp_capi.hip, dsp_capi_loop.hip).
 #pragma once
 #ifdef __HIPCC_RTC__     /* run-time compilation (hiprtc, dsp_rtc.cpp): no system headers, the HIP device API is built in */
 #ifndef DSP_RTC_TYPES
@@ -179,6 +179,9 @@ hipError_t launch_simplex(const SimplexArgs &a, int grid, size_t lds, hipStream_
 // float32-iterate solve (dsp_qp.hip); returns the launch geometry it chose
 hipError_t launch_solve_f32(int cpl, int rpl, const SolveArgs &a, int num_cus, size_t lds_limit, hipStream_t st, int *grid,
                             int *threads, size_t *lds);
+// hand-off kernels of the rolling double loops (dsp_loop.hip): one thread per plant; phase 2 also advances the clock, in a launch of its own
+hipError_t launch_wb_rolling(const dsp_wb_state &st, const dsp_wb_model &rt, const dsp_wb_model &tr, int phase, int k, hipStream_t stream);
+hipError_t launch_loop_update(const dsp_loop_state &st, const dsp_loop_model &rt, const dsp_loop_model &tr, int phase, int k, hipStream_t stream);
 // bid-curve points of a solved batch (dsp_bids.hip)
 hipError_t launch_bid_points(const dsp_bid_request &rq, hipStream_t st);
 // stochastic mode of the wind + battery double loop (dsp_market.hip): scenario fan-out, curve + clearing

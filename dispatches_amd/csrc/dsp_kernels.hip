@@ -445,7 +445,7 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
     if (a.skip_solved == 1 && __builtin_amdgcn_readfirstlane(b.status[s]) != DSP_STATUS_UNSOLVED) continue;
     if (a.skip_solved == 2 && __builtin_amdgcn_readfirstlane(b.status[s]) != DSP_STATUS_SUSPECT) continue;
     // re-certification pass: only scenarios the earlier passes accepted WITHOUT a certified objective accuracy, from a cold start under
-    // this launch's options (another restart cadence / weight controller: dsp_capi.hip, kRecertify)
+    // this launch's options (another restart cadence / weight controller: dsp_capi.hip, recertify_passes)
     if constexpr (!MATREG) if (a.skip_solved == 3 && !(__builtin_amdgcn_readfirstlane(b.status[s]) == DSP_STATUS_OPTIMAL && (__builtin_amdgcn_readfirstlane(b.flags[s]) & DSP_FLAG_OBJ_WAIVED))) continue;
     // (certificate pass: the iterations the first pass spent on the scenario count; the limit covers both passes.  Re-certification:
     //  they count too, the limit is this pass's own)

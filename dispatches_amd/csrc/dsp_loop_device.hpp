@@ -1,5 +1,5 @@
 // dsp_loop_device.hpp — the device arithmetic that the double-loop kernels share (dsp_market.hip, dsp_param.hip, dsp_project.hip and the
-// hand-off kernels of dsp_capi.hip), written once.  Device-only, every function __forceinline__.
+// hand-off kernels of dsp_loop.hip), written once.  Device-only, every function __forceinline__.
 //
 //   loop_opaque           the register barrier between a product and the sum that takes it: the _rn intrinsics alone do not keep the
 //                         compiler from contracting the two into one fma.
