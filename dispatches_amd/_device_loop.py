@@ -109,7 +109,10 @@ class _DeviceLoop:
         from .workflow.market import plant_curves
         B, S, Tc = power.shape
         lanes = lambda a: a.expand(B, S, Tc).permute(1, 0, 2).reshape(S, B * Tc)
-        return plant_curves(torch, lanes(power), lanes(price), lanes((status == 0).reshape(B, S, 1)), p_min_cents=getattr(self, "p_min_cents", 0))
+        p_min = getattr(self, "p_min_cents", 0)
+        if getattr(self, "p_min_cents_plant", None) is not None:          # plants of different minimum power: lane (b, t) reads plant b's
+            p_min = self.p_min_cents_plant.repeat_interleave(Tc)
+        return plant_curves(torch, lanes(power), lanes(price), lanes((status == 0).reshape(B, S, 1)), p_min_cents=p_min)
 
     def _clear(self, U, M, count, lmp):
         import torch

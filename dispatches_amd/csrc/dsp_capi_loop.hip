@@ -1,4 +1,7 @@
 // dsp_capi_loop.hip — the C ABI of the double loops, the bid kernel and the market kernels: descriptors checked on the host, then one launch_*
+#include <cmath>
+#include <vector>
+
 #include "dsp_capi_internal.hpp"
 
 using namespace dsp;
@@ -66,6 +69,21 @@ static bool loop_market_prepare_ok(const dsp_loop_market_state *st, const dsp_lo
   return loop_cols_ok(m->pda_cols, m->T, m->n) && loop_terms_ok(m->pt_cols, m->T, m->n);
 }
 
+// per-plant minimum powers (ABI 20): a device array, read back and bounded like the scalar - except on a capturing stream, which
+// cannot be read on (the loops run their first day eagerly)
+static bool plant_p_min_ok(const dsp_loop_market_state *st, hipStream_t stream) {
+  if (!st->p_min_cents_plant || st->B == 0) return true;
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) return false;
+  if (capturing != hipStreamCaptureStatusNone) return true;
+  std::vector<int64_t> host((size_t)st->B);
+  if (hipMemcpyAsync(host.data(), st->p_min_cents_plant, host.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
+  if (hipStreamSynchronize(stream) != hipSuccess) return false;
+  for (int64_t v : host)
+    if (v < 0 || v > 2000000000ll) return false;
+  return true;
+}
+
 extern "C" {
 
 int dsp_wb_rolling_update(const dsp_wb_state *st, const dsp_wb_model *rt, const dsp_wb_model *tr, int32_t phase, int32_t k, void *hipStream) {
@@ -92,6 +110,25 @@ int dsp_loop_update(const dsp_loop_state *st, const dsp_loop_model *rt, const ds
     return DSP_ERR_INVALID;
   if (st->B == 0) return DSP_OK;
   HIP_TRY(launch_loop_update(*st, *rt, *tr, (int)phase, (int)k, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
+// the ledger of the implemented hour (ABI 20): every index and pointer a lane would use is checked here
+int dsp_loop_ledger(const dsp_loop_state *st, const dsp_loop_model *tr, const dsp_loop_ledger_desc *g, void *hipStream) {
+  if (!st || !tr || !g || st->B < 0 || tr->n < 1 || !tr->x) return DSP_ERR_INVALID;
+  if (g->n_forms < 1 || g->n_forms > DSP_LEDGER_MAX_FORMS || g->reserved != 0) return DSP_ERR_INVALID;
+  if (!g->acc || !g->hour_value || !g->coef || !g->constant) return DSP_ERR_INVALID;
+  if (g->coef_stride < 0 || (g->coef_stride != 0 && g->coef_stride < (int64_t)g->n_forms * DSP_LEDGER_MAX_TERMS)) return DSP_ERR_INVALID;
+  if (g->const_stride < 0 || (g->const_stride != 0 && g->const_stride < g->n_forms)) return DSP_ERR_INVALID;
+  for (int f = 0; f < g->n_forms; ++f) {
+    if (g->n_terms[f] < 0 || g->n_terms[f] > DSP_LEDGER_MAX_TERMS || !loop_cols_ok(g->cols[f], g->n_terms[f], tr->n)) return DSP_ERR_INVALID;
+    if (g->per_avail[f] == 0.0) continue;
+    // the wind available in the hour: the tracker's wind size (per plant with both of its pointers, ABI 16), the series, the clock
+    if (!std::isfinite(g->per_avail[f]) || tr->wind_cols[0] < 0 || !st->cf_series || !st->start || !st->hour || st->N < 1) return DSP_ERR_INVALID;
+    if (!plant_sizes_ok(tr->wind_kw_plant, tr->c0_base_plant, tr->wind_cols[0])) return DSP_ERR_INVALID;
+  }
+  if (st->B == 0) return DSP_OK;
+  HIP_TRY(launch_loop_ledger(*st, *tr, *g, (hipStream_t)hipStream));
   return DSP_OK;
 }
 
@@ -182,6 +219,7 @@ int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market
   if (!plant_sizes_ok(m->wind_kw_plant, m->c0_base_plant, m->wind_cols[0])) return DSP_ERR_INVALID;
   if (k < 0 ? !loop_cols_ok(m->pda_cols, T, m->n) : !loop_terms_ok(m->pt_cols, T, m->n)) return DSP_ERR_INVALID;
   if (tr && (!loop_tracker_ok(tr, T, st->state, st->cf_series) || tr->n_state != m->n_state || !tr->wind_kw_plant != !m->wind_kw_plant)) return DSP_ERR_INVALID;
+  if (!plant_p_min_ok(st, (hipStream_t)hipStream)) return DSP_ERR_INVALID;
   if (st->B == 0) return DSP_OK;
   HIP_TRY(launch_loop_market_clear(*st, *m, tr, (int)k, (int)T, dispatch, curve, count, (hipStream_t)hipStream));
   return DSP_OK;

@@ -1,4 +1,4 @@
-// dsp_loop.hip — the hand-off kernels of the rolling double loops, gfx950 only (dsp_wb_rolling_update, dsp_loop_update: dsp_capi_loop.hip)
+// dsp_loop.hip — the hand-off kernels of the rolling double loops, gfx950 only (dsp_wb_rolling_update, dsp_loop_update, dsp_loop_ledger: dsp_capi_loop.hip)
 #include <hip/hip_runtime.h>
 
 #include "dsp_device.hpp"
@@ -151,7 +151,33 @@ __global__ void __launch_bounds__(256) loop_update_kernel(dsp_loop_state s, dsp_
   }
 }
 
+// ---- the ledger of the implemented hour (dsp_loop_ledger, ABI 20): one lane per (form, plant), plant fastest -----------------------------
+// blockIdx.y is the form, so everything a lane reads from the descriptor is wave-uniform and the accumulator traffic of a wave is 64
+// consecutive doubles.  Runs between the tracking solve and phase 2 above: the clock is still the implemented hour's.
+__global__ void __launch_bounds__(256) loop_ledger_kernel(dsp_loop_state s, const double *x, int n, double wind_kw, const double *wind_kw_plant,
+                                                          dsp_loop_ledger_desc g) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+  if (b >= s.B) return;
+  const double per_avail = g.per_avail[f];
+  double avail0 = 0.0;
+  if (per_avail != 0.0) {
+    const double kw = wind_kw_plant ? wind_kw_plant[b] : wind_kw;
+    avail0 = loop_opaque(__dmul_rn(kw, s.cf_series[(s.start[b] + *s.hour) % s.N]));
+  }
+  const double *coef = g.coef + (size_t)b * g.coef_stride + f * DSP_LEDGER_MAX_TERMS;
+  const double v = loop_ledger_form(x + (size_t)b * n, g.cols[f], coef, g.n_terms[f], g.constant[(size_t)b * g.const_stride + f], per_avail, avail0);
+  const size_t at = (size_t)f * s.B + b;
+  g.hour_value[at] = v;
+  g.acc[at] = __dadd_rn(g.acc[at], loop_opaque(v));
+}
+
 namespace dsp {
+
+hipError_t launch_loop_ledger(const dsp_loop_state &st, const dsp_loop_model &tr, const dsp_loop_ledger_desc &ledger, hipStream_t stream) {
+  hipLaunchKernelGGL(loop_ledger_kernel, dim3((st.B + 255) / 256, ledger.n_forms), dim3(256), 0, stream, st, tr.x, (int)tr.n, tr.wind_kw,
+                     tr.wind_kw_plant, ledger);
+  return hipGetLastError();
+}
 
 // one thread per plant; phase 2 is followed by the clock's own launch
 template <class K, class S, class M>

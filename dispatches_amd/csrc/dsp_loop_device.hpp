@@ -8,6 +8,7 @@
 //                         (dsp_wb_model) and the descriptor model (dsp_loop_model) share exactly these two.
 //   loop_tracker_plant    the plant half of a tracker's LP over a dsp_loop_model: state columns fixed, wind bounds of the window,
 //                         objective constant.  The dispatch row of a period stays with the kernel that knows its value.
+//   loop_ledger_form      one linear form of the ledger of the implemented hour on the tracker's solution (dsp_loop_ledger).
 //   loop_emit_point       one point of a bid curve: running maximum of the price, cleared on the way.
 //   loop_curve_close      zero-filled tail of a curve, cleared cents -> MW.
 //   loop_curve_and_clear  sorted keys -> curve points, count, tail, cleared dispatch, for a curve that starts at p_min.
@@ -68,6 +69,16 @@ __device__ __forceinline__ void loop_tracker_plant(const dsp_loop_model &tr, int
     c0 = loop_c0(c0, tr.waste_per_kw, loop_wind_window(ub, tr.wind_cols, tr.T, kw, cf_series, first, N));
   }
   tr.c0[b] = c0;
+}
+
+// one linear form of the ledger (dsp_loop_ledger_desc) on a plant's solution x: the constant, E terms folded in by fma in the order of e,
+// then the wind available in the hour times its factor - the fixed order that BatchedDoubleLoop._ledger_values states with exact_fma
+__device__ __forceinline__ double loop_ledger_form(const double *x, const int32_t *cols, const double *coef, int E, double constant,
+                                                   double per_avail, double avail0) {
+  double v = constant;
+  for (int e = 0; e < E; ++e) v = fma(coef[e], x[cols[e]], v);
+  if (per_avail != 0.0) v = fma(per_avail, avail0, v);
+  return v;
 }
 
 // point `pos` of a curve: (U, running maximum of M) in cents; a price taker is cleared up to the last point whose price the lmp covers

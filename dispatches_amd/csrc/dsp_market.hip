@@ -324,7 +324,7 @@ __global__ void __launch_bounds__(256) loop_market_clear_kernel(dsp_loop_market_
   const int b = g / T, t = g - b * T;
   const int S = s.S;
   const long long h = *s.hour, st0 = s.start[b];
-  const long long pmin = s.p_min_cents;
+  const long long pmin = s.p_min_cents_plant ? s.p_min_cents_plant[b] : s.p_min_cents;      // (ABI 20: per plant at the site of the scalar)
   const int hod = k < 0 ? 0 : k;
   const double *series = k < 0 ? s.da_series : s.rt_series;
   const int ca = k < 0 ? m.pda_cols[t] : m.pt_cols[t][0], cb = k < 0 ? -1 : m.pt_cols[t][1];

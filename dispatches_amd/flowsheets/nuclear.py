@@ -16,10 +16,11 @@ from . import parameters as prm
 from . import units
 
 
-def create_multiperiod_nuclear_model(b, n_time_points=4, h2_demand=0.35, demand_type="variable", h2_price=4):
+def create_multiperiod_nuclear_model(b, n_time_points=4, h2_demand=0.35, demand_type="variable", h2_price=4, pem_mw=None, tank_kg=None):
+    """pem_mw / tank_kg: the PEM and tank capacities of THIS plant (None: the flowsheet's, parameters.py)"""
     np_kw = prm.np_capacity_mw * 1e3
-    pem_kw = prm.nuclear_pem_capacity_mw * 1e3
-    tank_mol = prm.tank_capacity_kg / prm.mw_h2
+    pem_kw = (prm.nuclear_pem_capacity_mw if pem_mw is None else float(pem_mw)) * 1e3
+    tank_mol = (prm.tank_capacity_kg if tank_kg is None else float(tank_kg)) / prm.mw_h2
     demand_mol_s = h2_demand / prm.mw_h2
     holdup_init = b.var("h2_tank.tank_holdup_previous[0]", 0.0, 0.0, mutable=True, hull=(0.0, tank_mol))
     periods = []
@@ -51,7 +52,10 @@ class MultiPeriodNuclear(units.ResultRecords):
     # mol/s and kW coefficients; geometric pre-equilibration halves the PDLP iteration count of this flowsheet
     solver_hints = {"geo_iters": 8}
 
-    def __init__(self, model_data):
+    def __init__(self, model_data, pem_mw=None, tank_kg=None, h2_price=4, h2_demand=0.35):
+        """pem_mw [MW], tank_kg [kg], h2_price [$/kg], h2_demand [kg/s]: the plant's sizes and hydrogen market (defaults: the
+        flowsheet's 100 MW, parameters.tank_capacity_kg, 4 $/kg, 0.35 kg/s), so that host objects of a given size exist"""
+        self._pem_mw, self._tank_kg, self._h2_price, self._h2_demand = pem_mw, tank_kg, h2_price, h2_demand
         self.mp_nuclear = None
         self.result_list = []
         self.model_data = model_data
@@ -62,7 +66,8 @@ class MultiPeriodNuclear(units.ResultRecords):
     def populate_model(self, blk, horizon):
         if not blk.is_constructed():
             blk.construct()
-        mp = create_multiperiod_nuclear_model(blk, n_time_points=horizon)
+        mp = create_multiperiod_nuclear_model(blk, n_time_points=horizon, h2_demand=self._h2_demand, h2_price=self._h2_price,
+                                              pem_mw=self._pem_mw, tank_kg=self._tank_kg)
         blk.nuclear = mp
         mp["holdup_init"].fix(0)                                         # reference :203
         blk.HOUR = range(horizon)

@@ -109,10 +109,10 @@ EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_
                     "dsp_get_scaling", "dsp_destroy", "dsp_strerror", "dsp_last_hip_error", "dsp_version",
                     "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
                     "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step", "dsp_loop_project",
-                    "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare")
+                    "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare", "dsp_loop_ledger")
 
 
-ABI_VERSION = 19         # DSP_VERSION of the include/dsp_hip.h these structures mirror
+ABI_VERSION = 20         # DSP_VERSION of the include/dsp_hip.h these structures mirror
 
 
 BID_MAX_HOURS, BID_MAX_SCENARIOS = 64, 16384
@@ -158,13 +158,14 @@ class DspLoopMarketModel(C.Structure):
 
 
 class DspLoopMarketState(C.Structure):
-    """include/dsp_hip.h: dsp_loop_market_state (ABI 14; self_schedule, curve_slots: ABI 18; coupled: ABI 19)"""
+    """include/dsp_hip.h: dsp_loop_market_state (ABI 14; self_schedule, curve_slots: ABI 18; coupled: ABI 19; p_min_cents_plant: ABI 20)"""
     _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("D", C.c_int32), ("N", C.c_int32), ("backcast", C.c_int32), ("price_taker", C.c_int32),
                 ("start", C.c_void_p), ("hour", C.c_void_p),
                 ("da_series", C.c_void_p), ("rt_series", C.c_void_p), ("cf_series", C.c_void_p),
                 ("state", C.c_void_p), ("da_offer", C.c_void_p), ("da_prices", C.c_void_p),
                 ("bad", C.c_void_p), ("uncertified", C.c_void_p), ("p_min_cents", C.c_int64),
-                ("rt_history_lag_days", C.c_int32), ("self_schedule", C.c_int32), ("curve_slots", C.c_int32), ("coupled", C.c_int32)]
+                ("rt_history_lag_days", C.c_int32), ("self_schedule", C.c_int32), ("curve_slots", C.c_int32), ("coupled", C.c_int32),
+                ("p_min_cents_plant", C.c_void_p)]
 
 
 class DspLoopParamState(C.Structure):
@@ -187,6 +188,17 @@ class DspLoopProjectState(C.Structure):
                 ("bad", C.c_void_p), ("uncertified", C.c_void_p),
                 ("da_offer", C.c_void_p), ("da_prices", C.c_void_p), ("pend_offer", C.c_void_p), ("pend_prices", C.c_void_p),
                 ("da_curve", C.c_void_p), ("da_count", C.c_void_p), ("pend_curve", C.c_void_p), ("pend_count", C.c_void_p)]
+
+
+LEDGER_MAX_FORMS, LEDGER_MAX_TERMS = 8, 8
+
+
+class DspLoopLedgerDesc(C.Structure):
+    """include/dsp_hip.h: dsp_loop_ledger_desc (ABI 20) - the linear forms of the ledger of the implemented hour"""
+    _fields_ = [("n_forms", C.c_int32), ("reserved", C.c_int32), ("n_terms", C.c_int32 * LEDGER_MAX_FORMS),
+                ("cols", (C.c_int32 * LEDGER_MAX_TERMS) * LEDGER_MAX_FORMS), ("per_avail", C.c_double * LEDGER_MAX_FORMS),
+                ("coef", C.c_void_p), ("constant", C.c_void_p), ("coef_stride", C.c_int64), ("const_stride", C.c_int64),
+                ("acc", C.c_void_p), ("hour_value", C.c_void_p)]
 
 
 def source_hash(root: Optional[str] = None) -> Optional[str]:
@@ -284,6 +296,8 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_param_step.restype = C.c_int
     lib.dsp_loop_project.argtypes = [C.POINTER(DspLoopProjectState), C.POINTER(DspLoopModel), i32, i32, vp]
     lib.dsp_loop_project.restype = C.c_int
+    lib.dsp_loop_ledger.argtypes = [C.POINTER(DspLoopState), C.POINTER(DspLoopModel), C.POINTER(DspLoopLedgerDesc), vp]
+    lib.dsp_loop_ledger.restype = C.c_int
     lib.dsp_last_hip_error.restype = C.c_int
     if path == _LIB_PATH:
         _lib = lib

@@ -140,7 +140,9 @@ class BatchedWindBatteryDoubleLoop(_DeviceLoop):
                  day_ahead_horizon=48, real_time_horizon=4, tracking_horizon=4, wind_mw=200.0, batt_mw=25.0,
                  price_cap=500.0, warm_start=True, lp_backend=None, use_graphs=True, use_fused=True, record=None, simplex_warm=True, warm_patience=10000,
                  n_price_scenarios=1, forecaster="perfect", max_historical_days=10, market="stub"):
-        """lp_backend: None = the HIP solver on GPU `device`; tests pass a factory lp -> object with DeviceLP.solve's
+        """(This loop reports electricity-market revenue only.  The per-plant ledger - total cost, missed delivery, curtailment, profit -
+        is BatchedDoubleLoop("wind_battery", ..., ledger=True) of rolling_flowsheets.py, the descriptor loop that covers this flowsheet.)
+        lp_backend: None = the HIP solver on GPU `device`; tests pass a factory lp -> object with DeviceLP.solve's
         signature working on CPU tensors (tests/_highs_solver.py::HighsTensorLP), which runs the SAME window / objective /
         state-hand-off logic without a GPU.
         use_graphs: on the GPU, the day-ahead step and the 24 hour steps of a day (about 45 small device operations + two

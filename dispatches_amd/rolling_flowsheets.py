@@ -143,6 +143,7 @@ class _Model:
         self.PT, self.PT_const = t(PT), t(PT_const)                       # [T, n], [T]
         self.state_init = [int(c) for c in state_init]                    # columns fixed to the realised state
         self.pda_cols = self.track_rows = self.state_real = None          # day-ahead power columns (bidding models); dispatch rows, state after period 0 (trackers)
+        self.c_static = None                                              # [rows, n] per-row cost vector without prices where plants differ in it (nuclear h2_price), else base_c
         self.kw_plant = self.c0_plant = None                              # per-plant sizes: wind kW [B, 1], objective constant [B] (set_plant_sizes)
         self.per_plant = None                                             # rows per plant of a bidding model (None: the loop's S)
         self.wind = None
@@ -285,6 +286,87 @@ def _describe(cls, m, n_state):
     return w
 
 
+LEDGER_MAX_FORMS = LEDGER_MAX_TERMS = 8                # DSP_LEDGER_MAX_FORMS / DSP_LEDGER_MAX_TERMS of include/dsp_hip.h
+
+
+def _ledger_expression(block, n, d, family, scale, per_avail):
+    """family[0] * scale of a populated block as (row [n], constant, per_avail * scale), the capacity-factor constant per_avail *
+    (the block's wind_kw * the series' cf[0], what every template and model object is built on) taken out of the constant.  The ONE
+    statement of a ledger constant: the template's (_ledger_forms) and every sized plant's (_ledger_setup)."""
+    rows, const = _dense_rows(block, family, n, [0])
+    row, const = rows[0], float(const[0])
+    if per_avail:
+        fam = getattr(block, d["family"])
+        wind = fam["periods"][0]["wind"].index
+        if row[wind] != -per_avail:
+            raise RuntimeError(f"{family}[0] carries the wind column with {row[wind]!r}, not with minus its curtailment weight {per_avail!r}")
+        const -= per_avail * float(fam["wind_kw"] * d["prices"][2][0])
+    return row * scale, const * scale, per_avail * scale
+
+
+def _ledger_wind_expressions(d):
+    """key -> (expression family, scale, per_avail) of the two forms whose constant carries the capacity factor and the wind size"""
+    per_kw, to_mwh = d["waste"]
+    return {"tot_cost": ("tot_cost", 1.0, d["per_kw"]), "curtailed_mwh": ("wind_waste", to_mwh, per_kw)}
+
+
+def _ledger_forms(flowsheet, tr_model, d, with_h2_kg=True):
+    """The ledger of the implemented hour as linear forms over the TRACKER's period 0, taken from the host model's own expressions by the
+    route P_T takes (_dense_rows) -> list of (key, row [n], constant, per_avail).  A form's value is row . x + constant + per_avail *
+    avail0, avail0 = wind_kw * cf of the hour; `constant` is the expression's constant with the TEMPLATE's capacity-factor share taken
+    out (as _Model.__init__ does for c0): the window's enters at run time.
+        tot_cost        tot_cost[0] as the flowsheet defines it (nuclear: the hydrogen credit included)
+        under_mwh, over_mwh     the tracker's power_underdelivered[0] / power_overdelivered[0]
+        curtailed_mwh   wind_waste[0] in MWh (wind + PEM states it in kW)
+        h2_kg           wind + PEM: MultiPeriodWindPEM._h2_kg_per_hr(pem_elec[0]); nuclear: outlet_to_pipeline[0] * mw_h2 * 3600
+                        (with_h2_kg=False: the parametrized wind + PEM loop, which books it in a kernel phase of its own)
+        pem_mwh         PEM electricity of the hour
+        h2_revenue      nuclear: h2_kg * h2_price, the share of tot_cost that is revenue"""
+    from .flowsheets import parameters as prm
+    block, n = tr_model.block, tr_model.lp.n
+    fam = getattr(block, d["family"])
+    p0 = fam["periods"][0]
+
+    def unit(var, coef=1.0):
+        row = np.zeros(n)
+        row[var.index] = coef
+        return row
+
+    windy = d.get("waste") is not None
+    expression = lambda key: _ledger_expression(block, n, d, *(_ledger_wind_expressions(d)[key] if windy else ("tot_cost", 1.0, 0.0)))
+    forms = [("tot_cost",) + expression("tot_cost"),
+             ("under_mwh", unit(tr_model.power_underdelivered[0]), 0.0, 0.0), ("over_mwh", unit(tr_model.power_overdelivered[0]), 0.0, 0.0)]
+    if windy:
+        forms.append(("curtailed_mwh",) + expression("curtailed_mwh"))
+    if flowsheet == "wind_pem":
+        if with_h2_kg:
+            forms.append(("h2_kg", unit(p0["pem_elec"], prm.pem_electricity_to_mol / prm.h2_mols_per_kg * 3600), 0.0, 0.0))
+        forms.append(("pem_mwh", unit(p0["pem_elec"], 1e-3), 0.0, 0.0))
+    if flowsheet == "nuclear":
+        h2_kg = prm.mw_h2 * 3600
+        credit = -float(block.expressions["tot_cost"][0].coef[p0["outlet_to_pipeline"].index])      # mw_h2 * 3600 * h2_price, as tot_cost carries it
+        forms += [("h2_kg", unit(p0["outlet_to_pipeline"], h2_kg), 0.0, 0.0), ("pem_mwh", unit(p0["pem_elec"], 1e-3), 0.0, 0.0),
+                  ("h2_revenue", unit(p0["outlet_to_pipeline"], credit), 0.0, 0.0)]
+    return forms
+
+
+def _describe_ledger(L):
+    """-> the DspLoopLedgerDesc (hip_solver.py) of a loop's ledger L (BatchedDoubleLoop._ledger_setup); its columns are the tracker's"""
+    from .hip_solver import DspLoopLedgerDesc
+    g = DspLoopLedgerDesc()
+    g.n_forms = len(L["keys"])
+    for f, cols in enumerate(L["cols"]):
+        g.n_terms[f] = len(cols)
+        for e, col in enumerate(cols):
+            g.cols[f][e] = col
+        g.per_avail[f] = L["per_avail"][f]
+    g.coef, g.constant = L["coef"].data_ptr(), L["const"].data_ptr()
+    g.coef_stride = L["coef"].stride(0) if L["coef"].dim() == 3 else 0          # [B, F, 8] per plant, [F, 8] shared
+    g.const_stride = L["const"].stride(0) if L["const"].dim() == 2 else 0       # [B, F] per plant, [F] shared
+    g.acc, g.hour_value = L["acc"].data_ptr(), L["hour"].data_ptr()
+    return g
+
+
 _WIND_BATTERY_SIZES = dict(wind_mw=200.0, battery_mw=25.0, battery_mwh=100.0)      # the plant of the reference's wind + battery double loop
 
 
@@ -307,6 +389,7 @@ def _templates(flowsheet, day_ahead_horizon, tracking_horizon, sizes=None):
                     real=lambda blk: [getattr(blk, fam)["periods"][0]["state_of_charge"].index, getattr(blk, fam)["periods"][0]["energy_throughput"].index])
         prices = (np.clip(s["da_lmp"], 0.0, cap), np.clip(s["rt_lmp"], 0.0, cap), s["rt_cf"])
         desc["da_cf"] = s["da_cf"]
+        desc["waste"] = (1e-3, 1.0)                  # wind_waste[t] = 1e-3 (available kW - wind): MW, the ledger's MWh of an hour as it stands
     elif flowsheet == "wind_pem":
         series, stride, cap = "rts_gmlc_303.npz", 37, 500.0
         bidder, da = scenarios.wind_pem_batch(1, day_ahead_horizon, _NoSolver(), series=series, stride=stride,
@@ -316,13 +399,14 @@ def _templates(flowsheet, day_ahead_horizon, tracking_horizon, sizes=None):
         tr_obj = mo.__class__(mo.model_data, wind_capacity_factors=list(s["rt_cf"][:tracking_horizon]), wind_pmax_mw=mo._wind_pmax_mw,
                               pem_pmax_mw=mo._pem_pmax_mw)
         fam = "windPEM"
-        desc = dict(family=fam, per_kw=1.0, decimals=[], init=lambda blk: [], real=lambda blk: [], da_cf=s["da_cf"])
+        desc = dict(family=fam, per_kw=1.0, decimals=[], init=lambda blk: [], real=lambda blk: [], da_cf=s["da_cf"],
+                    waste=(1.0, 1e-3))               # wind_waste[t] = available kW - wind, in kW: 1e-3 of it is the ledger's MWh of an hour
         prices = (np.clip(s["da_lmp"], 0.0, cap), np.clip(s["rt_lmp"], 0.0, cap), s["rt_cf"])
     elif flowsheet == "nuclear":
         stride = 29
-        bidder, da = scenarios.nuclear_batch(1, day_ahead_horizon, _NoSolver())
+        bidder, da = scenarios.nuclear_batch(1, day_ahead_horizon, _NoSolver(), **(sizes or {}))      # sizes: pem_mw, tank_kg, h2_price, h2_demand
         s = scenarios.load_series("nuclear_price_taker_lmps.npz")        # bus Attlee, generator 121_NUCLEAR_1 (rts_gmlc_15_500.csv)
-        tr_obj = bidder.bidding_model_object.__class__(bidder.bidding_model_object.model_data)
+        tr_obj = bidder.bidding_model_object.__class__(bidder.bidding_model_object.model_data, **(sizes or {}))
         fam = "nuclear"
         desc = dict(family=fam, per_kw=None, decimals=[0],
                     init=lambda blk: [blk.nuclear["holdup_init"].index], real=lambda blk: [blk.nuclear["periods"][0]["tank_holdup"].index])
@@ -388,7 +472,8 @@ class BatchedDoubleLoop(_DeviceLoop):
     def __init__(self, flowsheet, n_scenarios, device=0, first_scenario=0, day_ahead_horizon=48, tracking_horizon=4, lp_backend=None,
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
                  market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
-                 battery_mwh=None, ruc_hour=None, scenario_coupling="independent"):
+                 battery_mwh=None, ruc_hour=None, scenario_coupling="independent", ledger=False, pem_mw=None, tank_kg=None,
+                 h2_price=None, h2_demand=None):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -435,7 +520,29 @@ class BatchedDoubleLoop(_DeviceLoop):
         solve stand for its S pairs and `uncertified` counts a flagged plant once.  The hourly steps, results() and reset() are the
         stochastic mode's.  The day-ahead step replays from a graph where the coupled LP stays in the fused kernels, as the
         self-schedule's.  Refused (ValueError): another value, bidder other than "lp", ruc_hour, per-plant sizes, bid_price /
-        storage_mw, forecaster="perfect", n_price_scenarios=1 (no pairs: that is the independent loop)."""
+        storage_mw, forecaster="perfect", n_price_scenarios=1 (no pairs: that is the independent loop).
+        ledger: False (the loops above: same launches, same bits) or True: every implemented hour is BOOKED per plant, after the tracking
+        solve and before the hand-off, from the tracker's solution of its period 0 - tot_cost [$] (the flowsheet's own tot_cost[0], its
+        constant at this hour's capacity factor and this plant's wind size; nuclear: the hydrogen credit included), under_mwh / over_mwh
+        (the tracker's missed delivery), curtailed_mwh (wind flowsheets), h2_kg and pem_mwh (wind + PEM, nuclear), h2_revenue [$]
+        (nuclear); _ledger_forms.  Works in every mode (each ends an hour with a tracking solve and a hand-off); the projection
+        tracker's chain of ruc_hour is not booked, those hours are not implemented.  results() gains these keys and profit = obj -
+        tot_cost; ledger_keys names the rows of ledger_acc / ledger_hour [F, B] (running sums / the last hour's values); reset()
+        zeroes both.  With bidder="parametrized" on wind + PEM h2_kg stays the existing accumulator, the ledger adds no second one.
+        Arithmetic (the kernel's, dsp_loop_ledger, and bit for bit the tensor form's, _ledger_book): constant, then one fma per term in
+        the form's order, then one fma with the hour's available wind, then a plain add into the accumulator.  Refused (ValueError): a
+        form of more than 8 terms, more than 8 forms.
+        pem_mw [MW], tank_kg [kg], h2_price [$/kg], h2_demand [kg/s] ("nuclear" only; scalars or arrays [B]; what is left None keeps the
+        flowsheet's 100 MW, parameters.tank_capacity_kg, 4 $/kg, 0.35 kg/s; all None = the loop above, bit for bit): every plant's
+        own PEM, tank and hydrogen market, so that the reference's (h2 price x PEM size) study is one batch (sweeps.nuclear_sweep).
+        None is a matrix coefficient: pem_mw is the upper bound of the np_to_pem columns, tank_kg of the holdup columns, h2_demand of
+        the pipeline columns, h2_price the objective entry of the pipeline columns - all static, written once per row of every model
+        (the projection tracker included) - and h2_price the per-plant coefficient of the ledger's tot_cost / h2_revenue.  One
+        template at the batch's largest values (_check_template).  The bid curves start at the plant's own p_min = p_max - pem_mw
+        (the notebook: 500 - 100 = 400), so a larger PEM can offer below 400 MW (dsp_loop_market_state::p_min_cents_plant); p_max
+        stays 500.  They combine with plant_windows, n_price_scenarios, forecaster, market, ruc_hour, graphs and ledger.  Refused
+        (ValueError): another flowsheet, bidder="self_schedule" / "parametrized", scenario_coupling="monotone", a wrong length,
+        non-finite or negative values, pem_mw outside (0, 500]."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
@@ -444,7 +551,11 @@ class BatchedDoubleLoop(_DeviceLoop):
         bid_price, storage_mw, ruc_hour, sizes, plant_windows = self._validate(
             forecaster, market, bidder, tracking_horizon, bid_price, storage_mw, ruc_hour, wind_mw, battery_mw, battery_mwh, plant_windows,
             scenario_coupling)
-        self.ruc_hour, self.sized = ruc_hour, sizes is not None
+        nuclear = self._nuclear_operands(pem_mw, tank_kg, h2_price, h2_demand)
+        self.nuclear_sized = nuclear is not None
+        if self.nuclear_sized:
+            sizes = nuclear
+        self.ruc_hour, self.sized = ruc_hour, sizes is not None and not self.nuclear_sized
         self.forecaster, self.market = forecaster, market
         self.stochastic = forecaster != "perfect" or market != "stub" or self.parametrized or self.self_schedule
         rows = 1 if self.parametrized else B if self.self_schedule else B * S                           # rows of the bidding batches (plant b, scenario i: row b * S + i; no bidding LP is solved in parametrized mode: one template row)
@@ -453,7 +564,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         bidder, da_model, rt_model, tracker, d = _templates(flowsheet, day_ahead_horizon, tracking_horizon,
                                                             None if sizes is None else {k: float(v.max()) for k, v in sizes.items()})
         tr_model = tracker.model
-        if self.sized:
+        if self.sized or self.nuclear_sized:
             _check_template(flowsheet, day_ahead_horizon, tracking_horizon, (da_model, rt_model, tr_model))
         self.bidder, self.tracker_template = bidder, tracker
         da_s, rt_s, cf_s = d["prices"]
@@ -510,7 +621,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         self._graphs, self._warm, self._pending = {}, False, False
         self._da_capturable = None                    # a coupled day-ahead LP: may its step be a graph node (day_ahead)
         self.use_fused = bool(use_fused) and lp_backend is None and self.rt.T <= 16 and self.tr.T <= 16 and len(self.scale) <= 2
-        self.exact = self.sized or self.parametrized or self.coupled_da       # these state phase 2 of dsp_loop_update exactly, sums included (_hand_off)
+        self.exact = self.sized or self.nuclear_sized or self.parametrized or self.coupled_da       # these state phase 2 of dsp_loop_update exactly, sums included (_hand_off)
         # what reset() zeroes and what results() reports beyond obj / energy_mwh / state: every setup below adds its own
         self._zeroed = [self.state, self.revenue, self.energy_mwh, self.delivered, self.da_offer, self.da_prices, self.hour_t, self.uncertified, self.bad]
         self._result_keys = []
@@ -529,6 +640,12 @@ class BatchedDoubleLoop(_DeviceLoop):
             self._market_buffers(S + 1)
         if self.ruc_hour is not None:
             self._ruc_setup(mk(tr_model, B))
+        self.p_min_cents_plant = None
+        if self.nuclear_sized:
+            self._nuclear_setup(nuclear, tr_model)
+        self.ledger = bool(ledger)
+        if self.ledger:
+            self._ledger_setup(d, tr_model)
         if self.use_fused:
             self._fused_setup()
             if self.parametrized:
@@ -646,6 +763,62 @@ class BatchedDoubleLoop(_DeviceLoop):
             raise ValueError("wind_mw + battery_mw must stay below 2e7")
         return out
 
+    def _nuclear_operands(self, pem_mw, tank_kg, h2_price, h2_demand):
+        """validated nuclear operands -> dict of float64 arrays [B] (what was left None at the flowsheet's default), or None without any"""
+        from .flowsheets import parameters as prm
+        given = {k: v for k, v in (("pem_mw", pem_mw), ("tank_kg", tank_kg), ("h2_price", h2_price), ("h2_demand", h2_demand)) if v is not None}
+        if not given:
+            return None
+        names = ", ".join(given)
+        if self.flowsheet != "nuclear":
+            raise ValueError(f"{names}: the nuclear flowsheet's operands, not {self.flowsheet!r}'s")
+        if self.parametrized or self.self_schedule:
+            raise ValueError(f"{names}: per-plant sizes belong to bidder='lp'")
+        if self.monotone:
+            raise ValueError(f"{names}: per-plant sizes belong to scenario_coupling='independent' (a monotone batch of different plants is a follow-up, DESIGN 9)")
+        out = {name: _per_plant(v, name, self.B, positive=name == "pem_mw") for name, v in given.items()}
+        if "pem_mw" in out and (out["pem_mw"] > prm.np_capacity_mw).any():
+            raise ValueError(f"pem_mw must be > 0 and at most the plant's {prm.np_capacity_mw:g} MW")
+        for name, default in (("pem_mw", prm.nuclear_pem_capacity_mw), ("tank_kg", prm.tank_capacity_kg), ("h2_price", 4.0), ("h2_demand", 0.35)):
+            out.setdefault(name, np.full(self.B, float(default)))
+        return out
+
+    def _nuclear_setup(self, ops, tr_model):
+        """the per-plant operands of a nuclear batch, written ONCE into the per-row tensors of every model (rows b * S + i of the bidding
+        models, row b of the tracker and of the projection tracker): np_to_pem <= pem kW, tank_holdup <= tank mol (every period but the
+        last, as the flowsheet), outlet_to_pipeline <= demand mol/s, and the pipeline columns' objective entry -(mw_h2 * 3600 * h2_price)
+        in the arithmetic of the flowsheet's tot_cost.  No step rewrites those; c_static keeps the deterministic tensor form from doing
+        so.  p_min_cents_plant: the curves' first point, p_max - pem_mw in integer cents."""
+        import torch
+        from .flowsheets import parameters as prm
+        B, S, dev = self.B, self.S, self.dev
+        self.pem_mw, self.tank_kg, self.h2_price, self.h2_demand = (ops[k] for k in ("pem_mw", "tank_kg", "h2_price", "h2_demand"))
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float64), device=dev)
+        pem_kw, tank_mol, demand = self.pem_mw * 1e3, self.tank_kg / prm.mw_h2, self.h2_demand / prm.mw_h2
+        credit = np.array([prm.mw_h2 * 3600 * float(p) for p in self.h2_price])      # tot_cost: - outlet_to_pipeline * (mw_h2 * 3600 * h2_price)
+        at = int(np.argmax(self.h2_price))                                          # the template IS the largest price: the same number, bit for bit
+        models = [(self.da, self.bidder.day_ahead_model, S), (self.rt, self.bidder.real_time_model, S), (self.tr, tr_model, 1)]
+        if self.ruc_hour is not None:
+            models.append((self.pj, tr_model, 1))
+        for m, model, per in models:
+            periods = model.block.nuclear["periods"]
+            pem, out = [p["pem_elec"].index for p in periods], [p["outlet_to_pipeline"].index for p in periods]
+            hold = [p["tank_holdup"].index for p in periods[:-1]]
+            base = m.base_c[out].cpu().numpy()
+            if not (base == -credit[at]).all():
+                raise RuntimeError(f"the template's pipeline objective entries {base!r} are not minus the hydrogen credit {credit[at]!r}")
+            rows = lambda a: t(np.repeat(a, per))[:, None]
+            m.ub[:, pem], m.ub[:, out] = rows(pem_kw), rows(demand)
+            if hold:
+                m.ub[:, hold] = rows(tank_mol)
+            m.c[:, out] = rows(-credit)
+            m.c_static = m.base_c.repeat(m.c.shape[0], 1)
+            m.c_static[:, out] = rows(-credit)
+            m.pem_cols, m.out_cols, m.hold_cols = pem, out, hold
+        md = self.bidder.bidding_model_object.model_data
+        self.p_min_cents_plant = torch.as_tensor(np.round((float(md.p_max) - self.pem_mw) * 100.0).astype(np.int64), device=dev)
+        self._credit = credit
+
     def _sizes_setup(self, sizes, d, tracker):
         """the per-plant operands of a sized batch: wind kW and objective constant [B] of each of the three models (host, float64,
         once), and the battery's static bounds written into the per-row tensors (rows b * S + i of the bidding models, row b of the
@@ -664,6 +837,7 @@ class BatchedDoubleLoop(_DeviceLoop):
                                     battery_pmax_mw=mo._battery_pmax_mw, battery_energy_capacity_mwh=mo._battery_energy_capacity_mwh)
             return mo.__class__(mo.model_data, wind_capacity_factors=list(cf[:max(self.da.T, self.rt.T, self.tr.T)]), wind_pmax_mw=w,
                                 pem_pmax_mw=mo._pem_pmax_mw)
+        self._sized_model_object = model_object                            # (the ledger's per-plant constants: _ledger_setup)
         distinct, inverse = np.unique(self.wind_mw, return_inverse=True)
         for m, family in ((self.da, mo.total_cost), (self.rt, mo.total_cost), (self.tr, tracker.tracking_model_object.total_cost)):
             c0 = np.array([_objective_constant(model_object(float(w)), m.T, family, m.wind[2], cf) for w in distinct])
@@ -681,6 +855,48 @@ class BatchedDoubleLoop(_DeviceLoop):
             m.batt_cols, m.soc_rows = cols, rows
             m.ub[:, cols] = t(np.repeat(batt_kw, per))[:, None]
             m.rhi[:, rows] = t(np.repeat(batt_kwh, per))[:, None]
+
+    def _ledger_setup(self, d, tr_model):
+        """the ledger's operands, once: the forms of _ledger_forms as index lists and device arrays - coefficients [F, 8] and constants
+        [F] shared by all plants, or per plant ([B, F, 8] / [B, F]) where plants differ: a sized wind batch carries each plant's own
+        constants (fixed O&M on ITS wind_kw), computed like its objective constant from a model object of its size - and the
+        accumulators / last hour's values [F, B]"""
+        import torch
+        from .lp import LinearBlock
+        B, dev, tr = self.B, self.dev, self.tr
+        forms = _ledger_forms(self.flowsheet, tr_model, d, with_h2_kg=not (self.parametrized and self.flowsheet == "wind_pem"))
+        if len(forms) > LEDGER_MAX_FORMS:
+            raise ValueError(f"the ledger takes at most {LEDGER_MAX_FORMS} forms, not {len(forms)}")
+        keys, cols, coef, const, per_avail = [], [], np.zeros((len(forms), LEDGER_MAX_TERMS)), np.zeros(len(forms)), []
+        for f, (key, row, c, pa) in enumerate(forms):
+            nz = np.nonzero(row)[0]
+            if len(nz) > LEDGER_MAX_TERMS:
+                raise ValueError(f"the ledger's form {key!r} has {len(nz)} terms: the kernel takes at most {LEDGER_MAX_TERMS}")
+            keys.append(key)
+            cols.append([int(j) for j in nz])
+            coef[f, :len(nz)], const[f] = row[nz], c
+            per_avail.append(float(pa))
+        if self.sized:                                 # per-plant constants: the same expressions of a model object of the plant's wind size
+            distinct, inverse = np.unique(self.wind_mw, return_inverse=True)
+            each = np.tile(const, (len(distinct), 1))
+            for i, w in enumerate(distinct):
+                block = LinearBlock("fs")
+                self._sized_model_object(float(w)).populate_model(block, tr.T)
+                for key, spec in _ledger_wind_expressions(d).items():
+                    each[i, keys.index(key)] = _ledger_expression(block, len(block.col_names), d, *spec)[1]
+            const = each[inverse]
+        if self.nuclear_sized:                         # per-plant coefficients: the hydrogen credit at the plant's own price
+            out0 = tr.out_cols[0]
+            coef = np.tile(coef, (B, 1, 1))
+            coef[:, keys.index("tot_cost"), cols[keys.index("tot_cost")].index(out0)] = -self._credit
+            coef[:, keys.index("h2_revenue"), cols[keys.index("h2_revenue")].index(out0)] = self._credit
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float64), device=dev)
+        z = lambda: torch.zeros((len(keys), B), dtype=torch.float64, device=dev)
+        self.ledger_keys = keys
+        self.ledger_acc, self.ledger_hour = z(), z()
+        self._ledger = dict(keys=keys, cols=cols, per_avail=per_avail, coef=t(coef), const=t(const), acc=self.ledger_acc, hour=self.ledger_hour,
+                            per_avail_t=t(per_avail))
+        self._zeroed += [self.ledger_acc, self.ledger_hour]
 
     def _parametrized_setup(self, d, bid_price, storage_mw, tr_model, fam):
         import torch
@@ -736,6 +952,8 @@ class BatchedDoubleLoop(_DeviceLoop):
         st.bad, st.uncertified = self.bad.data_ptr(), self.uncertified.data_ptr()
         self._loop_state = st
         self._loop_rt, self._loop_tr = loop_model(self.rt), loop_model(self.tr)
+        if self.ledger:
+            self._loop_ledger = _describe_ledger(self._ledger)
         if self.ruc_hour is not None:
             from .hip_solver import DspLoopProjectState
             self._loop_pj = loop_model(self.pj)
@@ -762,6 +980,8 @@ class BatchedDoubleLoop(_DeviceLoop):
         for name in ("start", "hour", "da_series", "rt_series", "cf_series", "state", "da_offer", "da_prices", "bad", "uncertified"):
             setattr(mk, name, getattr(self._loop_state, name))
         mk.p_min_cents = self.p_min_cents
+        if self.p_min_cents_plant is not None:
+            mk.p_min_cents_plant = self.p_min_cents_plant.data_ptr()
         self._mk_state = mk
         self._mk_da, self._mk_rt = (_describe(DspLoopMarketModel, m, len(self.scale)) for m in (self.da, self.rt))
         if self.monotone:
@@ -789,6 +1009,8 @@ class BatchedDoubleLoop(_DeviceLoop):
     # -- the kernels (C ABI, on the current stream: _call) ------------------------------------------------------------------------------
     def _fused(self, phase, k):
         import ctypes as C
+        if phase == 2 and self.ledger:                 # the implemented hour is booked before the hand-off advances the clock
+            self._call(self._lib.dsp_loop_ledger, C.byref(self._loop_state), C.byref(self._loop_tr), C.byref(self._loop_ledger))
         self._call(self._lib.dsp_loop_update, C.byref(self._loop_state), C.byref(self._loop_rt), C.byref(self._loop_tr), phase, k)
 
     def _param(self, phase, k):
@@ -815,7 +1037,7 @@ class BatchedDoubleLoop(_DeviceLoop):
     # -- pieces of a step (all capturable: persistent tensors, the clock read on the device; windows, curves, clearing: _DeviceLoop) ------
     def _set_prices(self, m, da, rt):
         """c = base - RT . dP_T/dx - (DA - RT) on day_ahead_power ; c0 = base - RT . PT_const (Bidder._pass_price_forecasts)"""
-        m.c.copy_(m.base_c - rt @ m.PT)
+        m.c.copy_((m.base_c if m.c_static is None else m.c_static) - rt @ m.PT)
         m.c[:, m.pda_cols] -= da - rt
         return -(rt @ m.PT_const)                                         # the prices' share of the objective constant [B]
 
@@ -885,6 +1107,8 @@ class BatchedDoubleLoop(_DeviceLoop):
         revenue += fma(delivered, rt, da_offer * (da - rt)); otherwise the matrix form, equal to the kernels' to a tolerance"""
         import torch
         tr = self.tr
+        if self.ledger:
+            self._ledger_book(x)
         day_ahead = self.da_offer[:, k] * (self.da_prices[:, k] - rt0)
         if exact:
             p = tr.PT_const[0].expand(self.B)
@@ -898,6 +1122,27 @@ class BatchedDoubleLoop(_DeviceLoop):
         self.revenue += exact_fma(torch, self.delivered, rt0, day_ahead) if exact else self.delivered * rt0 + day_ahead
         self.energy_mwh += self.delivered
         self.hour_t += 1
+
+    def _ledger_book(self, x):
+        """the ledger of the implemented hour on the tracker's solution x [B, n], BEFORE the hand-off (the clock is still the hour's), in
+        the arithmetic of dsp_loop_ledger so that the two agree bit for bit: v = constant; v = fma(coef_e, x[col_e], v) in the order of
+        e; v = fma(per_avail, avail0, v) where the form has a per_avail, avail0 = wind_kw[b] * cf[(start[b] + hour) % N] rounded on its
+        own; ledger_hour[f] = v; ledger_acc[f] += v"""
+        import torch
+        L, B = self._ledger, self.B
+        coef, const = L["coef"], L["const"]
+        avail0 = None
+        if any(L["per_avail"]):
+            kw = self.tr.kw()
+            avail0 = (kw if isinstance(kw, float) else kw[:, 0]) * self.cf_series[(self.start + self.hour_t) % self.N]
+        for f, cols in enumerate(L["cols"]):
+            v = (const[f] if const.dim() == 1 else const[:, f]).expand(B)
+            for e, col in enumerate(cols):
+                v = exact_fma(torch, (coef[f, e] if coef.dim() == 2 else coef[:, f, e]).expand(B), x[:, col], v)
+            if L["per_avail"][f] != 0.0:
+                v = exact_fma(torch, L["per_avail_t"][f].expand(B), avail0, v)
+            self.ledger_hour[f].copy_(v)
+            self.ledger_acc[f] += v
 
     # -- stochastic mode: backcast scenarios, bid curves from p_min, market clearing (semantics: rolling.py, generalised over the descriptor) --
     def _avail(self, m, offset=0):
@@ -1278,5 +1523,8 @@ class BatchedDoubleLoop(_DeviceLoop):
     def results(self):
         res = dict(obj=self.revenue, energy_mwh=self.energy_mwh, state=self.state)
         res.update((key, getattr(self, key)) for key in self._result_keys)
+        if self.ledger:
+            res.update((key, self.ledger_acc[f]) for f, key in enumerate(self.ledger_keys))
+            res["profit"] = self.revenue - res["tot_cost"]
         return res, not bool(self.bad.item())
 

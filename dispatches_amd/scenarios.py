@@ -127,8 +127,8 @@ def nuclear_prices(B, T, seed=2020):
     return da, rt
 
 
-def nuclear_batch(B, T, solver, seed=2020):
-    """LP #3 (nuclear + PEM + tank), BASELINE config 2."""
+def nuclear_batch(B, T, solver, seed=2020, **sizes):
+    """LP #3 (nuclear + PEM + tank), BASELINE config 2.  sizes: pem_mw, tank_kg, h2_price, h2_demand of MultiPeriodNuclear (default: the flowsheet's)."""
     da, rt = nuclear_prices(B, T, seed)
 
     class _Fixed(AbstractPrescientPriceForecaster):
@@ -146,7 +146,7 @@ def nuclear_batch(B, T, solver, seed=2020):
         ramp_up_60min=100, ramp_down_60min=100, shutdown_capacity=500, startup_capacity=500, initial_status=-1,
         initial_p_output=0, production_cost_bid_pairs=[(400, 15), (450, 17.5), (500, 20)],
         startup_cost_pairs=[(48, 7355.42)], fixed_commitment=1)
-    bidder = Bidder(MultiPeriodNuclear(md), day_ahead_horizon=T, real_time_horizon=min(12, T), n_scenario=B,
+    bidder = Bidder(MultiPeriodNuclear(md, **sizes), day_ahead_horizon=T, real_time_horizon=min(12, T), n_scenario=B,
                     solver=solver, forecaster=_Fixed())
     return bidder, bidder.day_ahead_model
 

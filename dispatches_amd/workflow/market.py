@@ -25,7 +25,7 @@ def clear_price_taker(U, M, lmp):
 def plant_curves(torch, power, price, ok, p_min_cents=0):
     """power, price: [S, L] float64 - the S scenarios' pairs of L independent (plant, period) lanes; ok [S, L] bool (False: the row's
     solve was not optimal, it offers nothing); p_min_cents: the generator's minimum power in integer cents (0 for the wind + battery
-    plant, 40000 for the 400 MW nuclear unit).  The arithmetic of `bid_curves.sorted_pairs` + `bid_curves.curves`, per lane: integer
+    plant, 40000 for the 400 MW nuclear unit), an int or - plants of different minimum - an int64 tensor [L], one per lane.  The arithmetic of `bid_curves.sorted_pairs` + `bid_curves.curves`, per lane: integer
     cents, pairs with power below p_min dropped, sorted by power ascending / price descending, the highest price per distinct power, the
     point (p_min, lowest price seen or 0) in front if no pair sits at p_min, running maximum over the prices.
     -> (U [S + 1, L], M [S + 1, L] int64 cents, unused slots 0; count [L])."""
@@ -49,7 +49,7 @@ def plant_curves(torch, power, price, ok, p_min_cents=0):
     U.scatter_(0, dest, ps)
     M.scatter_(0, dest, cs)
     U, M = U[:S + 1], M[:S + 1]
-    U[0] = torch.where(ins, torch.full_like(U[0], p_min_cents), U[0])
+    U[0] = torch.where(ins, p_min_cents if torch.is_tensor(p_min_cents) else torch.full_like(U[0], p_min_cents), U[0])
     M[0] = torch.where(ins, lowest, M[0])
     count = n + ins.to(torch.int64)
     valid = torch.arange(S + 1, device=power.device)[:, None] < count[None, :]

@@ -30,6 +30,9 @@
  * ABI 19 adds the Bidder's monotone bid curves across price scenarios: dsp_loop_monotone_prepare writes ONE coupled day-ahead LP per plant
  * (the same S blocks, and the bounds of the S (S - 1) / 2 * T ordered-pair rows from the order of the day-ahead scenario prices) and
  * dsp_loop_market_clear reads scenario i of plant b from block i of row b (dsp_loop_market_state::coupled, was reserved).
+ * ABI 20 adds the per-plant ledger of the implemented hour: dsp_loop_ledger evaluates up to 8 linear forms (total cost, missed delivery,
+ * curtailment, hydrogen, ...) on the tracker's solution and adds them to per-plant accumulators, before phase 2 of dsp_loop_update
+ * advances the clock; and dsp_loop_market_state::p_min_cents_plant, a per-plant minimum power of the bid curves (appended; NULL = ABI 19).
  */
 #ifndef DSP_HIP_H
 #define DSP_HIP_H
@@ -42,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 19
+#define DSP_VERSION 20
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -423,6 +426,39 @@ typedef struct dsp_loop_state {
  * Per-plant pointers (ABI 16): refusals as stated at dsp_loop_market_clear. */
 int dsp_loop_update(const dsp_loop_state *st, const dsp_loop_model *rt, const dsp_loop_model *tr, int32_t phase, int32_t k, void *hipStream);
 
+/* The ledger of the implemented hour (ABI 20; rolling_flowsheets.py::BatchedDoubleLoop(ledger=True)): n_forms linear forms over the
+ * tracker's solution x of plant b, each added to an accumulator of its own.  Called AFTER the tracking solve and BEFORE phase 2 of
+ * dsp_loop_update (which advances *st->hour and overwrites the state).  Form f of plant b, with E = n_terms[f] and
+ * coef_f = coef + b * coef_stride + f * DSP_LEDGER_MAX_TERMS, in this fixed order (every step rounded once):
+ *     v = constant[b * const_stride + f]
+ *     v = fma(coef_f[e], x[b][cols[f][e]], v)            for e = 0 .. E - 1
+ *     v = fma(per_avail[f], avail0, v)                   only if per_avail[f] != 0
+ *     hour_value[f * B + b] = v ;  acc[f * B + b] = acc[f * B + b] + v
+ * avail0 = kw * cf_series[(start[b] + *hour) % N] (the product rounded on its own) is the wind available to plant b in the implemented
+ * hour, kw = tr->wind_kw_plant[b] where that pointer is set, tr->wind_kw otherwise.  coef_stride / const_stride = 0: one set of
+ * coefficients / constants for all plants; otherwise the distance in doubles between two plants' sets (sized wind batches carry
+ * per-plant constants, a batch of different hydrogen prices per-plant coefficients).  One lane per (form, plant), plant fastest. */
+#define DSP_LEDGER_MAX_FORMS 8
+#define DSP_LEDGER_MAX_TERMS 8
+typedef struct dsp_loop_ledger_desc {
+  int32_t n_forms, reserved;           /* 1 .. DSP_LEDGER_MAX_FORMS; reserved = 0                                                  */
+  int32_t n_terms[8];                  /* 0 .. DSP_LEDGER_MAX_TERMS terms of form f                                                */
+  int32_t cols[8][8];                  /* column of term e of form f in [0, tr->n); entries past n_terms[f] are not read           */
+  double  per_avail[8];                /* factor of avail0 in form f (0: none; needs wind columns in `tr` and st->cf_series)       */
+  const double *coef;                  /* [n_forms][8] (coef_stride = 0) or plant b's set at coef + b * coef_stride                */
+  const double *constant;              /* [n_forms] (const_stride = 0) or plant b's at constant + b * const_stride                 */
+  int64_t coef_stride, const_stride;   /* 0, or >= n_forms * 8 / >= n_forms                                                        */
+  double *acc;                         /* [n_forms][B] running sums                                                                */
+  double *hour_value;                  /* [n_forms][B] the values of the last booked hour                                          */
+} dsp_loop_ledger_desc;
+
+/* DSP_ERR_INVALID, nothing launched and nothing written, for: a NULL st / tr / ledger; B < 0; tr->n < 1 or a NULL tr->x; n_forms outside
+ * 1 .. DSP_LEDGER_MAX_FORMS or n_terms[f] outside 0 .. DSP_LEDGER_MAX_TERMS; reserved != 0; a column outside [0, tr->n); a NULL acc,
+ * hour_value, coef or constant; a stride that is negative or shorter than one plant's set; per_avail[f] != 0 (or not finite) without wind
+ * columns in `tr` (tr->wind_cols[0] < 0), without st->cf_series / st->start / st->hour, or with N < 1.  B = 0 is DSP_OK and no launch.
+ * Capturable: one kernel launch on hipStream, no allocation, no synchronisation. */
+int dsp_loop_ledger(const dsp_loop_state *st, const dsp_loop_model *tr, const dsp_loop_ledger_desc *ledger, void *hipStream);
+
 /* The scenario half of the Bidder's bid assembly ON THE DEVICE (reference: idaes Bidder._assemble_bids as DISPATCHES drives it -
  * dispatches/workflow/coordinator.py hands its bids to Prescient; golden values
  * dispatches/case_studies/renewables_case/tests/test_multiperiod_wind_battery_doubleloop.py:245-250): per hour t the pairs
@@ -570,6 +606,11 @@ typedef struct dsp_loop_market_state {
                                           of plant b are the S blocks of ONE coupled row (dsp_loop_monotone_prepare): x of scenario i
                                           at m->x + b * row_stride + i * n, status / flags one entry per plant at [b], a flagged
                                           plant counted once in `uncertified`.  Needs row_stride >= S * n and self_schedule = 0      */
+  const int64_t *p_min_cents_plant;    /* (ABI 20) [B] DEVICE array or NULL: plant b's minimum power in integer cents where
+                                          dsp_loop_market_clear reads p_min_cents (a nuclear plant's 500 MW - its PEM size).  NULL = the
+                                          scalar, ABI 19 bit for bit.  Every entry is bounded like the scalar, 0 .. 2e9: the host
+                                          reads the array back and refuses (DSP_ERR_INVALID, nothing written) an entry outside -
+                                          unless hipStream is being captured, when it cannot read: capture after an eager call     */
 } dsp_loop_market_state;
 
 /* Scenario fan-out of bidding model `m` (B * S rows), one lane per row.  k = -1: the day-ahead LP (day_ahead_power free in every period);
