@@ -369,9 +369,10 @@ static int solve_streaming(dsp_handle *h, const dsp_batch *batch, const SolveArg
   stats->streaming = 1; stats->quadratic = a.qp;
   stats->grid_blocks = (std::max(h->n, h->m) + 255) / 256; stats->block_threads = 256;
   stats->stream_bytes_per_iteration = (int64_t)stream_bytes_per_iteration(&h->stream);
-  stats->stream_form = h->stream.last_form;
-  stats->stream_phases = (h->stream.last_form == DSP_STREAM_FORM_LANE || h->stream.last_form == DSP_STREAM_FORM_IPM) ? h->stream.last_phases : 0;
-  stats->ipm_solved = h->stream.last_ipm_solved;
+  const StreamReport &rep = h->stream.report;      // (phases: counted by the lane form and the interior-point form only)
+  stats->stream_form = rep.form;
+  stats->stream_phases = rep.phases;
+  stats->ipm_solved = rep.ipm_solved;
   return finish_stats(h, batch, stats, timed, st);
 }
 

@@ -23,6 +23,10 @@
 // "scenarios finished" counter every few check periods.  Reductions are two-stage and ordered (block partials in a
 // fixed layout, summed by one block per scenario), so a solve is bit-reproducible.
 //
+// Host side (end of the file): stream_solve is a sequence of steps, each of which takes the batch or leaves it to the next -
+// stream_begin, try_interior_point (dsp_ipm.hip), try_block, lane_run (dsp_stream_lane.hip), run_tile / run_two_launch - and one
+// k_finalize.  The last two share enqueue_check and the period loop run_periods; what a solve reports is one StreamReport.
+//
 // Matrix layout: ELL, entry-major ([W][nvec]: thread v reads entry e at e * nvec + v, coalesced) for A (rows) and A^T
 // (columns); the matrix is read once per thread and reused across the SG scenarios a thread processes.  Vectors longer
 // than the ELL width (design columns that touch every period) are "long": CSR segments reduced by one block each.
@@ -1494,17 +1498,6 @@ __global__ void k_finalize(StreamArgs a) {
   }
 }
 
-template <class T>
-hipError_t up(std::vector<void *> &allocs, const std::vector<T> &v, const T **out) {
-  void *d = nullptr;
-  hipError_t e = hipMalloc(&d, std::max<size_t>(v.size(), 1) * sizeof(T));
-  if (e != hipSuccess) return e;
-  allocs.push_back(d);
-  if (!v.empty()) { e = hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice); if (e != hipSuccess) return e; }
-  *out = reinterpret_cast<const T *>(d);
-  return hipSuccess;
-}
-
 // entry-major ELL + long list of a host CSR (vectors = rows of M): built on the host (dsp_prepare.hpp), uploaded here
 hipError_t build_matrix(const HostCSR &M, std::vector<void *> &allocs, StreamMatrix *out, HostStreamELL *host, int span_limit = 0) {
   *host = build_stream_ell(M, kStreamMaxW, kLongChunk, span_limit);
@@ -1512,17 +1505,12 @@ hipError_t build_matrix(const HostCSR &M, std::vector<void *> &allocs, StreamMat
   if ((int)E.long_id.size() > kStreamMaxLong) return hipErrorInvalidValue;
   out->nvec = E.nvec; out->W = E.W; out->nlong = (int)E.long_id.size(); out->nchunk = (int)E.chunk_begin.size();
   hipError_t e;
-  if ((e = up(allocs, E.val, &out->val)) != hipSuccess) return e;
-  if ((e = up(allocs, E.idx, &out->idx)) != hipSuccess) return e;
-  if ((e = up(allocs, E.is_long, &out->is_long)) != hipSuccess) return e;
-  if ((e = up(allocs, E.long_id, &out->long_id)) != hipSuccess) return e;
-  if ((e = up(allocs, E.long_ptr, &out->long_ptr)) != hipSuccess) return e;
-  if ((e = up(allocs, E.long_idx, &out->long_idx)) != hipSuccess) return e;
-  if ((e = up(allocs, E.long_val, &out->long_val)) != hipSuccess) return e;
-  if ((e = up(allocs, E.chunk_begin, &out->chunk_begin)) != hipSuccess) return e;
-  if ((e = up(allocs, E.chunk_end, &out->chunk_end)) != hipSuccess) return e;
-  if ((e = up(allocs, E.long_chunk_ptr, &out->long_chunk_ptr)) != hipSuccess) return e;
-  return hipSuccess;
+  if ((e = stream_up(allocs, E.val, &out->val)) != hipSuccess || (e = stream_up(allocs, E.idx, &out->idx)) != hipSuccess ||
+      (e = stream_up(allocs, E.is_long, &out->is_long)) != hipSuccess || (e = stream_up(allocs, E.long_id, &out->long_id)) != hipSuccess ||
+      (e = stream_up(allocs, E.long_ptr, &out->long_ptr)) != hipSuccess || (e = stream_up(allocs, E.long_idx, &out->long_idx)) != hipSuccess ||
+      (e = stream_up(allocs, E.long_val, &out->long_val)) != hipSuccess || (e = stream_up(allocs, E.chunk_begin, &out->chunk_begin)) != hipSuccess ||
+      (e = stream_up(allocs, E.chunk_end, &out->chunk_end)) != hipSuccess) return e;
+  return stream_up(allocs, E.long_chunk_ptr, &out->long_chunk_ptr);
 }
 
 }  // namespace
@@ -1545,8 +1533,8 @@ hipError_t stream_create(const HostCSR &A_scaled, const HostCSR &AT_scaled, cons
   if (!no_fused) {
     const HostFusedPlan H = build_fused_plan(A_scaled, AT_scaled, Er, Ec, kFusedMaxLong, rb_env > 0 ? rb_env : 250, 40 * 1024);     // one row + one column per thread (K = 1): measured best, profiles/r30j_fused_scan.log
     if (H.ntile > 0) {
-      if ((e = up(S->allocs, H.tile, &S->P.F.tile)) != hipSuccess) return e;
-      if ((e = up(S->allocs, H.ridx_enc, &S->P.F.ridx_enc)) != hipSuccess) return e;
+      if ((e = stream_up(S->allocs, H.tile, &S->P.F.tile)) != hipSuccess) return e;
+      if ((e = stream_up(S->allocs, H.ridx_enc, &S->P.F.ridx_enc)) != hipSuccess) return e;
       S->P.F.ntile = H.ntile; S->P.F.rows_per_tile = H.rows_per_tile; S->P.F.ny_max = H.ny_max; S->P.F.nxb_max = H.nxb_max;
       S->P.F.own_max = H.own_max; S->P.F.halo_max = H.halo_max;
     }
@@ -1602,190 +1590,189 @@ static hipError_t ensure_workspace(StreamSolver *S, int B) {
   return hipSuccess;
 }
 
-size_t stream_bytes_per_iteration(const StreamSolver *S) {
-  // per scenario and plain iteration of the form the last solve ran: two launches 8 n + 6 m doubles (see the file header); fused
-  // banded form 4 n + 3 m with shared bounds, 6 n + 5 m with per-scenario bounds (k_fused); before any solve: the two-launch figure
-  return S->last_bytes_per_iteration ? S->last_bytes_per_iteration : (size_t)8 * (8 * (size_t)S->P.n + 6 * (size_t)S->P.m);
+// Launch grids of the check sequence, the two-launch iteration and the certificate sequence, SG scenarios per thread
+struct StreamGrids {
+  dim3 cols, dual, rows, elem;          // columns + chunks of the long ones (k_primal, k_kkt_cols, k_ray_cols); rows + chunks; rows + long rows; max(n, m)
+  int fin_c, fin_r;                     // blocks of 64 threads over (long columns, scenarios) / (long rows, scenarios): the *_long_finish launches
+};
+static StreamGrids stream_grids(const StreamArgs &a, int SG) {
+  const StreamProblem &P = a.P;
+  const int B = a.b.B, groups = (B + SG - 1) / SG;
+  return {dim3(a.nblk_n + P.C.nchunk, groups), dim3(a.nblk + P.R.nchunk, groups), dim3(a.nblk + P.R.nlong, groups), dim3(a.nblk, groups),
+          (P.C.nlong * B + 63) / 64, (P.R.nlong * B + 63) / 64};
 }
 
 // The certificate sequence for the scenarios control_decide marked suspect, on the scenario-major workspace: a.W.x / a.W.y must be
 // the current iterate (every form's check sequence leaves it there; the lane form brings it back first).  xp / yp are overwritten
 // with T(z) of that iterate - what the next check would write anyway -, xbar and ray are scratch; certified scenarios get
 // status 2 / 3, done = 1 and count as finished.  The partial-sum buffer is left zeroed as after k_init.
-hipError_t stream_certify(StreamSolver *S, StreamArgs &a, hipStream_t st) {
+hipError_t stream_certify(StreamSolver *, StreamArgs &a, hipStream_t st) {
   const StreamProblem &P = a.P;
   const int B = a.b.B;
   const dim3 blk(kTB);
-  const dim3 g_primal(a.nblk_n + P.C.nchunk, B), g_rows(a.nblk + P.R.nlong, B), g_cols(a.nblk_n + P.C.nchunk, B), g_elem(a.nblk, B);
-  const int fin_c = (P.C.nlong * B + 63) / 64;
+  const StreamGrids g = stream_grids(a, 1);
   const size_t pbytes = (size_t)B * a.nblk_tot * kNQ * sizeof(double);
   hipError_t e;
-  hipLaunchKernelGGL((k_primal<1, true>), g_primal, blk, 0, st, a);
-  if (P.C.nlong) hipLaunchKernelGGL(k_primal_long_finish, dim3(fin_c), dim3(64), 0, st, a, 1);
-  hipLaunchKernelGGL((k_check_rows<1>), g_rows, blk, 0, st, a);
+  hipLaunchKernelGGL((k_primal<1, true>), g.cols, blk, 0, st, a);
+  if (P.C.nlong) hipLaunchKernelGGL(k_primal_long_finish, dim3(g.fin_c), dim3(64), 0, st, a, 1);
+  hipLaunchKernelGGL((k_check_rows<1>), g.rows, blk, 0, st, a);
   if ((e = hipMemsetAsync(a.W.partial, 0, pbytes, st)) != hipSuccess) return e;
-  hipLaunchKernelGGL((k_ray_prep<1>), g_elem, blk, 0, st, a);
-  hipLaunchKernelGGL((k_ray_rows<1>), g_rows, blk, 0, st, a);
-  hipLaunchKernelGGL((k_ray_cols<1>), g_cols, blk, 0, st, a);
-  if (P.C.nlong) hipLaunchKernelGGL(k_ray_long_finish, dim3(fin_c), dim3(64), 0, st, a);
+  hipLaunchKernelGGL((k_ray_prep<1>), g.elem, blk, 0, st, a);
+  hipLaunchKernelGGL((k_ray_rows<1>), g.rows, blk, 0, st, a);
+  hipLaunchKernelGGL((k_ray_cols<1>), g.cols, blk, 0, st, a);
+  if (P.C.nlong) hipLaunchKernelGGL(k_ray_long_finish, dim3(g.fin_c), dim3(64), 0, st, a);
   hipLaunchKernelGGL(k_ray_decide, dim3(B), dim3(256), 0, st, a);
   if ((e = hipMemsetAsync(a.W.partial, 0, pbytes, st)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(a.W.ndone + 1, 0, sizeof(int), st)) != hipSuccess) return e;
-  (void)S;
   return hipGetLastError();
 }
 
+// The check sequence of the host-enqueued forms on the scenario-major workspace: a.W.x / a.W.y are the current iterate, whichever
+// buffers those are; x+ / y+, the check sums, the decision of every scenario and its Halpern step or restart, all on the device.
 template <int SG>
-static hipError_t run(StreamSolver *S, StreamArgs &a, hipStream_t st, int *periods_run) {
-  const StreamProblem &P = a.P;
-  const int B = a.b.B;
-  const int groups = (B + SG - 1) / SG;
+static void enqueue_check(const StreamArgs &a, const StreamGrids &g, hipStream_t st, int C) {
   const dim3 blk(kTB);
-  const dim3 g_primal(a.nblk_n + P.C.nchunk, groups), g_dual(a.nblk + P.R.nchunk, groups);
-  const dim3 g_rows_chk(a.nblk + P.R.nlong, groups), g_cols(a.nblk_n + P.C.nchunk, groups);
-  const dim3 g_elem(a.nblk, groups);
-  const int fin_c = (P.C.nlong * B + 63) / 64, fin_r = (P.R.nlong * B + 63) / 64;
-  auto primal = [&](bool write_xp) {
-    if (write_xp) hipLaunchKernelGGL((k_primal<SG, true>), g_primal, blk, 0, st, a);
-    else hipLaunchKernelGGL((k_primal<SG, false>), g_primal, blk, 0, st, a);
-    if (P.C.nlong) hipLaunchKernelGGL(k_primal_long_finish, dim3(fin_c), dim3(64), 0, st, a, write_xp ? 1 : 0);
-  };
-  const int C = a.opt.check_every > 0 ? a.opt.check_every : 64;       // 0 = automatic (include/dsp_hip.h)
-  const int max_periods = (a.opt.max_iter + C - 1) / C;
-  const int poll = 4;                                        // check periods between two looks at the finished counter
+  hipLaunchKernelGGL((k_primal<SG, true>), g.cols, blk, 0, st, a);
+  if (a.P.C.nlong) hipLaunchKernelGGL(k_primal_long_finish, dim3(g.fin_c), dim3(64), 0, st, a, 1);
+  hipLaunchKernelGGL((k_check_rows<SG>), g.rows, blk, 0, st, a);
+  hipLaunchKernelGGL((k_kkt_cols<SG>), g.cols, blk, 0, st, a);
+  if (a.P.C.nlong) hipLaunchKernelGGL(k_kkt_long_finish, dim3(g.fin_c), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_control, dim3(a.b.B), dim3(256), 0, st, a, C);
+  hipLaunchKernelGGL((k_apply<SG>), g.elem, blk, 0, st, a);
+}
+
+// The period loop of the two-launch and the tile form: C - 1 plain iterations (`plain(u)` enqueues one), the check (`check(C)`: the
+// check sequence and whatever the form appends), a look at the finished counter when one is due, and the certificate sequence for
+// suspects on `current()`, the arguments whose x / y are the current iterate.  The callables are the forms' lambdas, inlined here:
+// these forms are bound by how fast the host enqueues.
+template <class Plain, class Check, class Current>
+static hipError_t run_periods(StreamSolver *S, const StreamArgs &a, hipStream_t st, int *periods_run, Plain plain, Check check, Current current) {
+  const int C = check_period(a.opt), max_periods = max_check_periods(a.opt);
   int period = 0;
-  hipError_t e = hipSuccess;
-  for (; period < max_periods; ++period) {
-    for (int u = 0; u < C - 1; ++u) {
-      primal(false);
-      hipLaunchKernelGGL((k_dual_halpern<SG>), g_dual, blk, 0, st, a, u);
-      if (P.R.nlong) hipLaunchKernelGGL(k_dual_long_finish, dim3(fin_r), dim3(64), 0, st, a, u);
-    }
-    primal(true);
-    hipLaunchKernelGGL((k_check_rows<SG>), g_rows_chk, blk, 0, st, a);
-    hipLaunchKernelGGL((k_kkt_cols<SG>), g_cols, blk, 0, st, a);
-    if (P.C.nlong) hipLaunchKernelGGL(k_kkt_long_finish, dim3((P.C.nlong * B + 63) / 64), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_control, dim3(B), dim3(256), 0, st, a, C);
-    hipLaunchKernelGGL((k_apply<SG>), g_elem, blk, 0, st, a);
-    if ((period + 1) % poll == 0 || period + 1 == max_periods) {
-      if ((e = hipMemcpyAsync(S->ndone_host, a.W.ndone, 2 * sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-      if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-      if (S->ndone_host[0] >= B) { ++period; break; }
-      // suspects (relative gap >= 1/2 after 2048 iterations): the certificate sequence, at most every 16 check periods
-      if (S->ndone_host[1] && (period + 1) % 16 == 0) {
-        if ((e = stream_certify(S, a, st)) != hipSuccess) return e;
-      }
+  hipError_t e;
+  while (period < max_periods) {
+    for (int u = 0; u < C - 1; ++u) if ((e = plain(u)) != hipSuccess) return e;
+    check(C);
+    ++period;
+    if (!poll_due(period, max_periods)) continue;
+    if ((e = stream_poll(S, a, st)) != hipSuccess) return e;
+    if (S->ndone_host[0] >= a.b.B) break;
+    if (certify_due(S->ndone_host, period)) {
+      StreamArgs ac = current();
+      if ((e = stream_certify(S, ac, st)) != hipSuccess) return e;
     }
   }
   *periods_run = period;
   return hipGetLastError();
 }
 
-// BLOCKING and one call at a time per handle (include/dsp_hip.h, dsp_solve): the per-scenario state lives in ONE workspace per
-// handle (reallocated when a larger batch arrives) and the host polls the device's finished-counter while it enqueues the
-// iteration launches, so - unlike the fused path with its ring of work queues - two solves of one handle cannot overlap.  The
-// mutex serialises callers on different threads / streams; the call returns after its stream work has completed.
-static hipError_t stream_solve_locked(StreamSolver *S, const dsp_batch &batch, const dsp_options &opt, double eta, hipStream_t st,
-                                      int *periods_run);
-
-// The fused form of `run`: C - 1 plain iterations = C - 1 launches of k_fused (x / y ping-pong), then the SAME check sequence
-// as the two-launch form on whichever buffers are current, then the long columns' partial sums of the y the check left.
 template <int SG>
-static hipError_t run_fused(StreamSolver *S, StreamArgs &a, hipStream_t st, int *periods_run, bool shared, bool qp) {
-  const StreamProblem &P = a.P;
-  const FusedPlan &F = P.F;
-  const int B = a.b.B;
-  const int groups = (B + SG - 1) / SG;
+static hipError_t run_two_launch(StreamSolver *S, StreamArgs &a, hipStream_t st, int *periods_run) {
   const dim3 blk(kTB);
-  const dim3 g_fused(groups, F.ntile), g_primal(a.nblk_n + P.C.nchunk, groups);
-  const dim3 g_rows_chk(a.nblk + P.R.nlong, groups), g_cols(a.nblk_n + P.C.nchunk, groups), g_elem(a.nblk, groups);
-  const int fin_c = (P.C.nlong * B + 63) / 64;
-  const int K_own = (F.own_max + kTB - 1) / kTB;
-  // (+ the thread-private slots of k_fused_pre's deferred form: y0, x0, and the row bounds when they differ per scenario)
-  const size_t lds = ((size_t)SG * (F.ny_max + F.nxb_max) + (1 + kTB / 64) * kFusedMaxLong * SG + (size_t)K_own * SG * (shared ? 2 : 4) * kTB) * sizeof(double);
-  // k_fused_pre (every HBM load of the workgroup ahead of the first barrier, matrix entries requested after the barriers) where a
-  // thread owns ONE row and ONE column of the tile (250-row tiles: always) and the halo columns fit one pass; k_fused (staged
-  // phases) otherwise.  DSP_FUSED_V=1 forces the staged form (development).  Since round 4 this form serves batches below 32
-  // scenarios only (larger ones run the lane form, dsp_stream_lane.hip): the instantiations of round 3 for 2 - 3 rows per thread,
-  // 4 scenarios per workgroup and loads-up-front are gone (144 -> 16 + 8).
-  const void *fn = nullptr;
+  const StreamGrids g = stream_grids(a, SG);
+  auto plain = [&](int u) {
+    hipLaunchKernelGGL((k_primal<SG, false>), g.cols, blk, 0, st, a);
+    if (a.P.C.nlong) hipLaunchKernelGGL(k_primal_long_finish, dim3(g.fin_c), dim3(64), 0, st, a, 0);
+    hipLaunchKernelGGL((k_dual_halpern<SG>), g.dual, blk, 0, st, a, u);
+    if (a.P.R.nlong) hipLaunchKernelGGL(k_dual_long_finish, dim3(g.fin_r), dim3(64), 0, st, a, u);
+    return hipSuccess;
+  };
+  return run_periods(S, a, st, periods_run, plain, [&](int C) { enqueue_check<SG>(a, g, st, C); }, [&]() { return a; });
+}
+
+// Tile form: dynamic LDS of a workgroup of `sg` scenarios (staged y + xbar per scenario, the long columns' sums per wave, the thread-private
+// slots of k_fused_pre's deferred form: y0, x0, and the row bounds when they differ per scenario).  What picks `sg` (tile_sg) is what is launched.
+static size_t fused_lds_bytes(const FusedPlan &F, int sg, bool shared) {
+  const size_t k_own = (size_t)(F.own_max + kTB - 1) / kTB;
+  return ((size_t)sg * (F.ny_max + F.nxb_max) + (size_t)(1 + kTB / 64) * kFusedMaxLong * sg + k_own * sg * (shared ? 2 : 4) * kTB) * sizeof(double);
+}
+
+// k_fused_pre (every HBM load of the workgroup ahead of the first barrier, matrix entries requested after the barriers) where a
+// thread owns ONE row and ONE column of the tile (250-row tiles: always) and the halo columns fit one pass; k_fused (staged
+// phases) otherwise.  DSP_FUSED_V=1 forces the staged form (development).  Since round 4 this form serves batches below 32
+// scenarios only (larger ones run the lane form, dsp_stream_lane.hip): the instantiations of round 3 for 2 - 3 rows per thread,
+// 4 scenarios per workgroup and loads-up-front are gone (144 -> 16 + 8).
+template <int SG>
+static const void *fused_kernel(const StreamProblem &P, int B, bool shared, bool qp, bool *is_pre) {
   const int v_env = getenv("DSP_FUSED_V") ? atoi(getenv("DSP_FUSED_V")) : 0;      // (read per solve: tests switch forms)
-  const int K = (F.own_max + kTB - 1) / kTB;
+  const int K = (P.F.own_max + kTB - 1) / kTB;
   const int mw = std::max(P.C.W, P.R.W);
   // the deferred form addresses with 32-bit byte offsets: every array it touches must stay below 4 GiB
   const bool narrow_ok = (uint64_t)std::max(B, mw) * (uint64_t)std::max(P.n, P.m) * 8ull < (1ull << 32);
-  const bool pre = v_env != 1 && K == 1 && mw <= 8 && F.halo_max <= kTB && narrow_ok;
+  const bool pre = v_env != 1 && K == 1 && mw <= 8 && P.F.halo_max <= kTB && narrow_ok;
+  *is_pre = pre;
 #define DSP_PICK(MM)                                                                                                                 \
   (shared ? (qp ? reinterpret_cast<const void *>(&k_fused_pre<SG, 1, MM, true, true, 1>) : reinterpret_cast<const void *>(&k_fused_pre<SG, 1, MM, true, false, 1>)) \
           : (qp ? reinterpret_cast<const void *>(&k_fused_pre<SG, 1, MM, false, true, 1>) : reinterpret_cast<const void *>(&k_fused_pre<SG, 1, MM, false, false, 1>)))
-  if (pre) fn = mw <= 4 ? DSP_PICK(4) : DSP_PICK(8);
-  else fn = shared ? (qp ? reinterpret_cast<const void *>(&k_fused<SG, true, true>) : reinterpret_cast<const void *>(&k_fused<SG, true, false>))
-                   : (qp ? reinterpret_cast<const void *>(&k_fused<SG, false, true>) : reinterpret_cast<const void *>(&k_fused<SG, false, false>));
+  if (pre) return mw <= 4 ? DSP_PICK(4) : DSP_PICK(8);
 #undef DSP_PICK
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
+  return shared ? (qp ? reinterpret_cast<const void *>(&k_fused<SG, true, true>) : reinterpret_cast<const void *>(&k_fused<SG, true, false>))
+                : (qp ? reinterpret_cast<const void *>(&k_fused<SG, false, true>) : reinterpret_cast<const void *>(&k_fused<SG, false, false>));
+}
+
+// C - 1 plain iterations = C - 1 launches of k_fused (x / y ping-pong), then the SAME check sequence as the two-launch form on
+// whichever buffers are current, then the long columns' partial sums of the y the check left.
+template <int SG>
+static hipError_t run_tile(StreamSolver *S, StreamArgs &a, hipStream_t st, int *periods_run, bool shared, bool qp) {
+  const StreamProblem &P = a.P;
+  const FusedPlan &F = P.F;
+  const int B = a.b.B, groups = (B + SG - 1) / SG;
+  const dim3 blk(kTB), g_fused(groups, F.ntile);
+  const StreamGrids g = stream_grids(a, SG);
+  const size_t lds = fused_lds_bytes(F, SG, shared);
+  bool pre = false;
+  const void *fn = fused_kernel<SG>(P, B, shared, qp, &pre);
+  const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (ea != hipSuccess) return ea;
   const int xcd_env = getenv("DSP_FUSED_XCD") ? atoi(getenv("DSP_FUSED_XCD")) : 1;   // default on (DSP_FUSED_XCD=0: grid order)
   const int xcd_full = (pre && xcd_env) ? fused_xcd_full(groups, F.ntile) : 0;
-  double *xcur = a.W.x, *ycur = a.W.y, *xalt = a.W.x2, *yalt = a.W.y2;
+  StreamArgs cur = a;                  // cur.W.x / cur.W.y: the current buffers (the check and the certificate sequence work in place on them)
+  double *xalt = a.W.x2, *yalt = a.W.y2;
   int lp_cur = 0;
   auto partials = [&]() {
-    if (P.C.nlong) hipLaunchKernelGGL(k_long_partials, dim3(F.ntile, B), blk, 0, st, a, (const double *)ycur, a.W.lpart[lp_cur]);
+    if (P.C.nlong) hipLaunchKernelGGL(k_long_partials, dim3(F.ntile, B), blk, 0, st, a, (const double *)cur.W.y, a.W.lpart[lp_cur]);
+  };
+  auto plain = [&](int u) {
+    FusedIO io{cur.W.x, cur.W.y, xalt, yalt, a.W.lpart[lp_cur], a.W.lpart[lp_cur ^ 1], xcd_full};
+    int kofs = u;
+    void *params[] = {&a, &io, &kofs};
+    const hipError_t e = hipLaunchKernel(fn, g_fused, blk, params, lds, st);
+    std::swap(cur.W.x, xalt); std::swap(cur.W.y, yalt); lp_cur ^= 1;
+    return e;
   };
   partials();
-  const int C = a.opt.check_every > 0 ? a.opt.check_every : 64;
-  const int max_periods = (a.opt.max_iter + C - 1) / C;
-  const int poll = 4;
-  int period = 0;
-  for (; period < max_periods; ++period) {
-    for (int u = 0; u < C - 1; ++u) {
-      FusedIO io{xcur, ycur, xalt, yalt, a.W.lpart[lp_cur], a.W.lpart[lp_cur ^ 1], xcd_full};
-      int kofs = u;
-      void *params[] = {&a, &io, &kofs};
-      if ((e = hipLaunchKernel(fn, g_fused, blk, params, lds, st)) != hipSuccess) return e;
-      std::swap(xcur, xalt); std::swap(ycur, yalt); lp_cur ^= 1;
-    }
-    // the check sequence works in place on the current buffers
-    StreamArgs ac = a;
-    ac.W.x = xcur; ac.W.y = ycur;
-    hipLaunchKernelGGL((k_primal<SG, true>), g_primal, blk, 0, st, ac);
-    if (P.C.nlong) hipLaunchKernelGGL(k_primal_long_finish, dim3(fin_c), dim3(64), 0, st, ac, 1);
-    hipLaunchKernelGGL((k_check_rows<SG>), g_rows_chk, blk, 0, st, ac);
-    hipLaunchKernelGGL((k_kkt_cols<SG>), g_cols, blk, 0, st, ac);
-    if (P.C.nlong) hipLaunchKernelGGL(k_kkt_long_finish, dim3(fin_c), dim3(64), 0, st, ac);
-    hipLaunchKernelGGL(k_control, dim3(B), dim3(256), 0, st, ac, C);
-    hipLaunchKernelGGL((k_apply<SG>), g_elem, blk, 0, st, ac);
-    partials();
-    if ((period + 1) % poll == 0 || period + 1 == max_periods) {
-      if ((e = hipMemcpyAsync(S->ndone_host, a.W.ndone, 2 * sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-      if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-      if (S->ndone_host[0] >= B) { ++period; break; }
-      if (S->ndone_host[1] && (period + 1) % 16 == 0) {          // certificate sequence on the buffers that are current
-        StreamArgs ar = a;
-        ar.W.x = xcur; ar.W.y = ycur;
-        if ((e = stream_certify(S, ar, st)) != hipSuccess) return e;
-      }
-    }
-  }
-  *periods_run = period;
-  return hipGetLastError();
+  return run_periods(S, a, st, periods_run, plain, [&](int C) { enqueue_check<SG>(cur, g, st, C); partials(); }, [&]() { return cur; });
 }
 
-hipError_t stream_solve(StreamSolver *S, const dsp_batch &batch, const dsp_options &opt, double eta, hipStream_t st,
-                        int *periods_run) {
-  std::lock_guard<std::mutex> lock(S->mu);
-  hipError_t e = stream_solve_locked(S, batch, opt, eta, st, periods_run);
-  // (the interior-point form solved part of the batch and a PDHG form the rest: reported as the former, dsp_stats::ipm_solved says how many)
-  if (e == hipSuccess && S->last_ipm_solved > 0) { S->last_form = DSP_STREAM_FORM_IPM; S->last_phases = ipm_partitions(S); }
-  const hipError_t es = hipStreamSynchronize(st);
-  return e != hipSuccess ? e : es;
+// scenarios per workgroup of the tile form (matrix entries are loaded once per workgroup): 2 measured best with 250-row tiles (81 vs
+// 89-91 us at 4, 102 at 1: profiles/r30j_fused_scan.log), 1 where that leaves the chip empty.  The workgroup's LDS must fit a CU's
+// 160 KB: plans with wide hulls (the host admits up to 40 KB per scenario) run with fewer scenarios per workgroup.
+static int tile_sg(const FusedPlan &F, int B, bool shared) {
+  int fsg = 2;
+  if ((long)F.ntile * ((B + 1) / 2) < 1024) fsg = 1;
+  static const int fsg_env = getenv("DSP_FUSED_SG") ? atoi(getenv("DSP_FUSED_SG")) : 0;      // development override
+  if (fsg_env == 1 || fsg_env == 2) fsg = fsg_env;
+  while (fsg > 1 && fused_lds_bytes(F, fsg, shared) > (size_t)160 * 1024) fsg /= 2;
+  return fsg;
 }
 
-static hipError_t stream_solve_locked(StreamSolver *S, const dsp_batch &batch, const dsp_options &opt, double eta, hipStream_t st,
-                                      int *periods_run) {
+// scenarios per thread of the two-launch form: enough (element blocks x scenario groups) to fill the chip, matrix reuse otherwise
+static int two_launch_sg(const StreamArgs &a) {
+  const long blocks1 = a.nblk;
+  int sg = 4;
+  if (blocks1 * ((a.b.B + 3) / 4) < 1024) sg = 2;
+  if (blocks1 * ((a.b.B + 1) / 2) < 1024) sg = 1;
+  static const int sg_env = getenv("DSP_STREAM_SG") ? atoi(getenv("DSP_STREAM_SG")) : 0;     // development override
+  if (sg_env == 1 || sg_env == 2 || sg_env == 4 || sg_env == 8) sg = sg_env;
+  return sg;
+}
+
+// ---- a solve, step by step: each step takes the batch (*took) or leaves it to the next --------------------------------------------
+// the arguments of every kernel of the solve, the workspace as k_init / k_init_control leave it
+static hipError_t stream_begin(StreamSolver *S, const dsp_batch &batch, const dsp_options &opt, double eta, hipStream_t st, StreamArgs &a) {
   const int B = batch.B;
   hipError_t e = ensure_workspace(S, B);
   if (e != hipSuccess) return e;
-  StreamArgs a{};
   a.P = S->P; a.W = S->W; a.b = batch; a.opt = opt; a.eta = eta;
   a.nblk_n = (S->P.n + kTB - 1) / kTB;
   a.nblk = (std::max(S->P.n, S->P.m) + kTB - 1) / kTB;
@@ -1796,109 +1783,84 @@ static hipError_t stream_solve_locked(StreamSolver *S, const dsp_batch &batch, c
   hipLaunchKernelGGL(k_init, dim3(a.nblk, B), dim3(kTB), 0, st, a);
   hipLaunchKernelGGL(k_init_control, dim3(B), dim3(64), 0, st, a);
   // k_init wrote its partials with stride nblk; the check kernels use nblk_tot: clear again before the first check
-  if ((e = hipMemsetAsync(a.W.partial, 0, (size_t)B * a.nblk_tot * kNQ * sizeof(double), st)) != hipSuccess) return e;
-  // time-banded LPs: interior point with exact banded solves first (dsp_ipm.hip); what it does not finish continues below as before
-  S->last_newton = 0;
-  S->last_ipm_solved = 0;
-  std::vector<int> left;                               // scenarios the interior-point form left (empty: it did not run, or solved nothing)
-  if (S->ipm && !opt.no_interior_point && !batch.row_compliance) {
-    bool all = false;
-    int n_solved = 0;
-    if ((e = ipm_run(S, a, st, &all, &S->last_newton, &n_solved)) != hipSuccess) return e;
-    S->last_ipm_solved = n_solved;
-    if (all) {
-      S->last_form = DSP_STREAM_FORM_IPM;
-      S->last_phases = ipm_partitions(S);
-      S->last_bytes_per_iteration = 0;
-      hipLaunchKernelGGL(k_finalize, dim3(a.nblk, B), dim3(kTB), 0, st, a);
-      *periods_run = -1;
-      return hipGetLastError();
-    }
-    if (n_solved > 0) {
-      // Per-scenario fallback: the scenarios it solved are done (ctrl.done, x+ / y+ exported); only the others go on - packed into as
-      // few lane groups as they need when the lane form applies (its phases' slot -> scenario map), skipped by every other form
-      // (their kernels leave scenarios with ctrl.done alone).  One infeasible member of 256 then costs one lane group of PDHG
-      // iterations until its certificate, not the whole batch over again.
-      std::vector<StreamCtrl> hc((size_t)B);
-      if ((e = hipMemcpyAsync(hc.data(), a.W.ctrl, (size_t)B * sizeof(StreamCtrl), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-      if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-      for (int s = 0; s < B; ++s) if (!hc[s].done) left.push_back(s);
-      if (left.empty()) {                              // (cannot happen: all == false; defensive)
-        hipLaunchKernelGGL(k_finalize, dim3(a.nblk, B), dim3(kTB), 0, st, a);
-        *periods_run = -1;
-        return hipGetLastError();
-      }
-    }
-  }
-  const bool after_ipm = !left.empty();
-  // mid-size LPs: the whole solve in ONE launch, one workgroup per scenario with its state in LDS
-  {
-    const size_t lds = ((size_t)7 * S->P.n + 7 * S->P.m + (1024 / 64) * kNQ + kNQ) * sizeof(double);
-    static const int no_block = getenv("DSP_STREAM_NO_BLOCK") ? atoi(getenv("DSP_STREAM_NO_BLOCK")) : 0;
-    const bool long_rows_ok = S->P.R.nlong == 0;      // long ROWS are not handled by the check of the block form
-    if (!no_block && long_rows_ok && lds <= S->lds_limit) {
-      const int nt = std::max(S->P.n, S->P.m) > 2048 ? 1024 : (std::max(S->P.n, S->P.m) > 512 ? 512 : 256);
-      hipError_t be = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_block_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (be != hipSuccess) return be;
-      S->last_form = DSP_STREAM_FORM_BLOCK;
-      hipLaunchKernelGGL(k_block_solve, dim3(B), dim3(nt), lds, st, a);
-      hipLaunchKernelGGL(k_finalize, dim3(a.nblk, B), dim3(kTB), 0, st, a);
-      *periods_run = -1;
-      return hipGetLastError();
-    }
-  }
-  // banded matrix with a handful of long columns: the lane-per-scenario form (dsp_stream_lane.hip)
-  {
-    bool used = false;
-    if ((e = lane_run(S, a, st, periods_run, &used, after_ipm ? &left : nullptr)) != hipSuccess) return e;
-    if (used) {
-      S->last_form = DSP_STREAM_FORM_LANE;
-      hipLaunchKernelGGL(k_finalize, dim3(a.nblk, B), dim3(kTB), 0, st, a);
-      return hipGetLastError();
-    }
-  }
-  // scenarios per thread: enough (element blocks x scenario groups) to fill the chip, matrix reuse otherwise
-  const long blocks1 = a.nblk;
-  int sg = 4;
-  if (blocks1 * ((B + 3) / 4) < 1024) sg = 2;
-  if (blocks1 * ((B + 1) / 2) < 1024) sg = 1;
-  a.nblk_tot = a.nblk + std::max(S->P.R.nlong, S->P.C.nlong);
-  static const int sg_env = getenv("DSP_STREAM_SG") ? atoi(getenv("DSP_STREAM_SG")) : 0;     // development override
-  if (sg_env == 1 || sg_env == 2 || sg_env == 4 || sg_env == 8) sg = sg_env;
-  S->last_bytes_per_iteration = (size_t)8 * (8 * (size_t)S->P.n + 6 * (size_t)S->P.m);
-  S->last_form = S->P.F.ntile > 0 ? DSP_STREAM_FORM_TILE : DSP_STREAM_FORM_TWO_LAUNCH;
-  if (S->P.F.ntile > 0) {
-    // banded matrix: one launch per plain iteration.  Bounds that are the same template for every scenario of the batch
-    // (stride 0: the price-taker families differ in the objective only) are read once per workgroup from scenario 0's copy.
-    const bool shared = (!batch.var_lb || batch.var_lb_stride == 0) && (!batch.var_ub || batch.var_ub_stride == 0) &&
-                        (!batch.row_lb || batch.row_lb_stride == 0) && (!batch.row_ub || batch.row_ub_stride == 0);
-    const bool qp = batch.row_compliance != nullptr;
-    int fsg = 2;                       // scenarios per workgroup (matrix entries are loaded once per workgroup): 2 measured best with
-    if ((long)S->P.F.ntile * ((B + 1) / 2) < 1024) fsg = 1;      // 250-row tiles (81 vs 89-91 us at 4, 102 at 1: profiles/r30j_fused_scan.log)
-    static const int fsg_env = getenv("DSP_FUSED_SG") ? atoi(getenv("DSP_FUSED_SG")) : 0;
-    if (fsg_env == 1 || fsg_env == 2) fsg = fsg_env;
-    // the workgroup's LDS (staged y + xbar per scenario, the deferred form's thread-private slots) must fit a CU's 160 KB: plans
-    // with wide hulls (the host admits up to 40 KB per scenario) run with fewer scenarios per workgroup
-    {
-      const FusedPlan &F = S->P.F;
-      const size_t k_own = (size_t)(F.own_max + kTB - 1) / kTB;
-      auto lds_need = [&](int g) {
-        return ((size_t)g * (F.ny_max + F.nxb_max) + (size_t)(1 + kTB / 64) * kFusedMaxLong * g + k_own * g * (shared ? 2 : 4) * kTB) * sizeof(double);
-      };
-      while (fsg > 1 && lds_need(fsg) > (size_t)160 * 1024) fsg /= 2;
-    }
-    S->last_bytes_per_iteration = (size_t)8 * (shared ? 4 * (size_t)S->P.n + 3 * (size_t)S->P.m : 6 * (size_t)S->P.n + 5 * (size_t)S->P.m)
-                                  + (qp ? 8 * (size_t)S->P.m : 0);
-    if (fsg == 2) e = run_fused<2>(S, a, st, periods_run, shared, qp);
-    else e = run_fused<1>(S, a, st, periods_run, shared, qp);
-  } else
-  if (sg == 8) e = run<8>(S, a, st, periods_run);
-  else if (sg == 4) e = run<4>(S, a, st, periods_run);
-  else if (sg == 2) e = run<2>(S, a, st, periods_run);
-  else e = run<1>(S, a, st, periods_run);
+  return hipMemsetAsync(a.W.partial, 0, (size_t)B * a.nblk_tot * kNQ * sizeof(double), st);
+}
+
+// time-banded LPs: interior point with exact banded solves first (dsp_ipm.hip).  `left`: the scenarios it did not finish, when it
+// finished some (empty otherwise: it did not run, or solved nothing, and the whole batch goes on as before).
+static hipError_t try_interior_point(StreamSolver *S, StreamArgs &a, hipStream_t st, std::vector<int> &left, bool *took) {
+  if (!S->ipm || a.opt.no_interior_point || a.b.row_compliance) return hipSuccess;
+  hipError_t e = ipm_run(S, a, st, took, &S->report.newton, &S->report.ipm_solved);
+  if (e != hipSuccess || *took || S->report.ipm_solved == 0) return e;
+  // Per-scenario fallback: the scenarios it solved are done (ctrl.done, x+ / y+ exported); only the others go on - packed into as
+  // few lane groups as they need when the lane form applies (its phases' slot -> scenario map), skipped by every other form
+  // (their kernels leave scenarios with ctrl.done alone).  One infeasible member of 256 then costs one lane group of PDHG
+  // iterations until its certificate, not the whole batch over again.
+  const int B = a.b.B;
+  std::vector<StreamCtrl> hc((size_t)B);
+  if ((e = hipMemcpyAsync(hc.data(), a.W.ctrl, (size_t)B * sizeof(StreamCtrl), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  for (int s = 0; s < B; ++s) if (!hc[s].done) left.push_back(s);
+  *took = left.empty();                                // (cannot happen: it said it left some; defensive)
+  return hipSuccess;
+}
+
+// mid-size LPs: the whole solve in ONE launch, one workgroup per scenario with its state in LDS
+static hipError_t try_block(StreamSolver *S, StreamArgs &a, hipStream_t st, bool *took) {
+  const size_t lds = ((size_t)7 * S->P.n + 7 * S->P.m + (1024 / 64) * kNQ + kNQ) * sizeof(double);
+  static const int no_block = getenv("DSP_STREAM_NO_BLOCK") ? atoi(getenv("DSP_STREAM_NO_BLOCK")) : 0;
+  if (no_block || S->P.R.nlong != 0 || lds > S->lds_limit) return hipSuccess;      // (long ROWS are not handled by the check of the block form)
+  const int nt = std::max(S->P.n, S->P.m) > 2048 ? 1024 : (std::max(S->P.n, S->P.m) > 512 ? 512 : 256);
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_block_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_finalize, dim3(a.nblk, B), dim3(kTB), 0, st, a);
+  *took = true;
+  S->report.form = DSP_STREAM_FORM_BLOCK;
+  hipLaunchKernelGGL(k_block_solve, dim3(a.b.B), dim3(nt), lds, st, a);
+  return hipSuccess;
+}
+
+// the host-enqueued forms of dsp_stream.hip, which take whatever reaches them.  Banded matrix: one launch per plain iteration, bounds
+// that are one template for the batch read once per workgroup from scenario 0's copy; two launches otherwise.
+static hipError_t run_tile_or_two_launch(StreamSolver *S, StreamArgs &a, hipStream_t st, int *periods_run) {
+  const int sg = two_launch_sg(a);
+  if (S->P.F.ntile == 0) {
+    S->report.form = DSP_STREAM_FORM_TWO_LAUNCH;               // (its bytes per iteration: the figure of a report that says none)
+    return sg == 8 ? run_two_launch<8>(S, a, st, periods_run) : sg == 4 ? run_two_launch<4>(S, a, st, periods_run)
+         : sg == 2 ? run_two_launch<2>(S, a, st, periods_run) : run_two_launch<1>(S, a, st, periods_run);
+  }
+  const bool shared = batch_bounds_shared(a.b), qp = a.b.row_compliance != nullptr;
+  S->report.form = DSP_STREAM_FORM_TILE;
+  S->report.bytes_per_iteration = one_launch_bytes_per_iteration(S->P.n, S->P.m, shared, qp);
+  return tile_sg(S->P.F, a.b.B, shared) == 2 ? run_tile<2>(S, a, st, periods_run, shared, qp) : run_tile<1>(S, a, st, periods_run, shared, qp);
+}
+
+static hipError_t stream_solve_locked(StreamSolver *S, const dsp_batch &batch, const dsp_options &opt, double eta, hipStream_t st, int *periods_run) {
+  StreamArgs a{};
+  hipError_t e = stream_begin(S, batch, opt, eta, st, a);
+  if (e != hipSuccess) return e;
+  *periods_run = -1;                                   // (the forms that count check periods on the host say how many)
+  std::vector<int> left;
+  bool took = false;
+  if ((e = try_interior_point(S, a, st, left, &took)) != hipSuccess) return e;
+  if (!took && (e = try_block(S, a, st, &took)) != hipSuccess) return e;
+  // banded matrix with a handful of long columns: the lane-per-scenario form (dsp_stream_lane.hip)
+  if (!took && (e = lane_run(S, a, st, periods_run, &took, left.empty() ? nullptr : &left)) != hipSuccess) return e;
+  if (!took && (e = run_tile_or_two_launch(S, a, st, periods_run)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_finalize, dim3(a.nblk, batch.B), dim3(kTB), 0, st, a);
   return hipGetLastError();
+}
+
+// BLOCKING and one call at a time per handle (include/dsp_hip.h, dsp_solve): the per-scenario state lives in ONE workspace per
+// handle (reallocated when a larger batch arrives) and the host polls the device's finished-counter while it enqueues the
+// iteration launches, so - unlike the fused path with its ring of work queues - two solves of one handle cannot overlap.  The
+// mutex serialises callers on different threads / streams; the call returns after its stream work has completed.
+hipError_t stream_solve(StreamSolver *S, const dsp_batch &batch, const dsp_options &opt, double eta, hipStream_t st, int *periods_run) {
+  std::lock_guard<std::mutex> lock(S->mu);
+  S->report = StreamReport{};
+  const hipError_t e = stream_solve_locked(S, batch, opt, eta, st, periods_run);
+  if (e == hipSuccess) report_interior_point(S);
+  const hipError_t es = hipStreamSynchronize(st);
+  return e != hipSuccess ? e : es;
 }
 
 }  // namespace dsp

@@ -146,8 +146,38 @@ struct StreamArgs {
   int nchunk_max;  // stride of long_partial
 };
 
+// bounds that are ONE template for the whole batch (stride 0: the price-taker families differ in the objective only)
+inline bool batch_bounds_shared(const dsp_batch &b) {
+  return (!b.var_lb || b.var_lb_stride == 0) && (!b.var_ub || b.var_ub_stride == 0) && (!b.row_lb || b.row_lb_stride == 0) &&
+         (!b.row_ub || b.row_ub_stride == 0);
+}
+// algorithmic HBM bytes per scenario and plain iteration of the one-launch forms (tile, lane): x, x0, c, y, y0 read, x, y written; bounds
+// of its own per scenario and the compliance of soft rows on top
+inline size_t one_launch_bytes_per_iteration(size_t n, size_t m, bool shared, bool qp) {
+  return (size_t)8 * (shared ? 4 * n + 3 * m : 6 * n + 5 * m) + (qp ? 8 * m : 0);
+}
+
+// The cadence of the host-enqueued PDHG forms (two-launch, tile, lane): a check every C iterations, a look at the finished counter every
+// kPollPeriods check periods and after the last one, the certificate sequence for suspects at most every kCertifyPeriods.
+constexpr int kPollPeriods = 4;
+constexpr int kCertifyPeriods = 16;
+inline int check_period(const dsp_options &o) { return o.check_every > 0 ? o.check_every : 64; }       // 0 = automatic (include/dsp_hip.h)
+inline int max_check_periods(const dsp_options &o) { return (o.max_iter + check_period(o) - 1) / check_period(o); }
+inline bool poll_due(int periods_done, int max_periods) { return periods_done % kPollPeriods == 0 || periods_done == max_periods; }
+// ndone_host: {scenarios finished, some scenario is suspect (relative gap >= 1/2 after 2048 iterations: control_decide)}
+inline bool certify_due(const int *ndone_host, int periods_done) { return ndone_host[1] && periods_done % kCertifyPeriods == 0; }
+
 struct LaneState;                      // lane-per-scenario form (dsp_stream_lane.hip); nullptr = not applicable to this matrix
 struct IpmState;                       // interior-point form for time-banded LPs (dsp_ipm.hip); nullptr = not applicable
+
+// What a solve reports (dsp_stats): value-initialised by stream_solve before anything else, then filled in by the form that takes the batch
+struct StreamReport {
+  int form = 0;                     // DSP_STREAM_FORM_*
+  int phases = 0;                   // lane form: its phases; interior point: its time partitions (dsp_stats::stream_phases)
+  size_t bytes_per_iteration = 0;   // algorithmic HBM bytes per scenario and plain iteration; 0 = the two-launch figure (stream_bytes_per_iteration)
+  int newton = 0;                   // interior-point form: Newton iterations
+  int ipm_solved = 0;               // ... and the scenarios it solved (the others went on to the PDHG forms)
+};
 
 struct StreamSolver {
   StreamProblem P{};
@@ -157,12 +187,8 @@ struct StreamSolver {
   int *ndone_host = nullptr;
   LaneState *lane = nullptr;
   IpmState *ipm = nullptr;
-  int last_newton = 0;                   // interior-point form: Newton iterations of the last solve
-  int last_ipm_solved = 0;               // ... and the scenarios it solved (the others went on to the PDHG forms)
-  int last_form = 0;                     // DSP_STREAM_FORM_* of the last solve
-  int last_phases = 0;                   // lane form: phases of the last solve (dsp_stats::stream_phases)
-  size_t last_bytes_per_iteration = 0;   // algorithmic HBM bytes per scenario and plain iteration of the form the last solve ran
-  std::mutex mu;          // one solve at a time per handle: the workspace above is per handle, not per call (stream_solve)
+  StreamReport report;    // of the last solve
+  std::mutex mu;         // one solve at a time per handle: the workspace above is per handle, not per call (stream_solve)
   size_t lds_limit = 160 * 1024 - 2048;   // dynamic LDS available to the block-resident form (static __shared__ on top)
 };
 
@@ -171,7 +197,22 @@ hipError_t stream_create(const HostCSR &A_scaled, const HostCSR &AT_scaled, cons
 void stream_destroy(StreamSolver *S);
 hipError_t stream_solve(StreamSolver *S, const dsp_batch &batch, const dsp_options &opt, double eta, hipStream_t st,
                         int *periods_run);
-size_t stream_bytes_per_iteration(const StreamSolver *S);
+// per scenario and plain iteration of the form the last solve ran: two launches 8 n + 6 m doubles (dsp_stream.hip, file header); the
+// one-launch forms say their own figure (one_launch_bytes_per_iteration); every other form and before any solve: the two-launch figure
+inline size_t stream_bytes_per_iteration(const StreamSolver *S) {
+  return S->report.bytes_per_iteration ? S->report.bytes_per_iteration : (size_t)8 * (8 * (size_t)S->P.n + 6 * (size_t)S->P.m);
+}
+// a host vector on the device (at least one element is allocated), the allocation entered in `allocs`
+template <class T>
+hipError_t stream_up(std::vector<void *> &allocs, const std::vector<T> &v, const T **out) {
+  void *d = nullptr;
+  hipError_t e = hipMalloc(&d, (v.empty() ? 1 : v.size()) * sizeof(T));
+  if (e != hipSuccess) return e;
+  allocs.push_back(d);
+  if (!v.empty() && (e = hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)) != hipSuccess) return e;
+  *out = reinterpret_cast<const T *>(d);
+  return hipSuccess;
+}
 
 // dsp_stream_lane.hip
 hipError_t lane_create(const HostCSR &A_scaled, const HostCSR &AT_scaled, StreamSolver *S);
@@ -184,5 +225,16 @@ hipError_t ipm_run(StreamSolver *S, StreamArgs &a, hipStream_t st, bool *all_sol
 int ipm_partitions(const StreamSolver *S);     // time partitions of its banded solves (1: sequential walks; 0: no interior-point plan)
 // certificate sequence on the scenario-major workspace (x, y = the current iterate): dsp_stream.hip
 hipError_t stream_certify(StreamSolver *S, StreamArgs &a, hipStream_t st);
+
+// the device's finished counter and suspect flag into S->ndone_host, after everything enqueued on `st`
+inline hipError_t stream_poll(StreamSolver *S, const StreamArgs &a, hipStream_t st) {
+  const hipError_t e = hipMemcpyAsync(S->ndone_host, a.W.ndone, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
+  return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+// The interior-point form solved the batch or part of it (a PDHG form took the rest): the solve is reported as DSP_STREAM_FORM_IPM with
+// its time partitions as phases; dsp_stats::ipm_solved says how many it solved.
+inline void report_interior_point(StreamSolver *S) {
+  if (S->report.ipm_solved > 0) { S->report.form = DSP_STREAM_FORM_IPM; S->report.phases = ipm_partitions(S); }
+}
 
 }  // namespace dsp

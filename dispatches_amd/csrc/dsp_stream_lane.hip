@@ -15,6 +15,7 @@
 // finished-counter every few periods, exactly as before.  Initialisation and results go through the scenario-major workspace of
 // dsp_stream.hip (k_init, k_init_control, k_finalize) and two transposing kernels.  A solve of more than 64 scenarios runs in
 // PHASES (lane_run): when enough scenarios have finished, the rest goes through the scenario-major workspace into fewer groups.
+// A phase on the host: lane_phase_tiling, lane_launches, lane_load, lane_iterate (-> LaneOutcome), lane_unload, lane_survivors.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -101,17 +102,6 @@ struct LaneArgs {
   dsp_options opt;
   double eta;
 };
-
-template <class T>
-hipError_t lane_up(std::vector<void *> &allocs, const std::vector<T> &v, const T **out) {
-  void *d = nullptr;
-  hipError_t e = hipMalloc(&d, std::max<size_t>(v.size(), 1) * sizeof(T));
-  if (e != hipSuccess) return e;
-  allocs.push_back(d);
-  if (!v.empty()) { e = hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice); if (e != hipSuccess) return e; }
-  *out = reinterpret_cast<const T *>(d);
-  return hipSuccess;
-}
 
 // ---- layout changes ---------------------------------------------------------------------------------------------------------------
 // scenario-major [B][len] (stride `stride`, 0 = one template for every scenario) -> lane layout [G][len + 1][64]; lanes beyond the
@@ -489,8 +479,8 @@ hipError_t lane_create(const HostCSR &A_scaled, const HostCSR &AT_scaled, Stream
   L->rec_ring = 16;                                       // the usual ring; a tiling with another one repacks (lane_records_for)
   pack_lane_records(H, L->rec_ring, crec, rrec);
   const char *cdev = nullptr, *rdev = nullptr;
-  if ((e = lane_up(L->allocs, crec, &cdev)) != hipSuccess || (e = lane_up(L->allocs, rrec, &rdev)) != hipSuccess ||
-      (e = lane_up(L->allocs, H.long_id, &L->long_id)) != hipSuccess || (e = lane_up(L->allocs, is_long, &L->is_long)) != hipSuccess) {
+  if ((e = stream_up(L->allocs, crec, &cdev)) != hipSuccess || (e = stream_up(L->allocs, rrec, &rdev)) != hipSuccess ||
+      (e = stream_up(L->allocs, H.long_id, &L->long_id)) != hipSuccess || (e = stream_up(L->allocs, is_long, &L->is_long)) != hipSuccess) {
     for (void *p : L->allocs) (void)hipFree(p);
     delete L;
     return e;
@@ -540,7 +530,7 @@ static hipError_t lane_tiling(LaneState *L, int rows_per_tile, LaneTiling **out)
     LaneTiling D;
     if (T.ok) {
       hipError_t e;
-      if ((e = lane_up(L->allocs, T.tiles, &D.tiles)) != hipSuccess || (e = lane_up(L->allocs, T.units, &D.units)) != hipSuccess) return e;
+      if ((e = stream_up(L->allocs, T.tiles, &D.tiles)) != hipSuccess || (e = stream_up(L->allocs, T.units, &D.units)) != hipSuccess) return e;
       D.ntile = T.ntile; D.nwg = (T.ntile + kLaneWaves - 1) / kLaneWaves; D.ring = T.ring; D.rows_per_tile = rows_per_tile;
     }
     it = L->tilings.emplace(key, D).first;
@@ -586,6 +576,266 @@ static hipError_t lane_workspace(LaneState *L, int B, int nwg, bool per_scenario
   return hipSuccess;
 }
 
+// ---- a solve in the lane form, piece by piece (lane_run puts them together) ---------------------------------------------------------
+struct LaneKnobs {                    // development variables, read at every solve (tests switch them)
+  // Small batches stay with the workgroup-per-tile form of round 3 (dsp_stream.hip: k_fused_pre): a lane's walk through its tile costs
+  // the same instruction stream whatever the batch - 36 us per iteration for 1 .. 32 scenarios, against 10 us (1 scenario) and
+  // 28 - 32 us (16) there; from 32 scenarios on the lane form is ahead (64: 42 vs 90 us, 256: 165 vs 407 us; profiles/r40h_lane_rates.log,
+  // r41a_lane_variants.log).  DSP_LANE_MIN_B: the threshold.
+  int min_b = getenv("DSP_LANE_MIN_B") ? atoi(getenv("DSP_LANE_MIN_B")) : 32;
+  int rows = getenv("DSP_LANE_ROWS") ? atoi(getenv("DSP_LANE_ROWS")) : 0;          // rows per tile
+  int waves = getenv("DSP_LANE_WAVES") ? atoi(getenv("DSP_LANE_WAVES")) : 0;
+  int graph = getenv("DSP_LANE_GRAPH") ? atoi(getenv("DSP_LANE_GRAPH")) : 1;
+  bool compact = !(getenv("DSP_LANE_COMPACT") && atoi(getenv("DSP_LANE_COMPACT")) == 0);   // =0: every scenario keeps its lane to the end (measurement)
+};
+
+// A solve runs in PHASES.  The first one gives every scenario of the batch a lane; whenever enough scenarios have finished to
+// free a quarter of the groups (at least one), the iterate goes back to the scenario-major workspace and the scenarios still
+// iterating are packed into fewer groups - a new tiling, a new graph: a launch costs what its groups cost, and a batch of year-long
+// LPs finishes over a 4 x range of iteration counts (35 k .. 139 k on the wind + battery family).
+struct LanePhase {
+  std::vector<int> ids;                 // slot -> scenario of this phase (empty: identity)
+  int nact = 0;                         // lane slots in use
+  const int *sid = nullptr;             // `ids` on the device (nullptr: identity)
+  LaneTiling *T = nullptr;              // its tiling (nullptr: before the first phase)
+  bool first = true, shared = true, counted = true;   // (counted in stream_phases: not a phase that only follows a certificate sequence)
+  LaneKernel kern[3];                   // what a check period launches: the kernel of each mode with its dynamic LDS, the grids
+  size_t lds[3];
+  dim3 g_tile, b_tile, g_long, tl;
+  int G() const { return (nact + 63) / 64; }
+};
+enum class LaneOutcome { finished, iteration_limit, shrink, certify };   // how a phase's iteration loop ended (the last two: another phase follows)
+
+static void lane_apply(const LanePhase &ph, const LaneArgs &q, hipStream_t s) {
+  if (q.NLP == 4) hipLaunchKernelGGL(k_lane_apply<4>, ph.g_tile, ph.b_tile, 0, s, q);
+  else hipLaunchKernelGGL(k_lane_apply<8>, ph.g_tile, ph.b_tile, 0, s, q);
+}
+
+// The tiling of a phase: wave count -> rows per tile -> tiling.  One wave per SIMD (1024 tiles) for a single group of 40 scenarios and
+// more (~50 rows per wave), two waves per SIMD (2048 tiles) otherwise - fewer scenarios (less to fetch per unit: the second wave hides
+// more than the extra halo rows cost), 2 - 3 groups (7 % / 2 % ahead), 8 and more (3 - 4 %).  Four groups: a tie in time (172 vs
+// 172 us, 164 vs 156 - 172 across boxes), and 1024 tiles move 1.01 x the algorithmic bytes against 1.12 x: 1024.
+// (profiles/r40y_, r40z_, r41a_lane_variants.log, r41l_large_batches.log, r41m_mid_batches.log, r41n_*)
+// Not applicable (no schedule for this tile size, or the check kernel's three windows + record stages of four waves beyond a CU's LDS -
+// kLaneMaxRing keeps them below: defensive): ph.T stays.  In the first phase that is nullptr: nothing has been touched, the caller's other forms
+// take the batch.  A LATER phase keeps the previous one's tiling (the scenario-major workspace holds a consistent iterate; somewhat larger tiles).
+static hipError_t lane_phase_tiling(LaneState *L, const LaneKnobs &knobs, LanePhase &ph) {
+  const int G = ph.G(), ch = lane_ch(L->plan.WC, L->plan.WR, L->plan.NLP);
+  const int want_waves = knobs.waves > 0 ? knobs.waves : (((G == 1 && ph.nact >= 40) || G == 4) ? 1024 : 2048);
+  int rows = knobs.rows > 0 ? knobs.rows : (int)(((int64_t)L->P.m * G + want_waves - 1) / want_waves);
+  rows = std::max(rows, 3 * ch);
+  rows = (rows + ch - 1) / ch * ch;
+  LaneTiling *T = nullptr;
+  const hipError_t e = lane_tiling(L, rows, &T);
+  if (e != hipSuccess) return e;
+  if (T->ntile != 0 && (size_t)kLaneWaves * (3 * (size_t)T->ring * 64 * sizeof(double) + kLaneStageBytes) <= 160u * 1024u) ph.T = T;
+  return hipSuccess;
+}
+
+// bounds: one template for the whole batch (stride 0), or equal apart from the long columns' (checked on the device)
+static hipError_t lane_bounds_shared(LaneState *L, const StreamArgs &a, hipStream_t st, bool *shared) {
+  *shared = true;
+  if (batch_bounds_shared(a.b) || a.b.B <= 1) return hipSuccess;
+  const int B = a.b.B, n = L->P.n, m = L->P.m;
+  hipError_t e;
+  if ((e = hipMemsetAsync(L->W.flag, 0, sizeof(int), st)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_lane_bounds_differ, dim3((n + 255) / 256, B - 1), dim3(256), 0, st, a.W.lb, a.W.ub, n, B, L->is_long, L->W.flag);
+  hipLaunchKernelGGL(k_lane_bounds_differ, dim3((m + 255) / 256, B - 1), dim3(256), 0, st, a.W.rlo, a.W.rhi, m, B, (const uint8_t *)nullptr, L->W.flag);
+  if ((e = hipMemcpyAsync(L->flag_host, L->W.flag, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  *shared = *L->flag_host == 0;
+  return hipSuccess;
+}
+
+// ph.ids -> the device (ph.sid)
+static hipError_t lane_slot_map(LaneState *L, int B, LanePhase &ph, hipStream_t st) {
+  ph.sid = nullptr;
+  if (ph.ids.empty()) return hipSuccess;
+  hipError_t e;
+  if (L->sid_cap < B) {
+    if (L->sid) (void)hipFree(L->sid);
+    L->sid = nullptr; L->sid_cap = 0;
+    if ((e = hipMalloc((void **)&L->sid, (size_t)B * sizeof(int))) != hipSuccess) return e;
+    L->sid_cap = B;
+  }
+  if ((e = hipMemcpyAsync(L->sid, ph.ids.data(), ph.ids.size() * sizeof(int), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  ph.sid = L->sid;
+  return hipStreamSynchronize(st);                                         // (`ids` is pageable and changes between phases)
+}
+
+static LaneArgs lane_args(const StreamSolver *S, const LaneState *L, const StreamArgs &a, const LanePhase &ph) {
+  const LaneWork &W = L->W;
+  const LaneTiling *T = ph.T;
+  const int NLP = L->plan.NLP;
+  LaneArgs la{};
+  la.P = L->P; la.P.tiles = T->tiles; la.P.units = T->units; la.P.ntile = T->ntile; la.P.ring_mask = T->ring - 1;
+  la.NLP = NLP; la.nwg = T->nwg; la.nslot = T->nwg + NLP; la.B = ph.nact; la.kofs = 0; la.sums_only = 0; la.sid = ph.sid;
+  la.long_id = L->long_id;
+  la.x0 = W.x0; la.c = W.c; la.y0 = W.y0; la.lb = W.lb; la.ub = W.ub; la.rlo = W.rlo; la.rhi = W.rhi; la.kap = W.kap;
+  la.xbl = W.xbl; la.xpl = W.xpl; la.lbl = W.lbl; la.ubl = W.ubl; la.xp = W.xp; la.yp = W.yp;
+  la.lpart = W.lpart; la.partial = W.partial; la.acc = W.acc; la.tau = W.tau; la.sig = W.sig; la.k = W.k; la.done = W.done; la.mode = W.mode;
+  la.x0w = W.x0; la.y0w = W.y0; la.xa = W.xA; la.ya = W.yA;
+  la.ctrl = a.W.ctrl; la.ndone = a.W.ndone; la.opt = a.opt; la.eta = a.eta; la.col_scale = S->P.col_scale;
+  la.rrec_stride = lane_rrec(L->plan.WR, NLP); la.ral_off = L->plan.WR * 12 + 16;
+  la.iters = check_period(a.opt);
+  return la;
+}
+
+// the kernels of the phase (false: no instantiation for this batch), their LDS and grids
+static bool lane_launches(const LaneState *L, LanePhase &ph, bool qp) {
+  const int NLP = L->plan.NLP, G = ph.G();
+  for (int mode = 0; mode < 3; ++mode) if (!(ph.kern[mode] = lane_pick(L->plan.WC, L->plan.WR, NLP, ph.shared, qp, mode))) return false;
+  const size_t lds_ring = (size_t)kLaneWaves * ph.T->ring * 64 * sizeof(double);
+  const size_t lds_red = (size_t)kLaneWaves * std::max(NLP, 8) * 64 * sizeof(double);
+  const size_t lds_stage = (size_t)kLaneWaves * kLaneStageBytes;
+  ph.lds[0] = ph.lds[2] = std::max(2 * lds_ring + lds_stage, lds_red);
+  ph.lds[1] = std::max(3 * lds_ring + lds_stage, lds_red);
+  ph.g_tile = dim3(ph.T->nwg, G); ph.b_tile = dim3(kLaneWaves * 64);
+  ph.g_long = dim3(std::max(1, L->P.nl), G); ph.tl = dim3(kLongWaves * 64);
+  return true;
+}
+
+// ---- in: scenario-major workspace -> lane layout (iterate, anchors, x+ / y+ of the last check, objective, bounds), the records'
+//      shared bounds when they are fresh, the per-lane control state, the long columns' partial sums of the y the phase starts from
+static hipError_t lane_load(const StreamSolver *S, LaneState *L, const StreamArgs &a, const LaneArgs &la, const LanePhase &ph,
+                     bool fill_records, bool qp, hipStream_t st) {
+  const LaneWork &W = L->W;
+  const int n = L->P.n, m = L->P.m, NLP = la.NLP;
+  const dim3 tb(256);
+  auto in = [&](const double *src, int len, double *dst) {
+    hipLaunchKernelGGL(k_lane_in, dim3((len + 63) / 64, ph.G()), tb, 0, st, src, (size_t)len, len, ph.nact, ph.sid, 0.0, dst);
+  };
+  in(a.W.x, n, W.xA); in(a.W.x0, n, W.x0); in(a.W.c, n, W.c); in(a.W.xp, n, W.xp);
+  in(a.W.y, m, W.yA); in(a.W.y0, m, W.y0); in(a.W.yp, m, W.yp);
+  if (!ph.shared) { in(a.W.lb, n, W.lb); in(a.W.ub, n, W.ub); in(a.W.rlo, m, W.rlo); in(a.W.rhi, m, W.rhi); }
+  if (qp) in(a.W.kap, m, W.kap);
+  if (fill_records) {           // (a.W.lb .. a.W.rhi: scenario 0's scaled bounds in the scenario-major workspace, valid for the whole solve)
+    hipLaunchKernelGGL(k_lane_fill_records, dim3((n + 255) / 256), tb, 0, st, L->crec, lane_crec(L->plan.WC), L->plan.WC * 12, L->plan.WC * 12 + 16,
+                       (const double *)a.W.lb, (const double *)a.W.ub, S->P.col_scale, n);
+    hipLaunchKernelGGL(k_lane_fill_records, dim3((m + 255) / 256), tb, 0, st, L->rrec, la.rrec_stride, L->plan.WR * 12, L->plan.WR * 12 + 16 + NLP * 8,
+                       (const double *)a.W.rlo, (const double *)a.W.rhi, S->P.row_scale, m);
+  }
+  const hipError_t e = hipMemsetAsync(W.partial, 0, (size_t)ph.G() * la.nslot * kLaneNQ * 64 * sizeof(double), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_lane_setup, dim3(ph.G()), dim3(64), 0, st, la, (const double *)a.W.lb, (const double *)a.W.ub);
+  LaneArgs q = la; q.x_in = W.xA; q.y_in = W.yA; q.sums_only = 1;          // (the iterate itself stays where it is)
+  lane_apply(ph, q, st);
+  return hipSuccess;
+}
+
+// One check period = 2 (C - 1) + 7 launches with the same arguments every time: it starts in buffer A and k_lane_apply leaves the
+// iterate there.
+static void lane_enqueue_period(const LanePhase &ph, const LaneArgs &la, const LaneWork &W, hipStream_t s) {
+  double *xcur = W.xA, *ycur = W.yA, *xalt = W.xB, *yalt = W.yB;
+  for (int u = 0; u < la.iters - 1; ++u) {
+    LaneArgs q = la; q.kofs = u; q.x_in = xcur; q.y_in = ycur; q.x_out = xalt; q.y_out = yalt;
+    if (la.P.nl) hipLaunchKernelGGL(k_lane_long<0>, ph.g_long, ph.tl, 0, s, q);
+    hipLaunchKernelGGL(ph.kern[0], ph.g_tile, ph.b_tile, ph.lds[0], s, q);
+    std::swap(xcur, xalt); std::swap(ycur, yalt);
+  }
+  LaneArgs q = la; q.kofs = 0; q.x_in = xcur; q.y_in = ycur; q.x_out = xalt; q.y_out = yalt;
+  if (la.P.nl) hipLaunchKernelGGL(k_lane_long<1>, ph.g_long, ph.tl, 0, s, q);
+  hipLaunchKernelGGL(ph.kern[1], ph.g_tile, ph.b_tile, ph.lds[1], s, q);
+  hipLaunchKernelGGL(ph.kern[2], ph.g_tile, ph.b_tile, ph.lds[2], s, q);
+  if (la.P.nl) hipLaunchKernelGGL(k_lane_long<2>, ph.g_long, ph.tl, 0, s, q);
+  hipLaunchKernelGGL(k_lane_sum, dim3(13, ph.G()), ph.tl, 0, s, q);
+  hipLaunchKernelGGL(k_lane_decide, dim3(ph.G()), dim3(64), 0, s, q);
+  LaneArgs r = la; r.x_in = xcur; r.y_in = ycur;
+  lane_apply(ph, r, s);
+}
+
+// The iteration loop of a phase, from check period *period on, at the cadence of the other host-enqueued forms (dsp_stream.hpp).  The period
+// is captured once into a hipGraph and replayed - a year-long solve is 10^3 .. 10^4 periods, and below ~30 us per iteration the host cannot
+// enqueue two launches per iteration fast enough.  The legacy default stream cannot be captured: the loop then runs on the handle's own
+// stream between two host synchronisations (the call is blocking anyway).  shrink: the scenarios still iterating fit G - max(1, G / 4) groups.
+static hipError_t lane_iterate(StreamSolver *S, const StreamArgs &a, const LanePhase &ph, const LaneArgs &la, const LaneKnobs &knobs, hipStream_t st,
+                               int *period, LaneOutcome *outcome) {
+  LaneState *L = S->lane;
+  const int B = a.b.B, max_periods = max_check_periods(a.opt);
+  hipError_t e = hipSuccess;
+  for (int mode = 0; mode < 3; ++mode)
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(ph.kern[mode]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ph.lds[mode])) != hipSuccess) return e;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (st) (void)hipStreamIsCapturing(st, &cap);
+  const bool use_graph = knobs.graph && max_periods - *period > 2 && cap == hipStreamCaptureStatusNone;
+  hipStream_t ls = st;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  if (use_graph) {
+    if (!L->stream && (e = hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking)) != hipSuccess) return e;
+    ls = L->stream;
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;                    // everything enqueued so far precedes the loop
+    if ((e = hipStreamBeginCapture(ls, hipStreamCaptureModeThreadLocal)) != hipSuccess) return e;
+    lane_enqueue_period(ph, la, L->W, ls);
+    if ((e = hipStreamEndCapture(ls, &graph)) != hipSuccess) return e;
+    if ((e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0)) != hipSuccess) { (void)hipGraphDestroy(graph); return e; }
+  }
+  const int shrink_at = (knobs.compact && ph.G() > 1) ? 64 * (ph.G() - std::max(1, ph.G() / 4)) : -1;
+  *outcome = LaneOutcome::iteration_limit;
+  while (*period < max_periods) {
+    if (use_graph) { if ((e = hipGraphLaunch(exec, ls)) != hipSuccess) break; }
+    else lane_enqueue_period(ph, la, L->W, ls);
+    ++*period;
+    if (!poll_due(*period, max_periods)) continue;
+    if ((e = stream_poll(S, a, ls)) != hipSuccess) break;
+    if (S->ndone_host[0] >= B) { *outcome = LaneOutcome::finished; break; }
+    if (*period == max_periods) break;
+    if (B - S->ndone_host[0] <= shrink_at) { *outcome = LaneOutcome::shrink; break; }
+    // Suspects: the infeasibility / unboundedness certificates are evaluated on the scenario-major workspace (stream_certify,
+    // dsp_stream.hip), so the phase ends here, the iterate goes back there, and the scenarios that are not certified go on in a new phase
+    if (certify_due(S->ndone_host, *period)) { *outcome = LaneOutcome::certify; break; }
+  }
+  if (use_graph) {
+    const hipError_t es = hipStreamSynchronize(ls);
+    (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph);
+    if (e == hipSuccess) e = es;
+  }
+  if (e != hipSuccess) return e;
+#ifdef DSP_LANE_PROBE
+  if (const char *path = getenv("DSP_LANE_PROBE_OUT")) {
+    std::vector<unsigned long long> h((size_t)kProbeWaves * kProbeSlots);
+    (void)hipStreamSynchronize(ls);
+    if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_lane_probe), h.size() * sizeof(unsigned long long)) == hipSuccess) {
+      if (FILE *f = fopen(path, "wb")) {
+        const int nwg = (la.P.ntile + kLaneWaves - 1) / kLaneWaves;
+        const int hdr[4] = {la.P.ntile, ph.G(), kLaneWaves, kProbeSlots};
+        const size_t prow = std::min<size_t>((size_t)kProbeWaves, (size_t)nwg * kLaneWaves * ph.G());
+        fwrite(hdr, sizeof(int), 4, f); fwrite(h.data(), sizeof(unsigned long long), prow * kProbeSlots, f); fclose(f);
+      }
+    }
+  }
+#endif
+  return hipSuccess;
+}
+
+// ---- out: x+, y+ of the last check back to the scenario-major workspace (k_finalize unscales them); between two phases also the
+//      iterate and its anchors (buffer A: where k_lane_apply left them)
+static void lane_unload(const LaneState *L, const StreamArgs &a, const LanePhase &ph, bool between_phases, hipStream_t st) {
+  const LaneWork &W = L->W;
+  const int n = L->P.n, m = L->P.m;
+  auto out = [&](const double *src, int len, double *dst) {
+    hipLaunchKernelGGL(k_lane_out, dim3((len + 63) / 64, ph.G()), dim3(256), 0, st, src, len, ph.nact, ph.sid, dst);
+  };
+  out(W.xp, n, a.W.xp); out(W.yp, m, a.W.yp);
+  if (between_phases) { out(W.xA, n, a.W.x); out(W.x0, n, a.W.x0); out(W.yA, m, a.W.y); out(W.y0, m, a.W.y0); }
+}
+
+// The scenarios that go on, in their order: the lanes' `done` flags - and after a certificate sequence the scenarios' control blocks,
+// where its verdicts are: a scenario that was just certified infeasible / unbounded must not take a lane in the next phase.
+static hipError_t lane_survivors(const LaneState *L, const StreamArgs &a, const LanePhase &ph, bool certified, hipStream_t st, std::vector<int> &next) {
+  std::vector<int> done_h((size_t)ph.G() * 64);
+  std::vector<StreamCtrl> hc(certified ? (size_t)a.b.B : 0);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(done_h.data(), L->W.done, done_h.size() * sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if (certified && (e = hipMemcpyAsync(hc.data(), a.W.ctrl, hc.size() * sizeof(StreamCtrl), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+  for (int slot = 0; slot < ph.nact; ++slot) {
+    const int sc = ph.ids.empty() ? slot : ph.ids[slot];
+    if (!done_h[slot] && !(certified && hc[(size_t)sc].done)) next.push_back(sc);
+  }
+  return hipSuccess;
+}
+
 // Runs the iteration loop in the lane form on the state k_init / k_init_control left in the scenario-major workspace `a.W`, and leaves
 // x+, y+ and the control blocks there for k_finalize.  *used = false: not applicable to this batch (the caller goes on with its own forms).
 // `only`: the scenarios to run (the rest of the batch is finished: the interior-point form solved it) - the first phase packs exactly those.
@@ -593,260 +843,47 @@ hipError_t lane_run(StreamSolver *S, StreamArgs &a, hipStream_t st, int *periods
   *used = false;
   LaneState *L = S->lane;
   if (!L) return hipSuccess;
-  const int B = a.b.B, n = L->P.n, m = L->P.m, NLP = L->plan.NLP;
-  // Small batches stay with the workgroup-per-tile form of round 3 (dsp_stream.hip: k_fused_pre): a lane's walk through its tile costs
-  // the same instruction stream whatever the batch - 36 us per iteration for 1 .. 32 scenarios, against 10 us (1 scenario) and
-  // 28 - 32 us (16) there; from 32 scenarios on the lane form is ahead (64: 42 vs 90 us, 256: 165 vs 407 us; profiles/r40h_lane_rates.log,
-  // r41a_lane_variants.log).  DSP_LANE_MIN_B: the threshold (development).
-  const int min_b = getenv("DSP_LANE_MIN_B") ? atoi(getenv("DSP_LANE_MIN_B")) : 32;
+  const LaneKnobs knobs;
+  const int B = a.b.B;
   // a subset worth packing: as many scenarios as the form wants of a batch; fewer go to the other forms, whose kernels leave the finished
   // scenarios of the batch alone (one scenario: 10 us per iteration there against 36 us for a lane group here)
-  const bool subset = only && (int)only->size() >= min_b;
-  if (only && !subset) return hipSuccess;
-  if (!subset && B < min_b) return hipSuccess;
+  if ((only ? (int)only->size() : B) < knobs.min_b) return hipSuccess;
   const bool qp = a.b.row_compliance != nullptr;
+  LanePhase ph;
+  if (only) ph.ids = *only;
+  ph.nact = only ? (int)only->size() : B;
+  int period = 0;
   hipError_t e;
-  const int rows_env = getenv("DSP_LANE_ROWS") ? atoi(getenv("DSP_LANE_ROWS")) : 0;          // rows per tile (development; read per solve)
-  const int waves_env = getenv("DSP_LANE_WAVES") ? atoi(getenv("DSP_LANE_WAVES")) : 0;
-  const int graph_env = getenv("DSP_LANE_GRAPH") ? atoi(getenv("DSP_LANE_GRAPH")) : 1;
-  // DSP_LANE_COMPACT=0: keep every scenario's lane to the end of the solve (measurement)
-  const bool compact = !(getenv("DSP_LANE_COMPACT") && atoi(getenv("DSP_LANE_COMPACT")) == 0);
-  const int ch = lane_ch(L->plan.WC, L->plan.WR, NLP);
-  const int CREC = lane_crec(L->plan.WC), RREC = lane_rrec(L->plan.WR, NLP);
-  const int C = a.opt.check_every > 0 ? a.opt.check_every : 64;
-  const int max_periods = (a.opt.max_iter + C - 1) / C;
-  const int poll = 4;
-  const dim3 tb(256);
-
-  // A solve runs in PHASES.  The first one gives every scenario of the batch a lane; whenever enough scenarios have finished to
-  // free a quarter of the groups (at least one), the iterate goes back to the scenario-major workspace and the scenarios still
-  // iterating are packed into fewer groups - a new tiling, a new graph: a launch costs what its groups cost, and a batch of year-long
-  // LPs finishes over a 4 x range of iteration counts (35 k .. 139 k on the wind + battery family).  `ids`: slot -> scenario of the
-  // current phase (empty: identity).
-  std::vector<int> ids;
-  int nact = B, period = 0;
-  if (subset) { ids = *only; nact = (int)ids.size(); }
-  S->last_phases = 0;
-  bool shared = true, first = true;
-  LaneTiling *Tprev = nullptr;            // the tiling the previous phase ran on
-  bool count_phase = true;
   for (;;) {
-    const int G = (nact + 63) / 64;
-    // tiles: one wave per SIMD (1024 tiles) for a single group of 40 scenarios and more (~50 rows per wave), two waves per SIMD (2048
-    // tiles) otherwise - fewer scenarios (less to fetch per unit: the second wave hides more than the extra halo rows cost), 2 - 3
-    // groups (7 % / 2 % ahead), 8 and more (3 - 4 %).  Four groups: a tie in time (172 vs 172 us, 164 vs 156 - 172 across boxes), and
-    // 1024 tiles move 1.01 x the algorithmic bytes against 1.12 x: 1024.  (profiles/r40y_, r40z_, r41a_lane_variants.log,
-    // r41l_large_batches.log, r41m_mid_batches.log, r41n_*)
-    const int want_waves = waves_env > 0 ? waves_env : (((G == 1 && nact >= 40) || G == 4) ? 1024 : 2048);
-    int rows = rows_env > 0 ? rows_env : (int)(((int64_t)m * G + want_waves - 1) / want_waves);
-    rows = std::max(rows, 3 * ch);
-    rows = (rows + ch - 1) / ch * ch;
-    LaneTiling *T = nullptr;
-    if ((e = lane_tiling(L, rows, &T)) != hipSuccess) return e;
-    // Not applicable (no schedule for this tile size, or the check kernel's three windows + record stages of four waves beyond a CU's
-    // LDS - kLaneMaxRing keeps them below: defensive): in the first phase nothing has been touched and the caller's other forms take
-    // the batch; a LATER phase - its tile size differs with the number of groups - keeps the tiling the previous phase ran on (the
-    // scenario-major workspace holds a consistent iterate; the packed groups run on somewhat larger tiles than they would have got).
-    if (T->ntile == 0 || (size_t)kLaneWaves * (3 * (size_t)T->ring * 64 * sizeof(double) + kLaneStageBytes) > 160u * 1024u) {
-      if (first) return hipSuccess;
-      T = Tprev;
-    }
-    Tprev = T;
+    if ((e = lane_phase_tiling(L, knobs, ph)) != hipSuccess) return e;
+    if (!ph.T) return hipSuccess;
     bool repacked = false;
-    if ((e = lane_records_for(L, T->ring, &repacked)) != hipSuccess) return e;
-    if ((e = lane_workspace(L, nact, T->nwg, !shared, qp)) != hipSuccess) return e;
-    if (first) {
-      // bounds: one template for the whole batch (stride 0), or equal apart from the long columns' (checked on the device)
-      shared = (!a.b.var_lb || a.b.var_lb_stride == 0) && (!a.b.var_ub || a.b.var_ub_stride == 0) &&
-               (!a.b.row_lb || a.b.row_lb_stride == 0) && (!a.b.row_ub || a.b.row_ub_stride == 0);
-      if (!shared && B > 1) {
-        if ((e = hipMemsetAsync(L->W.flag, 0, sizeof(int), st)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_lane_bounds_differ, dim3((n + 255) / 256, B - 1), dim3(256), 0, st, a.W.lb, a.W.ub, n, B, L->is_long, L->W.flag);
-        hipLaunchKernelGGL(k_lane_bounds_differ, dim3((m + 255) / 256, B - 1), dim3(256), 0, st, a.W.rlo, a.W.rhi, m, B, (const uint8_t *)nullptr, L->W.flag);
-        if ((e = hipMemcpyAsync(L->flag_host, L->W.flag, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-        shared = *L->flag_host == 0;
-      } else shared = true;
-      if (!shared) {
-        if (qp) return hipSuccess;                                     // (no instantiation: the two-launch form takes it)
-        if ((e = lane_workspace(L, nact, T->nwg, true, qp)) != hipSuccess) return e;
-      }
+    if ((e = lane_records_for(L, ph.T->ring, &repacked)) != hipSuccess) return e;
+    if ((e = lane_workspace(L, ph.nact, ph.T->nwg, !ph.shared, qp)) != hipSuccess) return e;
+    if (ph.first) {
+      if ((e = lane_bounds_shared(L, a, st, &ph.shared)) != hipSuccess) return e;
+      if (!ph.shared && qp) return hipSuccess;                               // (no instantiation: the two-launch form takes it)
+      if (!ph.shared && (e = lane_workspace(L, ph.nact, ph.T->nwg, true, qp)) != hipSuccess) return e;
     }
-    LaneWork &W = L->W;
-    LaneKernel kern[3];
-    for (int mode = 0; mode < 3; ++mode) if (!(kern[mode] = lane_pick(L->plan.WC, L->plan.WR, NLP, shared, qp, mode))) return first ? hipSuccess : hipErrorUnknown;
+    if (!lane_launches(L, ph, qp)) return ph.first ? hipSuccess : hipErrorUnknown;
     *used = true;
-    if (count_phase) ++S->last_phases;           // (a phase that only follows a certificate sequence is not a packing: not counted)
-    count_phase = true;
-    S->last_bytes_per_iteration = (size_t)8 * (shared ? 4 * (size_t)n + 3 * (size_t)m : 6 * (size_t)n + 5 * (size_t)m) + (qp ? 8 * (size_t)m : 0);
-    const int *sid = nullptr;
-    if (!ids.empty()) {
-      if (L->sid_cap < B) {
-        if (L->sid) (void)hipFree(L->sid);
-        L->sid = nullptr; L->sid_cap = 0;
-        if ((e = hipMalloc((void **)&L->sid, (size_t)B * sizeof(int))) != hipSuccess) return e;
-        L->sid_cap = B;
-      }
-      if ((e = hipMemcpyAsync(L->sid, ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-      if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;           // (`ids` is pageable and changes below)
-      sid = L->sid;
-    }
-
-    LaneArgs la{};
-    la.P = L->P; la.P.tiles = T->tiles; la.P.units = T->units; la.P.ntile = T->ntile; la.P.ring_mask = T->ring - 1;
-    la.NLP = NLP; la.nwg = T->nwg; la.nslot = T->nwg + NLP; la.B = nact; la.kofs = 0; la.sums_only = 0; la.sid = sid;
-    la.long_id = L->long_id;
-    la.x0 = W.x0; la.c = W.c; la.y0 = W.y0; la.lb = W.lb; la.ub = W.ub; la.rlo = W.rlo; la.rhi = W.rhi; la.kap = W.kap;
-    la.xbl = W.xbl; la.xpl = W.xpl; la.lbl = W.lbl; la.ubl = W.ubl; la.xp = W.xp; la.yp = W.yp;
-    la.lpart = W.lpart; la.partial = W.partial; la.acc = W.acc; la.tau = W.tau; la.sig = W.sig; la.k = W.k; la.done = W.done; la.mode = W.mode;
-    la.x0w = W.x0; la.y0w = W.y0; la.xa = W.xA; la.ya = W.yA;
-    la.ctrl = a.W.ctrl; la.ndone = a.W.ndone; la.opt = a.opt; la.eta = a.eta; la.col_scale = S->P.col_scale;
-    la.rrec_stride = RREC; la.ral_off = L->plan.WR * 12 + 16;
-    la.iters = C;
-
-    // ---- in: scenario-major workspace -> lane layout (iterate, anchors, x+ / y+ of the last check, objective, bounds) ----------------
-    const dim3 gcol((n + 63) / 64, G), grow((m + 63) / 64, G);
-    auto in = [&](const double *src, int len, double *dst) {
-      hipLaunchKernelGGL(k_lane_in, len == n ? gcol : grow, tb, 0, st, src, (size_t)len, len, nact, sid, 0.0, dst);
-    };
-    in(a.W.x, n, W.xA); in(a.W.x0, n, W.x0); in(a.W.c, n, W.c); in(a.W.xp, n, W.xp);
-    in(a.W.y, m, W.yA); in(a.W.y0, m, W.y0); in(a.W.yp, m, W.yp);
-    if (!shared) { in(a.W.lb, n, W.lb); in(a.W.ub, n, W.ub); in(a.W.rlo, m, W.rlo); in(a.W.rhi, m, W.rhi); }
-    if (qp) in(a.W.kap, m, W.kap);
-    if (first || repacked) {      // (a.W.lb .. a.W.rhi: scenario 0's scaled bounds in the scenario-major workspace, valid for the whole solve)
-      hipLaunchKernelGGL(k_lane_fill_records, dim3((n + 255) / 256), tb, 0, st, L->crec, CREC, L->plan.WC * 12, L->plan.WC * 12 + 16,
-                         (const double *)a.W.lb, (const double *)a.W.ub, S->P.col_scale, n);
-      hipLaunchKernelGGL(k_lane_fill_records, dim3((m + 255) / 256), tb, 0, st, L->rrec, RREC, L->plan.WR * 12, L->plan.WR * 12 + 16 + NLP * 8,
-                         (const double *)a.W.rlo, (const double *)a.W.rhi, S->P.row_scale, m);
-    }
-    if ((e = hipMemsetAsync(W.partial, 0, (size_t)G * la.nslot * kLaneNQ * 64 * sizeof(double), st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_lane_setup, dim3(G), dim3(64), 0, st, la, (const double *)a.W.lb, (const double *)a.W.ub);
-
-    const dim3 g_tile(T->nwg, G), b_tile(kLaneWaves * 64);
-    const size_t lds_ring = (size_t)kLaneWaves * T->ring * 64 * sizeof(double);
-    const size_t lds_red = (size_t)kLaneWaves * std::max(NLP, 8) * 64 * sizeof(double);
-    const size_t lds_stage = (size_t)kLaneWaves * kLaneStageBytes;
-    const size_t lds[3] = {std::max(2 * lds_ring + lds_stage, lds_red), std::max(3 * lds_ring + lds_stage, lds_red), std::max(2 * lds_ring + lds_stage, lds_red)};
-    for (int mode = 0; mode < 3; ++mode)
-      if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern[mode]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds[mode])) != hipSuccess) return e;
-    // the long columns' partial sums of the y the phase starts from (the iterate itself stays where it is)
-    {
-      LaneArgs q = la; q.x_in = W.xA; q.y_in = W.yA; q.sums_only = 1;
-      if (NLP == 4) hipLaunchKernelGGL(k_lane_apply<4>, g_tile, b_tile, 0, st, q);
-      else hipLaunchKernelGGL(k_lane_apply<8>, g_tile, b_tile, 0, st, q);
-    }
-
-    const dim3 g_long(std::max(1, L->P.nl), G), tl(kLongWaves * 64);
-    // One check period = 2 (C - 1) + 7 launches with the same arguments every time (a period starts in buffer A and k_lane_apply
-    // leaves the iterate there): captured once into a hipGraph and replayed - a year-long solve is 10^3 .. 10^4 periods, and below
-    // ~30 us per iteration the host cannot enqueue two launches per iteration fast enough.  The legacy default stream cannot be
-    // captured: the loop then runs on the handle's own stream between two host synchronisations (the call is blocking anyway).
-    auto enqueue_period = [&](hipStream_t s) {
-      double *xcur = W.xA, *ycur = W.yA, *xalt = W.xB, *yalt = W.yB;
-      for (int u = 0; u < C - 1; ++u) {
-        LaneArgs q = la; q.kofs = u; q.x_in = xcur; q.y_in = ycur; q.x_out = xalt; q.y_out = yalt;
-        if (L->P.nl) hipLaunchKernelGGL(k_lane_long<0>, g_long, tl, 0, s, q);
-        hipLaunchKernelGGL(kern[0], g_tile, b_tile, lds[0], s, q);
-        std::swap(xcur, xalt); std::swap(ycur, yalt);
-      }
-      LaneArgs q = la; q.kofs = 0; q.x_in = xcur; q.y_in = ycur; q.x_out = xalt; q.y_out = yalt;
-      if (L->P.nl) hipLaunchKernelGGL(k_lane_long<1>, g_long, tl, 0, s, q);
-      hipLaunchKernelGGL(kern[1], g_tile, b_tile, lds[1], s, q);
-      hipLaunchKernelGGL(kern[2], g_tile, b_tile, lds[2], s, q);
-      if (L->P.nl) hipLaunchKernelGGL(k_lane_long<2>, g_long, tl, 0, s, q);
-      hipLaunchKernelGGL(k_lane_sum, dim3(13, G), tl, 0, s, q);
-      hipLaunchKernelGGL(k_lane_decide, dim3(G), dim3(64), 0, s, q);
-      LaneArgs r = la; r.x_in = xcur; r.y_in = ycur;
-      if (NLP == 4) hipLaunchKernelGGL(k_lane_apply<4>, g_tile, b_tile, 0, s, r);
-      else hipLaunchKernelGGL(k_lane_apply<8>, g_tile, b_tile, 0, s, r);
-    };
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st) (void)hipStreamIsCapturing(st, &cap);
-    const bool use_graph = graph_env && max_periods - period > 2 && cap == hipStreamCaptureStatusNone;
-    hipStream_t ls = st;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (use_graph) {
-      if (!L->stream && (e = hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking)) != hipSuccess) return e;
-      ls = L->stream;
-      if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;                    // everything enqueued so far precedes the loop
-      if ((e = hipStreamBeginCapture(ls, hipStreamCaptureModeThreadLocal)) != hipSuccess) return e;
-      enqueue_period(ls);
-      if ((e = hipStreamEndCapture(ls, &graph)) != hipSuccess) return e;
-      if ((e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0)) != hipSuccess) { (void)hipGraphDestroy(graph); return e; }
-    }
-    // scenarios still iterating below which the phase ends: they fit G - max(1, G / 4) groups
-    const int shrink_at = (compact && G > 1) ? 64 * (G - std::max(1, G / 4)) : -1;
-    bool finished = false, shrink = false, certify = false;
-    for (; period < max_periods;) {
-      if (use_graph) { if ((e = hipGraphLaunch(exec, ls)) != hipSuccess) break; }
-      else enqueue_period(ls);
-      ++period;
-      if (period % poll == 0 || period == max_periods) {
-        if ((e = hipMemcpyAsync(S->ndone_host, a.W.ndone, 2 * sizeof(int), hipMemcpyDeviceToHost, ls)) != hipSuccess) break;
-        if ((e = hipStreamSynchronize(ls)) != hipSuccess) break;
-        if (S->ndone_host[0] >= B) { finished = true; break; }
-        if (B - S->ndone_host[0] <= shrink_at && period < max_periods) { shrink = true; break; }
-        // Suspects (relative gap >= 1/2 after 2048 iterations: control_decide): the infeasibility / unboundedness certificates are
-        // evaluated on the scenario-major workspace (stream_certify, dsp_stream.hip), so the phase ends here, the iterate goes back
-        // there, and the scenarios that are not certified go on in a new phase - at most every 16 check periods.
-        if (S->ndone_host[1] && period % 16 == 0 && period < max_periods) { shrink = true; certify = true; break; }
-      }
-    }
-    if (use_graph) {
-      const hipError_t es = hipStreamSynchronize(ls);
-      (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph);
-      if (e == hipSuccess) e = es;
-    }
-    if (e != hipSuccess) return e;
-#ifdef DSP_LANE_PROBE
-    if (const char *path = getenv("DSP_LANE_PROBE_OUT")) {
-      std::vector<unsigned long long> h((size_t)kProbeWaves * kProbeSlots);
-      (void)hipStreamSynchronize(ls);
-      if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_lane_probe), h.size() * sizeof(unsigned long long)) == hipSuccess) {
-        if (FILE *f = fopen(path, "wb")) {
-          const int nwg = (T->ntile + kLaneWaves - 1) / kLaneWaves;
-          const int hdr[4] = {T->ntile, G, kLaneWaves, kProbeSlots};
-          const size_t prow = std::min<size_t>((size_t)kProbeWaves, (size_t)nwg * kLaneWaves * G);
-          fwrite(hdr, sizeof(int), 4, f); fwrite(h.data(), sizeof(unsigned long long), prow * kProbeSlots, f); fclose(f);
-        }
-      }
-    }
-#endif
-    // ---- out: x+, y+ of the last check back to the scenario-major workspace (k_finalize unscales them); between two phases also the
-    //      iterate and its anchors (buffer A: where k_lane_apply left them) -----------------------------------------------------------
-    auto out = [&](const double *src, int len, double *dst) {
-      hipLaunchKernelGGL(k_lane_out, len == n ? gcol : grow, tb, 0, st, src, len, nact, sid, dst);
-    };
-    out(W.xp, n, a.W.xp); out(W.yp, m, a.W.yp);
-    if (!shrink) break;
-    (void)finished;
-    out(W.xA, n, a.W.x); out(W.x0, n, a.W.x0); out(W.yA, m, a.W.y); out(W.y0, m, a.W.y0);
-    if (certify) {
-      if ((e = stream_certify(S, a, st)) != hipSuccess) return e;
-      count_phase = false;
-    }
-    // the scenarios that go on, in their order
-    std::vector<int> done_h((size_t)G * 64);
-    if ((e = hipMemcpyAsync(done_h.data(), W.done, done_h.size() * sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-    // (after a certificate sequence the verdicts are in the scenarios' control blocks, not in the lanes' flags: a scenario that was just
-    //  certified infeasible / unbounded must not take a lane in the next phase)
-    std::vector<StreamCtrl> hc;
-    if (certify) {
-      hc.resize((size_t)B);
-      if ((e = hipMemcpyAsync(hc.data(), a.W.ctrl, (size_t)B * sizeof(StreamCtrl), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-      if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-    }
+    S->report.form = DSP_STREAM_FORM_LANE;
+    S->report.phases += ph.counted ? 1 : 0;
+    S->report.bytes_per_iteration = one_launch_bytes_per_iteration(L->P.n, L->P.m, ph.shared, qp);
+    if ((e = lane_slot_map(L, B, ph, st)) != hipSuccess) return e;
+    const LaneArgs la = lane_args(S, L, a, ph);
+    if ((e = lane_load(S, L, a, la, ph, ph.first || repacked, qp, st)) != hipSuccess) return e;
+    LaneOutcome outcome;
+    if ((e = lane_iterate(S, a, ph, la, knobs, st, &period, &outcome)) != hipSuccess) return e;
+    const bool again = outcome == LaneOutcome::shrink || outcome == LaneOutcome::certify;
+    lane_unload(L, a, ph, again, st);
+    if (!again) break;
+    if (outcome == LaneOutcome::certify && (e = stream_certify(S, a, st)) != hipSuccess) return e;
     std::vector<int> next;
-    for (int slot = 0; slot < nact; ++slot) {
-      const int sc = ids.empty() ? slot : ids[slot];
-      if (!done_h[slot] && !(certify && hc[(size_t)sc].done)) next.push_back(sc);
-    }
+    if ((e = lane_survivors(L, a, ph, outcome == LaneOutcome::certify, st, next)) != hipSuccess) return e;
     if (next.empty()) break;
-    ids.swap(next);
-    nact = (int)ids.size();
-    first = false;
+    ph.ids.swap(next); ph.nact = (int)ph.ids.size();
+    ph.first = false; ph.counted = outcome != LaneOutcome::certify;
   }
   *periods_run = period;
   return hipGetLastError();
