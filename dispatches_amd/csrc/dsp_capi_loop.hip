@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "dsp_capi_internal.hpp"
+#include "dsp_record_check.hpp"
 
 using namespace dsp;
 
@@ -129,6 +130,13 @@ int dsp_loop_ledger(const dsp_loop_state *st, const dsp_loop_model *tr, const ds
   }
   if (st->B == 0) return DSP_OK;
   HIP_TRY(launch_loop_ledger(*st, *tr, *g, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
+// the recorder (ABI 21): the descriptor's check is dsp_record_check.hpp's, every plant index included
+int dsp_loop_record(const dsp_loop_record_desc *rec, int32_t B, void *hipStream) {
+  if (!loop_record_ok(rec, B)) return DSP_ERR_INVALID;
+  HIP_TRY(launch_loop_record(*rec, (hipStream_t)hipStream));
   return DSP_OK;
 }
 

@@ -183,6 +183,7 @@ hipError_t launch_solve_f32(int cpl, int rpl, const SolveArgs &a, int num_cus, s
 hipError_t launch_wb_rolling(const dsp_wb_state &st, const dsp_wb_model &rt, const dsp_wb_model &tr, int phase, int k, hipStream_t stream);
 hipError_t launch_loop_update(const dsp_loop_state &st, const dsp_loop_model &rt, const dsp_loop_model &tr, int phase, int k, hipStream_t stream);
 hipError_t launch_loop_ledger(const dsp_loop_state &st, const dsp_loop_model &tr, const dsp_loop_ledger_desc &ledger, hipStream_t stream);
+hipError_t launch_loop_record(const dsp_loop_record_desc &rec, hipStream_t stream);
 // bid-curve points of a solved batch (dsp_bids.hip)
 hipError_t launch_bid_points(const dsp_bid_request &rq, hipStream_t st);
 // stochastic mode of the wind + battery double loop (dsp_market.hip): scenario fan-out, curve + clearing

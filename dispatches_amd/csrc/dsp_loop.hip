@@ -171,7 +171,35 @@ __global__ void __launch_bounds__(256) loop_ledger_kernel(dsp_loop_state s, cons
   g.acc[at] = __dadd_rn(g.acc[at], loop_opaque(v));
 }
 
+// ---- the recorder of the descriptor loop (dsp_loop_record, ABI 21): one lane per element (recorded plant q, element j), j fastest ---------
+// A pure gather.  blockIdx.y is the segment, so the segment's fields and the row are wave-uniform; consecutive lanes take consecutive j
+// of one plant, so a wave's stores are consecutive and its loads are wherever elem_stride == 1.  The row comes from the device clock:
+// whatever falls outside [0, rows) - past the span, or the hour before hour 0 - goes to the spare row `rows`.
+__global__ void __launch_bounds__(256) loop_record_kernel(dsp_loop_record_desc d) {
+  const dsp_loop_record_segment &g = d.segments[blockIdx.y];
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= d.n_plants * g.width) return;
+  const int q = e / g.width, j = e - q * g.width;
+  const long long t = *d.clock + d.offset;
+  const long long r = (t < 0 || t / d.divisor >= d.rows) ? d.rows : t / d.divisor;
+  const size_t from = (size_t)d.plants[q] * (size_t)g.plant_stride + (size_t)j * (size_t)g.elem_stride;
+  const size_t to = ((size_t)r * d.n_plants + q) * g.width + j;
+  if (g.elem_bytes == 8)
+    ((unsigned long long *)g.dst)[to] = ((const unsigned long long *)g.src)[from];
+  else
+    ((unsigned int *)g.dst)[to] = ((const unsigned int *)g.src)[from];
+}
+
 namespace dsp {
+
+// the grid's x spans the widest segment; a narrower one leaves its surplus blocks idle (they return at once)
+hipError_t launch_loop_record(const dsp_loop_record_desc &rec, hipStream_t stream) {
+  int widest = 0;
+  for (int g = 0; g < rec.n_segments; ++g) widest = rec.segments[g].width > widest ? rec.segments[g].width : widest;
+  const long long lanes = (long long)rec.n_plants * widest;
+  hipLaunchKernelGGL(loop_record_kernel, dim3((unsigned)((lanes + 255) / 256), rec.n_segments), dim3(256), 0, stream, rec);
+  return hipGetLastError();
+}
 
 hipError_t launch_loop_ledger(const dsp_loop_state &st, const dsp_loop_model &tr, const dsp_loop_ledger_desc &ledger, hipStream_t stream) {
   hipLaunchKernelGGL(loop_ledger_kernel, dim3((st.B + 255) / 256, ledger.n_forms), dim3(256), 0, stream, st, tr.x, (int)tr.n, tr.wind_kw,

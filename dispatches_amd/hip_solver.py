@@ -109,10 +109,10 @@ EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_
                     "dsp_get_scaling", "dsp_destroy", "dsp_strerror", "dsp_last_hip_error", "dsp_version",
                     "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
                     "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step", "dsp_loop_project",
-                    "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare", "dsp_loop_ledger")
+                    "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare", "dsp_loop_ledger", "dsp_loop_record")
 
 
-ABI_VERSION = 20         # DSP_VERSION of the include/dsp_hip.h these structures mirror
+ABI_VERSION = 21        # DSP_VERSION of the include/dsp_hip.h these structures mirror
 
 
 BID_MAX_HOURS, BID_MAX_SCENARIOS = 64, 16384
@@ -199,6 +199,22 @@ class DspLoopLedgerDesc(C.Structure):
                 ("cols", (C.c_int32 * LEDGER_MAX_TERMS) * LEDGER_MAX_FORMS), ("per_avail", C.c_double * LEDGER_MAX_FORMS),
                 ("coef", C.c_void_p), ("constant", C.c_void_p), ("coef_stride", C.c_int64), ("const_stride", C.c_int64),
                 ("acc", C.c_void_p), ("hour_value", C.c_void_p)]
+
+
+RECORD_MAX_PLANTS, RECORD_MAX_SEGMENTS, RECORD_MAX_WIDTH = 64, 16, 1 << 20
+
+
+class DspLoopRecordSegment(C.Structure):
+    """include/dsp_hip.h: dsp_loop_record_segment (ABI 21) - one strided source and its place in the record"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("plant_stride", C.c_int64), ("elem_stride", C.c_int64),
+                ("width", C.c_int32), ("elem_bytes", C.c_int32)]
+
+
+class DspLoopRecordDesc(C.Structure):
+    """include/dsp_hip.h: dsp_loop_record_desc (ABI 21) - the gather of the recorded plants' buffers into the row the clock names"""
+    _fields_ = [("n_plants", C.c_int32), ("n_segments", C.c_int32), ("plants", C.c_int32 * RECORD_MAX_PLANTS), ("clock", C.c_void_p),
+                ("divisor", C.c_int32), ("offset", C.c_int32), ("rows", C.c_int32), ("reserved", C.c_int32),
+                ("segments", DspLoopRecordSegment * RECORD_MAX_SEGMENTS)]
 
 
 def source_hash(root: Optional[str] = None) -> Optional[str]:
@@ -298,6 +314,8 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_project.restype = C.c_int
     lib.dsp_loop_ledger.argtypes = [C.POINTER(DspLoopState), C.POINTER(DspLoopModel), C.POINTER(DspLoopLedgerDesc), vp]
     lib.dsp_loop_ledger.restype = C.c_int
+    lib.dsp_loop_record.argtypes = [C.POINTER(DspLoopRecordDesc), i32, vp]
+    lib.dsp_loop_record.restype = C.c_int
     lib.dsp_last_hip_error.restype = C.c_int
     if path == _LIB_PATH:
         _lib = lib

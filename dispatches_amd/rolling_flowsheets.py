@@ -80,7 +80,11 @@ third choice again): in the last T_rt - 1 hours of a day the look-ahead periods 
 would still order across scenarios; this loop does not.  Not settled here: whether upstream idaes additionally orders the real-time power
 output across scenarios - idaes is not available to this project; the loop follows this project's host Bidder.
 `_day_ahead_step_monotone` (on `_coupled_blocks`, shared with the self-schedule) is the specification as tensor operations;
-csrc/dsp_market.hip (dsp_loop_monotone_prepare; dsp_loop_market_clear on a state with coupled = 1) is the same arithmetic, bit for bit."""
+csrc/dsp_market.hip (dsp_loop_monotone_prepare; dsp_loop_market_clear on a state with coupled = 1) is the same arithmetic, bit for bit.
+
+Recording (record=(plants, days); loop_record.py): what the reference's four result files per generator are made of - states, solutions,
+curves, dispatches, delivered power - kept hour by hour for up to 64 plants in device buffers, by one gather launch per write
+(dsp_loop_record) inside the captured steps, and written as those files through the host classes' own row builders (write_results)."""
 from __future__ import annotations
 
 import numpy as np
@@ -473,7 +477,7 @@ class BatchedDoubleLoop(_DeviceLoop):
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
                  market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
                  battery_mwh=None, ruc_hour=None, scenario_coupling="independent", ledger=False, pem_mw=None, tank_kg=None,
-                 h2_price=None, h2_demand=None):
+                 h2_price=None, h2_demand=None, record=None, record_max_bytes=2 ** 30):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -542,10 +546,29 @@ class BatchedDoubleLoop(_DeviceLoop):
         (the notebook: 500 - 100 = 400), so a larger PEM can offer below 400 MW (dsp_loop_market_state::p_min_cents_plant); p_max
         stays 500.  They combine with plant_windows, n_price_scenarios, forecaster, market, ruc_hour, graphs and ledger.  Refused
         (ValueError): another flowsheet, bidder="self_schedule" / "parametrized", scenario_coupling="monotone", a wrong length,
-        non-finite or negative values, pem_mw outside (0, 500]."""
+        non-finite or negative values, pem_mw outside (0, 500].
+        record: None (the loops above: same launches, same bits) or (plants, days): keep, for up to 64 plants of the batch (strictly
+        increasing indices) and `days` simulated days, what the reference's four result files per generator are made of, in device
+        buffers [hours or days (+ 1 spare row), plants, ...] (loop_record.py).  Per day, in the row of the day the bid is FOR (a bid made
+        at the RUC hour of day d: row d + 1): da_state (the state the bid was built on; ruc_hour: the projected one), da_x [S, n] (a
+        plant's S rows, or the S blocks of its one coupled row), da_obj / da_c0 / da_status / da_iters (per row of the batch), da_curve /
+        da_count (modes with curves), da_offer / da_prices (of a pending bid: the pending buffers).  Per hour, after the tracking solve
+        and the ledger and before the hand-off: state (the state the hour's LPs were built from), rt_x [per, n] / rt_obj / rt_c0 /
+        rt_status (per = S, 1 for a self-schedule), rt_curve / rt_count / rt_dispatch, tr_x / tr_obj / tr_c0 / tr_status, ledger_hour
+        [F] with ledger=True; after the hand-off: delivered.  bidder="parametrized" has no bidding LP: curves, offers and the tracker
+        only.  The projection tracker's chain of ruc_hour is not recorded (the reference writes no files for it; it ends on da_state).
+        Each of the three writes is one launch of dsp_loop_record inside the step, so the captured graphs stay as many and replay the
+        record; hours and days past the span land in the spare row.  recorded() returns host arrays cut to what was run, plus
+        `plants`; write_results(path) the reference's files; reset() zeroes the record; record_bytes is its size.  Refused
+        (ValueError): plants that are not increasing, not distinct or outside [0, B), more than 64 plants, days < 1, buffers above
+        record_max_bytes (default 2 ** 30: a guard against recording a whole batch by mistake, not a measured figure)."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
+        self._rec, self.record_bytes = None, 0
+        if record is not None:
+            from .loop_record import check_record
+            record = check_record(record, B)
         self.S = S = int(n_price_scenarios)
         self.D = D = int(max_historical_days)
         bid_price, storage_mw, ruc_hour, sizes, plant_windows = self._validate(
@@ -663,6 +686,8 @@ class BatchedDoubleLoop(_DeviceLoop):
             self._da_step = self._day_ahead_step_stochastic if self.stochastic else self._day_ahead_step
             self._hour = self._hour_step_bid if self.stochastic else self._hour_step
             self._n_da, self._n_hour = B * S, B * S + B
+        if record is not None:
+            self._record_setup(record, int(record_max_bytes))
 
     # -- setup: buffers, argument checks, per-mode operands, the kernels' descriptors -----------------------------------------------------
     def _market_buffers(self, slots):
@@ -1006,12 +1031,31 @@ class BatchedDoubleLoop(_DeviceLoop):
             bid.rt_history_lag_days = 1
             self._mk_bid = bid
 
+    def _record_setup(self, record, max_bytes):
+        """the recorder (loop_record.LoopRecorder: buffers, segments, descriptors) and the day-ahead step that ends with its daily write"""
+        from .loop_record import LoopRecorder
+        self._rec = LoopRecorder(self, record[0], record[1], max_bytes)
+        self.record_bytes = self._rec.bytes
+        step = self._da_step
+
+        def recorded_step(bid=False):
+            if bid:
+                step(bid=True)
+            else:
+                step()
+            self._rec.write("bid" if bid else "daily")
+        self._da_step = recorded_step
+
     # -- the kernels (C ABI, on the current stream: _call) ------------------------------------------------------------------------------
     def _fused(self, phase, k):
         import ctypes as C
         if phase == 2 and self.ledger:                 # the implemented hour is booked before the hand-off advances the clock
             self._call(self._lib.dsp_loop_ledger, C.byref(self._loop_state), C.byref(self._loop_tr), C.byref(self._loop_ledger))
+        if phase == 2 and self._rec is not None:       # ... and recorded: the state is still the one the hour's LPs were built from
+            self._rec.write("hour")
         self._call(self._lib.dsp_loop_update, C.byref(self._loop_state), C.byref(self._loop_rt), C.byref(self._loop_tr), phase, k)
+        if phase == 2 and self._rec is not None:       # after the hand-off: delivered power of the hour that just ended (clock - 1)
+            self._rec.write("after")
 
     def _param(self, phase, k):
         import ctypes as C
@@ -1109,6 +1153,8 @@ class BatchedDoubleLoop(_DeviceLoop):
         tr = self.tr
         if self.ledger:
             self._ledger_book(x)
+        if self._rec is not None:
+            self._rec.write("hour")
         day_ahead = self.da_offer[:, k] * (self.da_prices[:, k] - rt0)
         if exact:
             p = tr.PT_const[0].expand(self.B)
@@ -1122,6 +1168,8 @@ class BatchedDoubleLoop(_DeviceLoop):
         self.revenue += exact_fma(torch, self.delivered, rt0, day_ahead) if exact else self.delivered * rt0 + day_ahead
         self.energy_mwh += self.delivered
         self.hour_t += 1
+        if self._rec is not None:
+            self._rec.write("after")
 
     def _ledger_book(self, x):
         """the ledger of the implemented hour on the tracker's solution x [B, n], BEFORE the hand-off (the clock is still the hour's), in
@@ -1500,6 +1548,8 @@ class BatchedDoubleLoop(_DeviceLoop):
         else:
             self._run("da", self._da_step)
         self.solves += self._n_da
+        if self._rec is not None:
+            self._rec.days_bid = max(self._rec.days_bid, self.hour // 24 + 1)
         return self.da_offer.clone()
 
     def hour_step(self):
@@ -1508,6 +1558,8 @@ class BatchedDoubleLoop(_DeviceLoop):
             self._run(k, lambda: (self._ruc_step(), self._hour(k)))
             self.solves += self._n_da + (self.B * (24 - k) if len(self.scale) else 0)
             self._pending = True
+            if self._rec is not None:                  # the bid of the next day sits in its daily row
+                self._rec.days_bid = max(self._rec.days_bid, self.hour // 24 + 2)
         else:
             self._run(k, lambda: self._hour(k))
         self.solves += self._n_hour
@@ -1519,6 +1571,23 @@ class BatchedDoubleLoop(_DeviceLoop):
             t.zero_()
         self._pending = False
         self.hour = self.solves = 0
+        if self._rec is not None:
+            self._rec.reset()
+
+    def recorded(self):
+        """-> dict of host arrays [hours or days run, plants, ...] of the record (record=... at construction; keys: __init__'s docstring),
+        and `plants`"""
+        if self._rec is None:
+            raise RuntimeError("this loop records nothing: construct it with record=(plants, days)")
+        return self._rec.recorded()
+
+    def write_results(self, path, start_date="2020-01-02"):
+        """the reference's bidder_detail.csv, bidding_model_detail.csv, tracker_detail.csv and tracking_model_detail.csv of every recorded
+        plant, in path/plant_<index>/, hour 0 of the run being hour 0 of start_date (loop_record.write_results)"""
+        from .loop_record import write_results
+        if self._rec is None:
+            raise RuntimeError("this loop records nothing: construct it with record=(plants, days)")
+        write_results(self, path, start_date)
 
     def results(self):
         res = dict(obj=self.revenue, energy_mwh=self.energy_mwh, state=self.state)

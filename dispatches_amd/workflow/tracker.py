@@ -158,17 +158,23 @@ class Tracker:
         date, hour = kwargs.get("date"), kwargs.get("hour")
         fs = self.model.fs
         P_T = fs.expressions[self.tracking_model_object.power_output]
-        rows = []
-        for t in self.model.HOUR:
-            lo = fs.row_lo[self.model.tracking_rows[t]]
-            rows.append({
-                "Date": date, "Hour": hour, "Horizon [hr]": int(t),
-                "Power Dispatch [MW]": None if not np.isfinite(lo) else round(lo + self.model.PT_const[t], 2),
-                "Power Output [MW]": round(fs.value(P_T[t]), 2),
-                "Power Underdelivered [MW]": round(self.model.power_underdelivered[t].value, 2),
-                "Power Overdelivered [MW]": round(self.model.power_overdelivered[t].value, 2),
-            })
+        HOUR = self.model.HOUR
+        rows = self.detail_rows(date, hour, [fs.row_lo[self.model.tracking_rows[t]] for t in HOUR], self.model.PT_const,
+                                [fs.value(P_T[t]) for t in HOUR], [self.model.power_underdelivered[t].value for t in HOUR],
+                                [self.model.power_overdelivered[t].value for t in HOUR])
         self.result_list.append(rows)              # row dicts; the frame is built once in write_results
+
+    @staticmethod
+    def detail_rows(date, hour, dispatch_lo, pt_const, power, under, over):
+        """The rows of tracker_detail.csv of one tracked hour, one per horizon period t: dispatch_lo[t] is the lower bound of the
+        dispatch row (dispatch - PT_const; not finite: no dispatch was passed), power / under / over the values of P_T[t] and of the
+        two deviation columns.  The one statement of these columns: record_results above, and the device loop's writer
+        (loop_record.write_results) on a recorded solution."""
+        return [{"Date": date, "Hour": hour, "Horizon [hr]": int(t),
+                 "Power Dispatch [MW]": None if not np.isfinite(dispatch_lo[t]) else round(dispatch_lo[t] + pt_const[t], 2),
+                 "Power Output [MW]": round(power[t], 2),
+                 "Power Underdelivered [MW]": round(under[t], 2),
+                 "Power Overdelivered [MW]": round(over[t], 2)} for t in range(len(power))]
 
     def write_results(self, path):
         print("")

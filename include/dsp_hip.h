@@ -33,6 +33,9 @@
  * ABI 20 adds the per-plant ledger of the implemented hour: dsp_loop_ledger evaluates up to 8 linear forms (total cost, missed delivery,
  * curtailment, hydrogen, ...) on the tracker's solution and adds them to per-plant accumulators, before phase 2 of dsp_loop_update
  * advances the clock; and dsp_loop_market_state::p_min_cents_plant, a per-plant minimum power of the bid curves (appended; NULL = ABI 19).
+ * ABI 21 adds the recorder of the descriptor loop: dsp_loop_record copies up to 16 strided segments (states, solutions, curves, ...) of up
+ * to 64 chosen plants into the row of the record that the device clock names - one gather launch, so that the record is written by the
+ * replayed hipGraphs too.  Nothing else changes.
  */
 #ifndef DSP_HIP_H
 #define DSP_HIP_H
@@ -45,7 +48,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 20
+#define DSP_VERSION 21
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -458,6 +461,41 @@ typedef struct dsp_loop_ledger_desc {
  * columns in `tr` (tr->wind_cols[0] < 0), without st->cf_series / st->start / st->hour, or with N < 1.  B = 0 is DSP_OK and no launch.
  * Capturable: one kernel launch on hipStream, no allocation, no synchronisation. */
 int dsp_loop_ledger(const dsp_loop_state *st, const dsp_loop_model *tr, const dsp_loop_ledger_desc *ledger, void *hipStream);
+
+/* The recorder of the descriptor loop (ABI 21; rolling_flowsheets.py::BatchedDoubleLoop(record=(plants, days))): a pure gather - no
+ * arithmetic, no atomics, no LDS - of n_segments strided buffers of n_plants chosen plants into ONE row of the record.  With
+ *     t = *clock + offset ;   r = t / divisor  if  t >= 0 and t / divisor < rows,   r = rows  otherwise (the SPARE row)
+ * element j of recorded plant q of segment g is read at  src + plants[q] * plant_stride + j * elem_stride  and written at
+ * dst + (r * n_plants + q) * width + j  (all in elements of elem_bytes bytes).  So every dst holds rows + 1 rows of n_plants * width
+ * elements, and whatever falls outside the recorded span - the hours after it, the hour "-1" of offset -1 at clock 0 - lands in the spare
+ * last row, never out of bounds (the rule of rolling.py::_record).  The two strides let a source be plant-major ([B][width]: plant_stride
+ * = its row length, elem_stride = 1) or plant-minor (the ledger's [F][B]: plant_stride = 1, elem_stride = B).  One lane per element,
+ * the segment is blockIdx.y (descriptor reads are wave-uniform), consecutive lanes take consecutive j of one plant. */
+#define DSP_RECORD_MAX_PLANTS 64
+#define DSP_RECORD_MAX_SEGMENTS 16
+#define DSP_RECORD_MAX_WIDTH 1048576
+typedef struct dsp_loop_record_segment {
+  const void *src;                     /* the live buffer                                                                         */
+  void *dst;                           /* [rows + 1][n_plants][width] of the record                                               */
+  int64_t plant_stride, elem_stride;   /* in elements, each 1 .. 2^40                                                             */
+  int32_t width, elem_bytes;           /* 1 .. DSP_RECORD_MAX_WIDTH elements per plant; 4 or 8 bytes each                         */
+} dsp_loop_record_segment;
+typedef struct dsp_loop_record_desc {
+  int32_t n_plants, n_segments;        /* 1 .. DSP_RECORD_MAX_PLANTS; 1 .. DSP_RECORD_MAX_SEGMENTS                                */
+  int32_t plants[64];                  /* strictly increasing, in [0, B): held by value so that the entry point checks every one  */
+  const int64_t *clock;                /* [1] device: the loop's clock (dsp_loop_state::hour) or the clock of a bid               */
+  int32_t divisor, offset;             /* 1 = an hourly record, 24 = a daily one (1 .. 8784); 0, or -1 = the hour just ended      */
+  int32_t rows, reserved;              /* the span, 1 .. 2^24 (dst has one more); reserved = 0                                    */
+  dsp_loop_record_segment segments[16];
+} dsp_loop_record_desc;
+
+/* B is the number of plants of the batch the sources belong to.  DSP_ERR_INVALID, nothing launched and nothing written, for: a NULL rec or
+ * rec->clock; B < 1; n_plants outside 1 .. DSP_RECORD_MAX_PLANTS; n_segments outside 1 .. DSP_RECORD_MAX_SEGMENTS; rows outside 1 .. 2^24;
+ * divisor outside 1 .. 8784; an offset other than 0 or -1; reserved != 0; plants that are not strictly increasing, or one outside [0, B);
+ * in a used segment a NULL src or dst, a width outside 1 .. DSP_RECORD_MAX_WIDTH, an elem_bytes other than 4 or 8, a plant_stride or
+ * elem_stride outside 1 .. 2^40.  (That the sources hold B plants at these strides is the caller's statement, as for every buffer of this
+ * interface.)  Capturable: one kernel launch on hipStream, no allocation, no synchronisation, no memset. */
+int dsp_loop_record(const dsp_loop_record_desc *rec, int32_t B, void *hipStream);
 
 /* The scenario half of the Bidder's bid assembly ON THE DEVICE (reference: idaes Bidder._assemble_bids as DISPATCHES drives it -
  * dispatches/workflow/coordinator.py hands its bids to Prescient; golden values
