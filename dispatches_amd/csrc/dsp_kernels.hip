@@ -255,6 +255,28 @@ struct Rare {
   __device__ __forceinline__ void set(double x) { if constexpr (L) lds_store_f64(addr, x); else v = x; }
 };
 
+// A wave-uniform flag of the solve loop.  PACK (the three-wave metric kernel): one bit of a word all of them share - kept as `bool`
+// each is a 64-bit lane mask in two scalar registers through the whole solve, and the scalar file is what that kernel is short of.
+// Every other kernel keeps the plain `bool` (wave_flag<false, BIT>), and with it its code, instruction for instruction.
+template <unsigned BIT>
+struct WaveFlag {
+  unsigned &word;
+  __device__ __forceinline__ operator bool() const { return (word >> BIT) & 1u; }
+  __device__ __forceinline__ WaveFlag &operator=(bool v) { word = (word & ~(1u << BIT)) | ((unsigned)v << BIT); return *this; }
+};
+struct NoFlagWord {};
+template <bool PACK, unsigned BIT> struct wave_flag {
+  using type = bool;
+  using word = NoFlagWord;
+  static constexpr __device__ __forceinline__ bool make(NoFlagWord, bool v) { return v; }
+};
+template <unsigned BIT> struct wave_flag<true, BIT> {
+  using type = WaveFlag<BIT>;
+  using word = unsigned;
+  static __device__ __forceinline__ WaveFlag<BIT> make(unsigned &w, bool v) { WaveFlag<BIT> f{w}; f = v; return f; }
+};
+#define DSP_WAVE_FLAG(NAME, BIT, INIT) typename wave_flag<ARGS_HERE, BIT>::type NAME = wave_flag<ARGS_HERE, BIT>::make(wave_flags, INIT)
+
 // LIGHT (launch bounds only - the body is the same): the generic kernel as the FOLLOW-UP pass (certificates, re-certification) of a
 // three-wave first pass, compiled for blocks of one wave at three waves per SIMD, so that a block fits the 168 VGPRs ONE leaving
 // wave of the first pass sets free; at 256 VGPRs a wave needs two of a SIMD's three gone, a block of four that on one CU four times
@@ -379,6 +401,24 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
   // allocator spills - four scratch reloads, each behind its own s_waitcnt, on the path of every check.  `opt_here` keeps the
   // compiler from hoisting them back out of the loop.
   auto opt_here = [](double v) __attribute__((always_inline)) { asm volatile("" : "+s"(v)); return v; };
+  // ARGS_HERE (the three-wave metric kernel): the options of the restart, steady and ray-jump tests are LOADED where they are used,
+  // from the kernel-argument segment through the scalar data cache.  Held in scalar registers from the kernel's entry they - and the
+  // comparisons on them the compiler forms up there, 64-bit lane masks each - are spilled to VGPR lanes, and the allocator brings a
+  // spilled argument back eight registers at a time, the s_load_dwordx8 it arrived in: 57 v_readlane_b32, VALU-issued in all 64
+  // lanes, on the path of a check on which nothing fires.  `args_here` makes the segment's address opaque, so that nothing read
+  // through it is hoisted back; the loads return where no LDS gather is in flight.
+  constexpr bool ARGS_HERE = three_waves_shape(CPL, RPL, WC, WR, QP);
+  using args_ptr = const __attribute__((address_space(4))) char *;
+  auto args_here = []() __attribute__((always_inline)) {
+    args_ptr p = (args_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+  };
+#define DSP_ARG(p, member) (*(const __attribute__((address_space(4))) decltype(SolveArgs::member) *)((p) + __builtin_offsetof(SolveArgs, member)))
+#define DSP_OPT(p, field) (*(const __attribute__((address_space(4))) decltype(dsp_options::field) *)((p) + __builtin_offsetof(SolveArgs, opt) + __builtin_offsetof(dsp_options, field)))
+#define DSP_OPT_HERE(field) (ARGS_HERE ? DSP_OPT(ka, field) : a.opt.field)
+#define DSP_OPT_F64(field) (ARGS_HERE ? DSP_OPT(ka, field) : opt_here(a.opt.field))
+#define DSP_OPT_LOADED(loaded, argument) (ARGS_HERE ? (loaded) : (argument))      /* a value the ARGS_HERE kernel loaded in a batch */
   // The step sizes are folded into the products: out = init + tau A^T (vector in yb) and out = init - sig A (vector in
   // xb).  Register-resident matrices hold tau A^T / -sig A themselves, so a PDHG half-step is the FMA chain alone;
   // the LDS matrix is shared by the block's waves (each with its own weight) and is scaled on the way out.
@@ -562,7 +602,8 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
     }
     // warm start on patience (dsp_options::warm_patience): started from the caller's point, not terminated after that many iterations ->
     // once more from the cold point at the next check (the restart block)
-    bool warm = a.opt.warm_patience > 0 && a.skip_solved == 0 && (b.x0 != nullptr || b.y0 != nullptr);      // (first pass only: the later passes' x0 is the pass before)
+    typename wave_flag<ARGS_HERE, 0>::word wave_flags{};      // (ARGS_HERE: the five flags below, one bit each)
+    DSP_WAVE_FLAG(warm, 0, a.opt.warm_patience > 0 && a.skip_solved == 0 && (b.x0 != nullptr || b.y0 != nullptr));      // (first pass only: the later passes' x0 is the pass before)
 
     DSP_TRACE("[trace] loaded w=%g\n", w);
     int k = 0;                       // iterations since the last restart
@@ -573,13 +614,13 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
     double gate2 = 0.0;              // the next gated KKT test runs once r^2 <= gate2
     int jump_not_before = 0;         // no ray-jump test while k (iterations since the anchor reset) is below this
     int stalls = 0;                  // restarts forced after >= stall_rescue iterations without decay
-    bool waive_obj = false;          // stalled twice: terminate on the eps_rel tests alone
-    bool lastjump = false;           // the last restart of the anchor was a ray jump
-    bool suspect = false;            // the last KKT test found the objectives drifting apart: KKT tests at every 4th check from then on
+    DSP_WAVE_FLAG(waive_obj, 1, false);    // stalled twice: terminate on the eps_rel tests alone
+    DSP_WAVE_FLAG(lastjump, 2, false);    // the last restart of the anchor was a ray jump
+    DSP_WAVE_FLAG(suspect, 3, false);    // the last KKT test found the objectives drifting apart: KKT tests at every 4th check from then on
     int nsus = 0;                    // consecutive KKT tests that did (register-resident kernels: three of them end the first pass)
     pol_best.set(INFINITY);          // polish phase (eps_rel tests hold, eps_obj tests missing): best worst-ratio seen,
     int pol_it = 0, nboost = 0;      //   the iteration it was seen at, guard tightenings so far
-    bool pol_tried = false;          //   the guard test of this stagnation period has been made
+    DSP_WAVE_FLAG(pol_tried, 4, false);    //   the guard test of this stagnation period has been made
     pol_po.set(0.0);                 //   primal objective when the best ratio was seen
 #ifdef DSP_KKT_TRACE
     int ntrace = 0;
@@ -723,14 +764,20 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
           const double dy = yp[q] - y[q];
           py = fma(dy, fma(2.0, adx[q], dy), py);
         }
+        // (ARGS_HERE: the two options of the gate, requested ahead of the reduction and waited for behind it)
+        args_ptr ka = nullptr;
+        double kkt_gate = 0.0;
+        int kkt_every_ = 0;
+        if constexpr (ARGS_HERE) { ka = args_here(); kkt_gate = DSP_OPT(ka, kkt_gate); kkt_every_ = DSP_OPT(ka, kkt_every); }
         const double r = fmax(wave_sum(fma(w, px, iw * py)), 0.0);
+        if constexpr (ARGS_HERE) { asm volatile("" : "+s"(kkt_gate), "+s"(kkt_every_)); kkt_every_ = kkt_every_ > 0 ? kkt_every_ : 1; }
         if (!(r == r)) { status = DSP_STATUS_NUMERICAL; break; }
         // ---- KKT test at (x+, y+) in the ORIGINAL (unscaled) space: 7 reductions + two SpMVs, so it is scheduled from
         // r, which the restart test has anyway (see dsp_options::kkt_gate); kkt_gate = 0: every kkt_every-th check
         ++ncheck;
-        const bool kkt_now = (a.opt.kkt_gate > 0.0
-                                  ? (ncheck - last_kkt >= (last_kkt ? kkt_every : min(4, kkt_every)) || r <= gate2)
-                                  : (ncheck % kkt_every) == 0) || (suspect && (ncheck & 3) == 0);
+        const bool kkt_now = (DSP_OPT_LOADED(kkt_gate, a.opt.kkt_gate) > 0.0
+                                  ? (ncheck - last_kkt >= (last_kkt ? DSP_OPT_LOADED(kkt_every_, kkt_every) : min(4, DSP_OPT_LOADED(kkt_every_, kkt_every))) || r <= gate2)
+                                  : (ncheck % DSP_OPT_LOADED(kkt_every_, kkt_every)) == 0) || (suspect && (ncheck & 3) == 0);
         DSP_PROF_ADD(1)
         if (kkt_now) {
 #pragma unroll
@@ -877,16 +924,29 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
         }
         // ---- restart test (r0 = residual at the first check after a restart) ----------------------------------
         const bool first = !(r0 < INFINITY);
-        const double rs_ = opt_here(a.opt.restart_sufficient), rn_ = opt_here(a.opt.restart_necessary);
+        // (ARGS_HERE: what the three tests below read, in one round trip)
+        double rs_, rn_, ra_ = 0.0, js_ = 0.0;
+        int warm_patience = 0, stall_rescue = 0, ray_jumps = 0, check_every_ = 0;
+        if constexpr (ARGS_HERE) {
+          ka = args_here();
+          rs_ = DSP_OPT(ka, restart_sufficient); rn_ = DSP_OPT(ka, restart_necessary); ra_ = DSP_OPT(ka, restart_artificial);
+          js_ = DSP_OPT(ka, jump_steady);
+          warm_patience = DSP_OPT(ka, warm_patience); stall_rescue = DSP_OPT(ka, stall_rescue); ray_jumps = DSP_OPT(ka, ray_jumps);
+          check_every_ = DSP_OPT(ka, check_every);
+          asm volatile("" : "+s"(rs_), "+s"(rn_), "+s"(ra_), "+s"(js_), "+s"(warm_patience), "+s"(stall_rescue), "+s"(ray_jumps), "+s"(check_every_));
+          check_every_ = check_every_ > 0 ? check_every_ : (CPL + RPL > 8 ? 32 : 16);
+        } else {
+          rs_ = opt_here(a.opt.restart_sufficient); rn_ = opt_here(a.opt.restart_necessary);
+        }
         const double beta_s2 = rs_ * rs_, beta_n2 = rn_ * rn_;
         const bool decayed = (r <= beta_s2 * r0) || (r <= beta_n2 * r0 && r > rprev);
-        const bool artificial = (double)k >= a.opt.restart_artificial * (double)(it - it0 + 1);
-        const bool give_up_warm = warm && it >= a.opt.warm_patience;
+        const bool artificial = (double)k >= DSP_OPT_LOADED(ra_, a.opt.restart_artificial) * (double)(it - it0 + 1);
+        const bool give_up_warm = warm && it >= DSP_OPT_LOADED(warm_patience, a.opt.warm_patience);
         const bool do_restart = (!first && (decayed || artificial)) || boost_now || give_up_warm;
         // no decay for >= stall_rescue iterations: the iteration sits on its rounding floor (dsp_options::stall_rescue).
         // First time, with the weight within 30x of its rounding guard: the controller has driven the weight away, reset
         // it.  From the second time on: nothing more to gain, the eps_obj tests are waived (the eps_rel tests stay).
-        const bool floor_hit = do_restart && !boost_now && !decayed && a.opt.stall_rescue > 0 && k >= a.opt.stall_rescue;
+        const bool floor_hit = do_restart && !boost_now && !decayed && DSP_OPT_LOADED(stall_rescue, a.opt.stall_rescue) > 0 && k >= DSP_OPT_LOADED(stall_rescue, a.opt.stall_rescue);
         const bool stalled = floor_hit && stalls == 0 && (w < 30.0 * w_lo.get() || 30.0 * w > w_hi.get());
         if (floor_hit && ++stalls >= 2) { waive_obj = true; gate2 = INFINITY; }
 #ifdef DSP_NO_JUMP
@@ -894,11 +954,11 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
 #else
         // steady residual over two checks, or (chaining, ray_jumps = 2) the previous event was a jump: a landing point
         // usually lies on the next piece's ray already, so it is tested again at its first check
-        const double js_ = opt_here(a.opt.jump_steady);
+        if constexpr (!ARGS_HERE) js_ = opt_here(a.opt.jump_steady);
         const double steady_lo2 = (1.0 - js_) * (1.0 - js_), steady_hi2 = (1.0 + js_) * (1.0 + js_);
-        const bool steady = a.opt.ray_jumps && !do_restart && k >= jump_not_before &&
-                            ((k >= 2 * check_every && rprev >= steady_lo2 * r && rprev <= steady_hi2 * r) ||
-                             (a.opt.ray_jumps > 1 && lastjump && k >= check_every));
+        const bool steady = DSP_OPT_LOADED(ray_jumps, a.opt.ray_jumps) && !do_restart && k >= jump_not_before &&
+                            ((k >= 2 * DSP_OPT_LOADED(check_every_, check_every) && rprev >= steady_lo2 * r && rprev <= steady_hi2 * r) ||
+                             (DSP_OPT_LOADED(ray_jumps, a.opt.ray_jumps) > 1 && lastjump && k >= DSP_OPT_LOADED(check_every_, check_every)));
 #endif
         if (first) r0 = r;
         rprev = r;
@@ -929,7 +989,8 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
             // log(w |dx| / |dy|) and the exponential in single precision (hardware v_log_f32 / v_exp_f32): the weight
             // is a heuristic parameter, 1e-7 relative noise on it is irrelevant and FP64 log + exp cost ~150 instructions
             const float e = __logf((float)w) + 0.5f * (__logf((float)dd[0]) - __logf((float)dd[1]));
-            const float kp_ = (float)opt_here(a.opt.pid_kp), md_ = (float)opt_here(a.opt.max_dlog_weight);
+            if constexpr (ARGS_HERE) ka = args_here();
+            const float kp_ = (float)DSP_OPT_F64(pid_kp), md_ = (float)DSP_OPT_F64(max_dlog_weight);
             const float dl = fminf(fmaxf(-kp_ * e, -md_), md_);
             w *= (double)__expf(dl);
           }
@@ -1042,7 +1103,8 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
           // the ratio test (one FP64 division per owned element + a wave-min) only for rays that pass the translation
           // test: about one attempt in ten
           double alpha = 0.0;
-          const double jt_ = opt_here(a.opt.jump_tol);
+          if constexpr (ARGS_HERE) ka = args_here();
+          const double jt_ = DSP_OPT_F64(jump_tol);
           if (tt[1] > 0.0 && tt[0] <= jt_ * jt_ * tt[1]) {
             // the unprojected points of the FIRST application, recomputed (bit-identical to what the step above had)
             double g0x[CPL], g0y[RPL];
@@ -1066,8 +1128,9 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
           }
           // a ray that is too short to be worth an anchor reset reaches its breakpoint by itself in alpha steps: no
           // point in testing again before that
-          if (alpha >= a.opt.jump_min && alpha < a.opt.jump_rel * (double)k) jump_not_before = k + (int)fmin(alpha, 1e6);
-          if (alpha >= a.opt.jump_min && alpha >= a.opt.jump_rel * (double)k && alpha < 1e200) {
+          if constexpr (ARGS_HERE) ka = args_here();
+          if (alpha >= DSP_OPT_HERE(jump_min) && alpha < DSP_OPT_HERE(jump_rel) * (double)k) jump_not_before = k + (int)fmin(alpha, 1e6);
+          if (alpha >= DSP_OPT_HERE(jump_min) && alpha >= DSP_OPT_HERE(jump_rel) * (double)k && alpha < 1e200) {
             const double al = floor(alpha) - 1.0;
 #pragma unroll
             for (int q = 0; q < CPL; ++q) {
@@ -1091,6 +1154,9 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
       if (!moved) DSP_HALPERN_STEP(DSP_ANCHOR_WEIGHT())
       DSP_PROF_ADD(5)
     }
+#undef DSP_OPT_HERE
+#undef DSP_OPT_LOADED
+#undef DSP_OPT_F64
 #undef DSP_PDHG_STEP
 #undef DSP_SET_STEPS
 #undef DSP_SET_SCALARS
