@@ -13,7 +13,7 @@ class _NoSolver:
         raise RuntimeError("template model: never solved on the host")
 
 
-def attach_solver(m, B, dev, device_index, extra_options, lp_backend, solved=True):
+def attach_solver(m, B, dev, device_index, extra_options, lp_backend, solved=True, simplex_certify=False):
     """m.opts / opts_warm / opts_first, m.dlp and m.out of a device model m (m.lp, m.T set) with B rows.
     recertify: the loop never reads a flag back between solves (its days are hipGraph replays), so a solve accepted without a certified
     objective accuracy is re-solved on the device under other settings (dsp_options::recertify_passes) - three passes for a day-ahead LP,
@@ -22,6 +22,9 @@ def attach_solver(m, B, dev, device_index, extra_options, lp_backend, solved=Tru
     come back flagged, the loop's `uncertified` count says so.  They share one matrix from hour to hour: the simplex starts hour k from
     hour k - 1's final basis (dsp_options::simplex_warm = 1: 2 - 4 pivots instead of ~26) and from the slack basis in the first hour
     of every day (= 2).  The output buffers have fixed addresses from the start: the fused kernels and the hipGraphs hold pointers.
+    simplex_certify: the hourly LPs (T <= 16) are solved under dsp_options::simplex_certify = 1 - the simplex stores status 0 only for a pair
+    (x, y) that passed the full KKT certificate against the original LP and flags it DSP_FLAG_SIMPLEX_KKT; what it rejects reaches the PDLP
+    pass, whose status and flags feed `bad` / `uncertified` as ever.  m.out then carries the certificates, kkt [B, 4].
     lp_backend: tests pass a stand-in with DeviceLP.solve's signature (CPU tensors + HiGHS); solved=False: a template never solved."""
     import torch
     if lp_backend is not None:
@@ -29,6 +32,8 @@ def attach_solver(m, B, dev, device_index, extra_options, lp_backend, solved=Tru
         return
     from .hip_solver import DspOptions
     extra = {"recertify_passes": 3} if m.T > 16 else {"recertify_passes": 0, "eps_infeasible": 0.0}
+    if simplex_certify and m.T <= 16:
+        extra["simplex_certify"] = 1
     m.opts = default_options(**{**extra, **(extra_options or {})})
     m.opts_warm, m.opts_first = DspOptions.from_buffer_copy(m.opts), DspOptions.from_buffer_copy(m.opts)
     if m.T <= 16:
@@ -37,6 +42,8 @@ def attach_solver(m, B, dev, device_index, extra_options, lp_backend, solved=Tru
     f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
     i32 = lambda: torch.zeros(B, dtype=torch.int32, device=dev)
     m.out = dict(x=f64(B, m.lp.n), y=f64(B, max(m.lp.m, 1)), obj=f64(B), status=i32(), iters=i32(), jumps=i32(), flags=i32())
+    if m.opts.simplex_certify == 1:
+        m.out["kkt"] = torch.full((B, 4), float("nan"), dtype=torch.float64, device=dev)
 
 
 class _DeviceLoop:

@@ -298,10 +298,11 @@ static int create_device_objects(dsp_handle *h, const HostCSR &A) {
 }
 
 // ---- dsp_solve in passes, none of which allocates per solve.  First the options this solve runs under (a->opt, a->eta, a->qp)
-static int resolve_options(const dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, SolveArgs *a) {
-  a->P = h->P; a->b = *batch; a->anchor_w = h->anchor_w;
-  a->opt = opt ? *opt : h->opt;
-  const dsp_options &o = a->opt;
+// (*full: the caller's options, resolved; the kernels' argument block carries their view of them and of the batch, dsp_device.hpp)
+static int resolve_options(const dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, SolveArgs *a, dsp_options *full) {
+  a->P = h->P; a->b = prefix_of(*batch); a->anchor_w = h->anchor_w;
+  *full = opt ? *opt : h->opt;
+  dsp_options &o = *full;
   if (o.max_iter < 1 || o.check_every < 0 || o.kkt_every < 0 || !(o.kkt_gate >= 0) || o.stall_rescue < 0 || o.polish_patience < 0 || !(o.jump_rel >= 0) ||
       !(o.eps_rel > 0) || !(o.eps_obj >= 0) || !(o.eps_infeasible >= 0) || !(o.pid_kp >= 0) || !(o.restart_artificial >= 0) || !(o.step_scale > 0))
     return DSP_ERR_INVALID;
@@ -310,14 +311,17 @@ static int resolve_options(const dsp_handle *h, const dsp_batch *batch, const ds
   // 0 = automatic (include/dsp_hip.h): the fused float64 kernels restart their Halpern epochs earlier and steer the primal
   // weight more gently than the HBM-resident and float32 paths, which keep the values they were tuned with
   const bool fused64 = !h->streaming && o.precision == 0;
-  if (o.restart_artificial == 0.0) a->opt.restart_artificial = fused64 ? (a->qp ? 0.3 : 0.2) : 0.36;
-  if (o.pid_kp == 0.0) a->opt.pid_kp = fused64 ? 0.6 : 0.7;
+  if (o.restart_artificial == 0.0) o.restart_artificial = fused64 ? (a->qp ? 0.3 : 0.2) : 0.36;
+  if (o.pid_kp == 0.0) o.pid_kp = fused64 ? 0.6 : 0.7;
   if (o.precision != 0 && o.precision != 1) return DSP_ERR_INVALID;
+  // the in-wave simplex' KKT certificate: off or on, a tolerance that is a number >= 0 (0 = 1e-9), its output only when it is on
+  if ((o.simplex_certify != 0 && o.simplex_certify != 1) || !(o.simplex_kkt_tol >= 0.0) || (batch->kkt && !o.simplex_certify)) return DSP_ERR_INVALID;
   // float32 iterates exist in the fused kernels only; soft rows in the fused kernels without long vectors and in the
   // HBM-resident streaming form
   const bool has_long = h->P.long_c.count > 0 || h->P.long_r.count > 0;
   if (o.precision && (h->streaming || has_long)) return DSP_ERR_INVALID;
   if (a->qp && !h->streaming && has_long) return DSP_ERR_INVALID;
+  a->opt = prefix_of(o);
   return DSP_OK;
 }
 
@@ -361,10 +365,10 @@ static int *claim_queue_slot(dsp_handle *h, hipStream_t st, int ints) {
   return q;
 }
 
-static int solve_streaming(dsp_handle *h, const dsp_batch *batch, const SolveArgs &a, dsp_stats *stats, bool timed, hipStream_t st) {
+static int solve_streaming(dsp_handle *h, const dsp_batch *batch, const dsp_options &full, const SolveArgs &a, dsp_stats *stats, bool timed, hipStream_t st) {
   if (timed) HIP_TRY(hipEventRecord(h->ev0, st));
   int periods = 0;
-  HIP_TRY(stream_solve(&h->stream, *batch, a.opt, a.eta, st, &periods));
+  HIP_TRY(stream_solve(&h->stream, *batch, full, a.eta, st, &periods));
   if (timed) HIP_TRY(hipEventRecord(h->ev1, st));
   stats->streaming = 1; stats->quadratic = a.qp;
   stats->grid_blocks = (std::max(h->n, h->m) + 255) / 256; stats->block_threads = 256;
@@ -402,7 +406,8 @@ static int grow_simplex_warm(dsp_handle *h, int B) {
 }
 
 // simplex pass: certified vertices get their final status; DSP_STATUS_UNSOLVED marks what the PDLP kernel still has to do
-static int simplex_pass(dsp_handle *h, SolveArgs &a, hipStream_t st) {
+// (batch, full: the caller's structures - the certificate's output and options are not in the kernels' views of them)
+static int simplex_pass(dsp_handle *h, const dsp_batch *batch, const dsp_options &full, SolveArgs &a, hipStream_t st) {
   if (!h->simplex || a.qp) return DSP_OK;
   const int B = a.b.B;
   SimplexArgs sa{};
@@ -416,10 +421,11 @@ static int simplex_pass(dsp_handle *h, SolveArgs &a, hipStream_t st) {
     sa.warm = a.opt.simplex_warm;
     sa.warm_T = h->sx_warm_T; sa.warm_basis = h->sx_warm_basis; sa.warm_upper = h->sx_warm_upper; sa.warm_valid = h->sx_warm_valid;
   }
+  const SimplexCertArgs cert{batch->kkt, full.simplex_kkt_tol > 0.0 ? full.simplex_kkt_tol : 1e-9};
   static const int sx_debug = getenv("DSP_SX_DEBUG") ? atoi(getenv("DSP_SX_DEBUG")) : 0;
   sa.debug_keep = sx_debug;
   const int per_cu = std::max<int>(1, std::min<int>(32, (int)((size_t)h->lds_limit / h->sx_lds)));
-  HIP_TRY(launch_simplex(sa, std::min(B, h->num_cus * per_cu), h->sx_lds, st));
+  HIP_TRY(launch_simplex(sa, full.simplex_certify ? &cert : nullptr, std::min(B, h->num_cus * per_cu), h->sx_lds, st));
   a.skip_solved = 1;
   return DSP_OK;
 }
@@ -479,7 +485,7 @@ static int recertify_passes(dsp_handle *h, const SolveArgs &a, Followup f, hipSt
   return DSP_OK;
 }
 
-static int solve_fused(dsp_handle *h, const dsp_batch *batch, SolveArgs &a, dsp_stats *stats, bool timed, hipStream_t st) {
+static int solve_fused(dsp_handle *h, const dsp_batch *batch, const dsp_options &full, SolveArgs &a, dsp_stats *stats, bool timed, hipStream_t st) {
   const int B = batch->B, qp = a.qp;
   if (qp && h->rtc_state[1] == -1) {
     // first QP solve on a run-time specialised shape: compile its QP instantiation (the layout is the tight one already)
@@ -514,7 +520,7 @@ static int solve_fused(dsp_handle *h, const dsp_batch *batch, SolveArgs &a, dsp_
   const Followup f = followup_geometry(h, a.matreg && !qp && h->rtc_state[0] != 1 && h->light_lds > 0);
   if (a.matreg && a.opt.eps_infeasible > 0.0 && !f.wpb) a.opt.eps_infeasible = 0.0;
   if (timed) HIP_TRY(hipEventRecord(h->ev0, st));
-  if ((rc = simplex_pass(h, a, st)) != DSP_OK) return rc;
+  if ((rc = simplex_pass(h, batch, full, a, st)) != DSP_OK) return rc;
   HIP_TRY(first_pass(h, a, grid, geo.lds, st));
   if ((rc = certificate_pass(h, a, f, timed, st)) != DSP_OK || (rc = recertify_passes(h, a, f, st)) != DSP_OK) return rc;
   if (timed) HIP_TRY(hipEventRecord(h->ev1, st));
@@ -533,7 +539,10 @@ static int solve_fused(dsp_handle *h, const dsp_batch *batch, SolveArgs &a, dsp_
   stats->quadratic = qp; stats->rtc = (h->rtc_state[qp] == 1 && a.matreg) ? 1 : 0;
   stats->lds_conflicts_identity = h->lds_conflicts[0] + h->lds_conflicts[2];
   stats->lds_conflicts_chosen = a.matreg ? h->lds_conflicts[1] + h->lds_conflicts[3] : stats->lds_conflicts_identity;
-  return finish_stats(h, batch, stats, timed, st);
+  if ((rc = finish_stats(h, batch, stats, timed, st)) != DSP_OK || !timed || !stats->simplex) return rc;
+  // (the stream is idle: finish_stats waited) what the simplex pass counted for the PDLP pass
+  HIP_TRY(hipMemcpy(&stats->simplex_unsolved, a.unsolved, sizeof(int32_t), hipMemcpyDeviceToHost));
+  return DSP_OK;
 }
 
 extern "C" {
@@ -571,6 +580,8 @@ void dsp_default_options(dsp_options *o) {
   o->recertify_passes = 0;
   o->simplex_warm = 0;
   o->warm_patience = 0;
+  o->simplex_certify = 0;
+  o->simplex_kkt_tol = 0.0;      // 1e-9 (simplex_pass)
 }
 
 int dsp_version(void) { return DSP_VERSION; }
@@ -644,14 +655,18 @@ int dsp_solve(dsp_handle *h, const dsp_batch *batch, const dsp_options *opt, dsp
   hipStream_t st = (hipStream_t)hipStream;
   HIP_TRY(hipSetDevice(h->device));
   SolveArgs a{};
-  if (int rc = resolve_options(h, batch, opt, &a)) return rc;
+  dsp_options full;
+  if (int rc = resolve_options(h, batch, opt, &a, &full)) return rc;
   dsp_stats lent;                                   // (the paths always fill a struct; `timed`: the caller waits for it)
   const bool timed = stats && sync_stats;
   stats = stats ? stats : &lent;
   std::memset(stats, 0, sizeof(*stats));
-  if (h->streaming) return solve_streaming(h, batch, a, stats, timed, st);
+  // a certificate output on a call the in-wave simplex does not serve (larger LPs, soft rows, float32 iterates): all NaN (bytes 0xFF)
+  if (batch->kkt && !(h->simplex && !a.qp && !h->streaming && a.opt.precision == 0))
+    HIP_TRY(hipMemsetAsync(batch->kkt, 0xFF, (size_t)batch->B * 4 * sizeof(double), st));
+  if (h->streaming) return solve_streaming(h, batch, full, a, stats, timed, st);
   if (a.opt.precision == 1) return solve_f32(h, batch, a, stats, timed, st);
-  return solve_fused(h, batch, a, stats, timed, st);
+  return solve_fused(h, batch, full, a, stats, timed, st);
 }
 
 int dsp_spmv_step(dsp_handle *h, int32_t B, const double *X, const double *Y, double *AX, double *ATY, void *hipStream) {

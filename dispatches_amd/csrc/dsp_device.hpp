@@ -65,6 +65,32 @@ struct DeviceProblem {
   const int32_t *mr_nat_slot_x, *mr_nat_slot_y;                    // [n_pad] / [m_pad]  8 * slot(position(column j / row i))
 };
 
+// The kernels' views of dsp_batch and dsp_options (include/dsp_hip.h): the members up to ABI 21, in the same order and at the same offsets.
+// Kernel argument blocks embed THESE, not the public structures, so that a member appended to the public ones (ABI 22: dsp_batch::kkt,
+// dsp_options::simplex_certify / simplex_kkt_tol, which no solve kernel but the certifying simplex reads) moves no offset in the argument
+// block of any kernel and the default kernels compile to what they were.  Filled from the caller's structures by prefix_of().
+struct KernelBatch {
+  int32_t B; int32_t reserved; const double *c; int64_t c_stride; const double *var_lb; int64_t var_lb_stride; const double *var_ub;
+  int64_t var_ub_stride; const double *row_lb; int64_t row_lb_stride; const double *row_ub; int64_t row_ub_stride; const double *obj_offset;
+  int64_t obj_offset_stride; const double *row_compliance; int64_t row_compliance_stride; const double *x0; const double *y0; double *primal_weight;
+  double *x; double *y; double *obj; int32_t *status; int32_t *iters; int32_t *jumps; int32_t *flags;
+};
+struct KernelOptions {
+  double eps_rel; double eps_obj; int32_t max_iter; int32_t check_every; double restart_sufficient; double restart_necessary;
+  double restart_artificial; double pid_kp; double max_dlog_weight; double step_scale; double weight_guard; double jump_steady; double jump_tol;
+  double jump_min; int32_t ray_jumps; int32_t ruiz_iters; int32_t waves_per_block; int32_t kkt_every; int32_t no_matreg; int32_t geo_iters;
+  double kkt_gate; int32_t stall_rescue; int32_t no_simplex; double jump_rel; int32_t precision; int32_t polish_patience; int32_t no_rtc;
+  int32_t no_interior_point; double eps_infeasible; int32_t recertify_passes; int32_t simplex_warm; int32_t warm_patience;
+};
+static_assert(sizeof(KernelBatch) == __builtin_offsetof(dsp_batch, kkt), "KernelBatch is dsp_batch without its ABI 22 member");
+static_assert(sizeof(KernelOptions) == __builtin_offsetof(dsp_options, simplex_kkt_tol) && __builtin_offsetof(KernelOptions, warm_patience) == __builtin_offsetof(dsp_options, warm_patience),
+              "KernelOptions is dsp_options without its ABI 22 members");
+static_assert(__builtin_offsetof(KernelBatch, flags) == __builtin_offsetof(dsp_batch, flags) && __builtin_offsetof(KernelOptions, eps_infeasible) == __builtin_offsetof(dsp_options, eps_infeasible), "");
+#ifndef __HIPCC_RTC__
+inline KernelBatch prefix_of(const dsp_batch &b) { KernelBatch k; __builtin_memcpy(&k, &b, sizeof(k)); return k; }
+inline KernelOptions prefix_of(const dsp_options &o) { KernelOptions k; __builtin_memcpy(&k, &o, sizeof(k)); return k; }
+#endif
+
 // internal status written by the simplex kernel for scenarios it leaves to the PDLP kernel (never reaches the caller)
 #define DSP_STATUS_UNSOLVED 99
 // internal status of a register-resident solve kernel for a scenario whose objectives keep drifting apart (an LP without a solution is
@@ -73,14 +99,14 @@ struct DeviceProblem {
 
 struct SolveArgs {
   DeviceProblem P;
-  dsp_batch b;
+  KernelBatch b;
   int skip_solved;             // 1 = only scenarios whose status is DSP_STATUS_UNSOLVED are solved (after the simplex pass);
                                // 2 = only DSP_STATUS_SUSPECT ones, continued from the iterate in b.x / b.y (certificate pass)
                                // 3 = only OPTIMAL ones flagged DSP_FLAG_OBJ_WAIVED, from a cold start; results replace the earlier
                                //     ones only when certified (re-certification pass, dsp_options::recertify_passes)
   int waves_per_block;
   double eta;
-  dsp_options opt;
+  KernelOptions opt;
   int *queue;                  // device work-queue head of this launch (zeroed on the stream right before it)
   unsigned queue_base;         //   scenario = ticket - queue_base (0 since the heads are reset per launch)
   const int *unsolved;         // skip_solved: number of scenarios the simplex pass left unsolved (0 = nothing to do)
@@ -142,7 +168,7 @@ struct SimplexArgs {
   int max_pivots;
   const double *A_dense;       // [m][n] scaled matrix D_r A D_c, row-major
   const double *col_scale, *row_scale;
-  dsp_batch b;
+  KernelBatch b;
   double tol_p, tol_d, tol_piv;
   int *unsolved;               // incremented for every scenario left to the PDLP kernel
   int debug_keep;              // development (DSP_SX_DEBUG=1): status 51 / 52 instead of the hand-over
@@ -152,6 +178,12 @@ struct SimplexArgs {
   int *warm_basis;             // [B][m] variable of every row
   unsigned char *warm_upper;   // [B][n + m] 1 = nonbasic at its upper bound
   int *warm_valid;             // [B] 1 = the state above is that of a certified optimal vertex
+};
+
+// second argument of the certifying instantiations only (dsp_options::simplex_certify = 1): the plain kernels' argument block is SimplexArgs alone
+struct SimplexCertArgs {
+  double *kkt;                 // [B][4] or NULL: primal, dual_col, dual_row, gap of every vertex judged (dsp_batch::kkt)
+  double kkt_tol;              // all four numbers <= kkt_tol: certified
 };
 
 struct SpmvArgs {
@@ -175,7 +207,8 @@ hipError_t occupancy_solve(int cpl, int rpl, const SolveArgs &a, int block_threa
 int light_followup_blocks(int cpl, int rpl, const SolveArgs &first, size_t lds);
 hipError_t launch_solve_light(int cpl, int rpl, const SolveArgs &first, const SolveArgs &a, int grid, size_t lds, hipStream_t st);
 size_t simplex_lds_bytes(int n, int m, int *row_stride);
-hipError_t launch_simplex(const SimplexArgs &a, int grid, size_t lds, hipStream_t st);
+// cert: NULL = the plain kernels
+hipError_t launch_simplex(const SimplexArgs &a, const SimplexCertArgs *cert, int grid, size_t lds, hipStream_t st);
 // float32-iterate solve (dsp_qp.hip); returns the launch geometry it chose
 hipError_t launch_solve_f32(int cpl, int rpl, const SolveArgs &a, int num_cus, size_t lds_limit, hipStream_t st, int *grid,
                             int *threads, size_t *lds);

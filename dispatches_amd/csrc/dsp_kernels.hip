@@ -302,7 +302,7 @@ __global__ void __launch_bounds__(LIGHT ? 64 : (CPL + RPL >= DSP_ONE_WAVE_FROM &
   // generic kernel (skip_solved = 2), which continues from its iterate.  Feasible batches: that launch returns at the line above.
   constexpr bool CERT = !MATREG;
   const DeviceProblem &P = a.P;
-  const dsp_batch &b = a.b;
+  const KernelBatch &b = a.b;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform, and known to be)
 

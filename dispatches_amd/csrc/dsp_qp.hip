@@ -58,7 +58,7 @@ template <int CPL, int RPL>
 __global__ void __launch_bounds__(64 * kF32Waves) pdlp_solve_f32_kernel(SolveArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const DeviceProblem &P = a.P;
-  const dsp_batch &b = a.b;
+  const KernelBatch &b = a.b;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = P.n, m = P.m;
   Entry32 *ellc = reinterpret_cast<Entry32 *>(smem);                   // A^T  [Wc*CPL*64]

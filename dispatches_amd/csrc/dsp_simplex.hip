@@ -19,6 +19,8 @@
 // index), lane j owns column j's status.  All control flow is wave-uniform; reductions run on the VALU (DPP).
 // A solved LP is certified against the ORIGINAL rows before it is reported optimal; anything else (pivot limit,
 // failed certificate) is left to the PDLP kernel that runs afterwards on the scenarios still marked unsolved.
+// With dsp_options::simplex_certify = 1 (the kernels' CERT instantiations) the stored pair (x, y) also has to pass a full KKT
+// certificate against the original LP - dual feasibility and the duality gap included (KktAcc below).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -39,12 +41,110 @@ __device__ __forceinline__ double lds_d(const double *base, int idx) { return ba
 // lowest set lane of a wave-uniform 64-bit ballot
 __device__ __forceinline__ int first_lane(unsigned long long mask) { return __ffsll((long long)mask) - 1; }
 
+// ---- full KKT certificate of a stored pair (x, y) against the ORIGINAL LP (dsp_options::simplex_certify = 1) --------------
+// The pivot loop stops on reduced costs of the TABLEAU, and y is read off the tableau's slack columns: a tableau that drifted
+// (carried warm through the hours of a day without refactorisation) can stop at a feasible vertex that is not optimal, with
+// a y that prices nothing.  The CERT instantiations of the two kernels therefore check what they are about to store - x after
+// the refinement, y - against the data the caller gave: A_dense with the handle's scalings undone, c, the bounds and the row
+// sides.  Four numbers in the caller's units, the definitions of tests/_small_lp_cases.py::kkt_residuals and of
+// tools/simplex_proto.py::kkt_certificate, each relative to 1 + the largest magnitude among the numbers it compares:
+//   primal    lb <= x <= ub and rlo <= A x <= rhi (A x recomputed from x: the slack value is not read)
+//   dual_col  r = c - A'y: r_j > 0 needs a finite lb_j, r_j < 0 a finite ub_j
+//   dual_row  y_i > 0 needs a finite rlo_i, y_i < 0 a finite rhi_i
+//   gap       |c.x - (y+.rlo - y-.rhi + r+.lb - r-.ub)|, finite sides only
+// All four <= kkt_tol: (x, y) is a primal-dual optimal pair to that tolerance, whatever the tableau says.  What this does NOT
+// prove: that x is a vertex (a basic solution) - an optimal point in the relative interior of an optimal face passes as well.
+// Lane j (+ 64 q) contributes column j: a structural (x_j, c_j, (A'y)_j, its bounds) or the slack of row j - n ((A x)_i, y_i,
+// the row's sides); a NaN anywhere makes all four infinite.
+struct KktAcc {
+  double pv = 0.0, pm = 0.0, dcv = 0.0, dcm = 0.0, drv = 0.0, drm = 0.0, pobj = 0.0, dobj = 0.0;
+  bool nan = false;
+};
+
+__device__ __forceinline__ void kkt_column(KktAcc &k, double x, double c, double aty, double lb, double ub) {
+  const double r = c - aty;
+  const bool lf = is_finite(lb), uf = is_finite(ub);
+  k.pv = fmax(k.pv, fmax(lb - x, x - ub));
+  k.pm = fmax(k.pm, fmax(fabs(x), fmax(fabs(finite_or_zero(lb)), fabs(finite_or_zero(ub)))));
+  k.dcv = fmax(k.dcv, fmax(lf ? 0.0 : r, uf ? 0.0 : -r));
+  k.dcm = fmax(k.dcm, fmax(fabs(c), fabs(aty)));
+  k.pobj = fma(c, x, k.pobj);
+  k.dobj += fmax(r, 0.0) * finite_or_zero(lb) - fmax(-r, 0.0) * finite_or_zero(ub);
+  k.nan |= !(x == x) || !(r == r);
+}
+
+__device__ __forceinline__ void kkt_row(KktAcc &k, double ax, double y, double rlo, double rhi) {
+  const bool lf = is_finite(rlo), uf = is_finite(rhi);
+  k.pv = fmax(k.pv, fmax(rlo - ax, ax - rhi));
+  k.pm = fmax(k.pm, fmax(fabs(ax), fmax(fabs(finite_or_zero(rlo)), fabs(finite_or_zero(rhi)))));
+  k.drv = fmax(k.drv, fmax(lf ? 0.0 : y, uf ? 0.0 : -y));
+  k.drm = fmax(k.drm, fabs(y));
+  k.dobj += fmax(y, 0.0) * finite_or_zero(rlo) - fmax(-y, 0.0) * finite_or_zero(rhi);
+  k.nan |= !(ax == ax) || !(y == y);
+}
+
+// wave reductions -> primal, dual_col, dual_row, gap (wave-uniform); true when all four are within tol
+__device__ __forceinline__ bool kkt_finish(const KktAcc &k, double tol, double (&out)[4]) {
+  double mx[6] = {k.pv, k.pm, k.dcv, k.dcm, k.drv, k.drm};
+  wave_reduce<OpMax, 6>(mx);
+  double sm[2] = {k.pobj, k.dobj};
+  wave_sums<2>(sm);
+  out[0] = mx[0] / (1.0 + mx[1]);
+  out[1] = mx[2] / (1.0 + mx[3]);
+  out[2] = mx[4] / (1.0 + mx[5]);
+  out[3] = fabs(sm[0] - sm[1]) / (1.0 + fmax(fabs(sm[0]), fabs(sm[1])));
+  const bool any_nan = __ballot(k.nan) != 0ull;
+  bool ok = true;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (any_nan || !(out[e] == out[e])) out[e] = INFINITY;
+    ok = ok && out[e] <= tol;
+  }
+  return ok;
+}
+
+// duals of the LDS-tableau kernel: y_i = reduced cost of slack i with the phase-2 costs, through the kernel's LDS vectors
 template <int CQ>
-__global__ void __launch_bounds__(64, CQ == 1 ? 4 : 3) simplex_kernel(SimplexArgs a) {
+__device__ __forceinline__ void lds_duals(double (&dsl)[CQ], const double (&cost)[CQ], double *xval, double *cB_s, const double *T, int bvar, int lane,
+                                          int m, int N, int RS) {
+#pragma unroll
+  for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j < N) xval[j] = cost[q]; }
+  wave_lds_fence();
+  if (lane < m) cB_s[lane] = xval[bvar];
+  wave_lds_fence();
+#pragma unroll
+  for (int q = 0; q < CQ; ++q) dsl[q] = cost[q];
+#pragma unroll 4
+  for (int i = 0; i < m; ++i) {
+    const double cb = cB_s[i];
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j < N) dsl[q] = fma(-cb, T[i * RS + j], dsl[q]); }
+  }
+}
+
+// one of four wave-uniform numbers by lane id (lanes 0 .. 3 store the certificate)
+__device__ __forceinline__ double pick4(const double (&v)[4], int e) { return e == 0 ? v[0] : (e == 1 ? v[1] : (e == 2 ? v[2] : v[3])); }
+
+// what the CERT path carries from the certificate to the stores; empty in the plain instantiations, whose source is the kernels' as they were
+template <int CQ, bool CERT> struct CertState {};
+template <int CQ> struct CertState<CQ, true> {
+  double ax = 0.0;                                   // (A x)_i of row lane i, scaled
+  double y[CQ];                                      // the certified duals (scaled), stored afterwards
+  double kk[4] = {NAN, NAN, NAN, NAN};               // primal, dual_col, dual_row, gap; NaN: no vertex was judged
+};
+
+// second kernel argument: SimplexCertArgs in the certifying instantiations, an empty structure in the plain ones, whose argument block is
+// SimplexArgs as ever
+struct NoCertArgs {};
+template <bool CERT> struct CertArgsOf { using type = NoCertArgs; };
+template <> struct CertArgsOf<true> { using type = SimplexCertArgs; };
+
+template <int CQ, bool CERT>
+__global__ void __launch_bounds__(64, CQ == 1 ? 4 : 3) simplex_kernel(SimplexArgs a, typename CertArgsOf<CERT>::type ck) {
   // CQ == 1 (the 4-h wind + battery LPs, 20 x 54): 128 VGPRs and 9.5 KB of LDS -> 4 waves per SIMD, 16 per CU: a 4096-plant batch is ONE
   // round of waves over the 256 CUs (at 137 VGPRs / 14.6 KB it was 12 per CU, a full round and a quarter-full one)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const dsp_batch &b = a.b;
+  const KernelBatch &b = a.b;
   const int lane = threadIdx.x;
   const int n = a.n, m = a.m, N = n + m;
   const int RS = a.row_stride;                       // odd number of doubles per tableau row
@@ -110,6 +210,7 @@ __global__ void __launch_bounds__(64, CQ == 1 ? 4 : 3) simplex_kernel(SimplexArg
 #pragma unroll
       for (int q = 0; q < CQ; ++q) nanc |= !(cost[q] == cost[q]);
       const bool any_nan = __ballot(nanc) != 0ull;
+      if constexpr (CERT) { if (ck.kkt && lane < 4) ck.kkt[(size_t)s * 4 + lane] = NAN; }
       if (lane == 0) {
         b.obj[s] = NAN;
         b.status[s] = any_nan ? DSP_STATUS_NUMERICAL : DSP_STATUS_PRIMAL_INFEASIBLE;
@@ -435,23 +536,67 @@ __global__ void __launch_bounds__(64, CQ == 1 ? 4 : 3) simplex_kernel(SimplexArg
       if (j < n) po = fma(cost[q], xs[q], po);
     }
     po = wave_sum(po);
+    CertState<CQ, CERT> cs;
     {
       // row residuals with the ORIGINAL scaled matrix, sum_j a_ij x_j - s_i, against the scale of the whole vertex: the
       // basic values carry an ABSOLUTE drift of ~1e-11 x the largest number in the tableau (1e5 kWh states), which lands
       // on rows whose own terms may all be ~0 (seen: 4.9e-6 on such a row, 5e-11 of the state-of-charge scale).  The
       // certificate is there to catch a broken tableau, not rounding.
       // (a vertex that was refined and not pivoted on since: the residual BEFORE the correction is the statement about the tableau)
+      // (CERT: always the residual of the FINAL vertex, and (A x)_i on its own for the certificate below)
       double res = res_c, mag = mag_c;
-      if (lane < m && !res_valid) {
+      if (lane < m && (CERT || !res_valid)) {
         res = -xval[n + lane]; mag = fabs(xval[n + lane]);
 #pragma unroll 8
         for (int j = 0; j < n; ++j) {
           const double t = a.A_dense[(size_t)lane * n + j] * xval[j];
           res += t; mag += fabs(t);
+          if constexpr (CERT) cs.ax += t;
         }
       }
       const double gmag = wave_max(mag);
       if (lane < m && !(fabs(res) <= 1e-9 * (1.0 + gmag))) { okv = false; okr = false; }
+    }
+    if constexpr (CERT) {
+      if (status == DSP_STATUS_OPTIMAL) {
+        // the pair about to be stored against the original LP (see KktAcc): y through LDS to the column lanes (A'y, lane j walks
+        // column j of A_dense: consecutive across the wave) and (A x)_i from row lane i to the lane of slack n + i
+        wave_lds_fence();
+        lds_duals<CQ>(cs.y, cost, xval, cB_s, T, bvar, lane, m, N, RS);
+        wave_lds_fence();
+#pragma unroll
+        for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j >= n && j < N) xval[j] = cs.y[q]; }
+        if (lane < m) cB_s[lane] = cs.ax;
+        wave_lds_fence();
+        double aty[CQ];
+#pragma unroll
+        for (int q = 0; q < CQ; ++q) aty[q] = 0.0;
+#pragma unroll 4
+        for (int i = 0; i < m; ++i) {
+          const double yi = xval[n + i];
+#pragma unroll
+          for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j < n) aty[q] = fma(a.A_dense[(size_t)i * n + j], yi, aty[q]); }
+        }
+        KktAcc k;
+#pragma unroll
+        for (int q = 0; q < CQ; ++q) {
+          const int j = lane + 64 * q;
+          if (j < n) {
+            const double d = a.col_scale[j];
+            const double lu = b.var_lb ? b.var_lb[(size_t)s * b.var_lb_stride + j] : -INFINITY;
+            const double uu = b.var_ub ? b.var_ub[(size_t)s * b.var_ub_stride + j] : INFINITY;
+            kkt_column(k, xs[q] * d, b.c[(size_t)s * b.c_stride + j], aty[q] / d, lu, uu);
+          } else if (j < N) {
+            const int i = j - n;
+            const double d = a.row_scale[i];
+            const double l = b.row_lb ? b.row_lb[(size_t)s * b.row_lb_stride + i] : -INFINITY;
+            const double u = b.row_ub ? b.row_ub[(size_t)s * b.row_ub_stride + i] : INFINITY;
+            kkt_row(k, cB_s[i] / d, cs.y[q] * d, l, u);
+          }
+        }
+        if (!kkt_finish(k, ck.kkt_tol, cs.kk)) okv = false;
+        wave_lds_fence();
+      }
     }
     const bool certified = __ballot(!okv) == 0ull;
     const unsigned long long bad_bounds = __ballot(!okb), bad_any = __ballot(!okv);
@@ -462,6 +607,8 @@ __global__ void __launch_bounds__(64, CQ == 1 ? 4 : 3) simplex_kernel(SimplexArg
       wave_lds_fence();
       goto restart;
     }
+    // the certificate's numbers of every vertex judged, accepted or not; NaNs where the solve ended without one
+    if constexpr (CERT) { if (ck.kkt && lane < 4) ck.kkt[(size_t)s * 4 + lane] = pick4(cs.kk, lane); }
     if (a.warm) {
       // the final basis for the next solve of this scenario (only a certified optimum is worth starting from)
       const bool keep = status == DSP_STATUS_OPTIMAL && certified;
@@ -520,19 +667,24 @@ __global__ void __launch_bounds__(64, CQ == 1 ? 4 : 3) simplex_kernel(SimplexArg
       continue;
     }
     // duals: y_i = reduced cost of slack i with the phase-2 costs (recomputed so that a phase-1 stop reports something sane)
-#pragma unroll
-    for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j < N) xval[j] = cost[q]; }
-    wave_lds_fence();
-    if (lane < m) cB_s[lane] = xval[bvar];
-    wave_lds_fence();
     double dsl[CQ];
+    if constexpr (CERT) {                                    // the y that was certified
 #pragma unroll
-    for (int q = 0; q < CQ; ++q) dsl[q] = cost[q];
+      for (int q = 0; q < CQ; ++q) dsl[q] = cs.y[q];
+    } else {
+#pragma unroll
+      for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j < N) xval[j] = cost[q]; }
+      wave_lds_fence();
+      if (lane < m) cB_s[lane] = xval[bvar];
+      wave_lds_fence();
+#pragma unroll
+      for (int q = 0; q < CQ; ++q) dsl[q] = cost[q];
 #pragma unroll 4
-    for (int i = 0; i < m; ++i) {
-      const double cb = cB_s[i];
+      for (int i = 0; i < m; ++i) {
+        const double cb = cB_s[i];
 #pragma unroll
-      for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j < N) dsl[q] = fma(-cb, T[i * RS + j], dsl[q]); }
+        for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j < N) dsl[q] = fma(-cb, T[i * RS + j], dsl[q]); }
+      }
     }
 #pragma unroll
     for (int q = 0; q < CQ; ++q) {
@@ -545,7 +697,7 @@ __global__ void __launch_bounds__(64, CQ == 1 ? 4 : 3) simplex_kernel(SimplexArg
       b.status[s] = status;
       if (b.iters) b.iters[s] = pivots;
       if (b.jumps) b.jumps[s] = 0;
-      if (b.flags) b.flags[s] = 0;
+      if (b.flags) b.flags[s] = CERT ? DSP_FLAG_SIMPLEX_KKT : 0;
     }
     wave_lds_fence();
   }
@@ -573,10 +725,11 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 
-template <int CQ, int MR>
-__global__ void __launch_bounds__(64, 2) simplex_reg_kernel(SimplexArgs a) {
+template <int CQ, int MR, bool CERT>
+__global__ void __launch_bounds__(64, 2) simplex_reg_kernel(SimplexArgs a, typename CertArgsOf<CERT>::type ck) {
+  static_assert(!CERT || CQ == 1, "the certificate keeps (A x) in the upper half of xval: n + m <= 64");
   __shared__ double xval[128];                       // value (or cost) of every variable: vertex assembly / certificate
-  const dsp_batch &b = a.b;
+  const KernelBatch &b = a.b;
   const int lane = threadIdx.x;
   const int n = a.n, m = a.m, N = n + m;
 
@@ -623,6 +776,7 @@ __global__ void __launch_bounds__(64, 2) simplex_reg_kernel(SimplexArgs a) {
 #pragma unroll
       for (int q = 0; q < CQ; ++q) nanc |= !(cost[q] == cost[q]);
       const bool any_nan = __ballot(nanc) != 0ull;
+      if constexpr (CERT) { if (ck.kkt && lane < 4) ck.kkt[(size_t)s * 4 + lane] = NAN; }
       if (lane == 0) {
         b.obj[s] = NAN;
         b.status[s] = any_nan ? DSP_STATUS_NUMERICAL : DSP_STATUS_PRIMAL_INFEASIBLE;
@@ -889,11 +1043,13 @@ __global__ void __launch_bounds__(64, 2) simplex_reg_kernel(SimplexArgs a) {
       if (j < n) po = fma(cost[q], xs[q], po);
     }
     po = wave_sum(po);
+    CertState<CQ, CERT> cs;
     {
       // row residuals with the ORIGINAL scaled matrix, sum_j a_ij x_j - s_i, against the scale of the whole vertex (see the
       // LDS-tableau kernel): coalesced row loads + wave reductions, four rows at a time
       double res = 0.0, mag = 0.0;
       for (int i0 = 0; i0 < m; i0 += 2) {
+        // (CERT: (A x)_i on its own as well, for the certificate below)
         double part[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -909,11 +1065,65 @@ __global__ void __launch_bounds__(64, 2) simplex_reg_kernel(SimplexArgs a) {
         wave_sums<4>(part);
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-          if (lane == i0 + u) { res = part[2 * u] - xval[n + lane]; mag = part[2 * u + 1] + fabs(xval[n + lane]); }
+          if (lane == i0 + u) {
+            res = part[2 * u] - xval[n + lane]; mag = part[2 * u + 1] + fabs(xval[n + lane]);
+            if constexpr (CERT) cs.ax = part[2 * u];
+          }
       }
       const double gmag = wave_max(mag);
       if (lane < m && !(fabs(res) <= 1e-9 * (1.0 + gmag))) { okv = false; okr = false; }
     }
+    if constexpr (CERT) {
+      if (status == DSP_STATUS_OPTIMAL) {
+        // the pair about to be stored against the original LP (KktAcc, above the LDS-tableau kernel): y in xval[n .. N), where the
+        // column lanes read it for A'y (coalesced rows of A_dense), (A x)_i in the free upper half of xval for the lane of slack n + i
+        {
+#pragma unroll
+          for (int q = 0; q < CQ; ++q) cs.y[q] = cost[q];
+          const double cb2 = (lane < m) ? cbas : 0.0;
+#pragma unroll
+          for (int i = 0; i < MR; ++i) {
+            const double cb = readlane_f64(cb2, i);
+#pragma unroll
+            for (int q = 0; q < CQ; ++q) cs.y[q] = fma(-cb, T[i][q], cs.y[q]);
+          }
+        }
+        wave_lds_fence();
+#pragma unroll
+        for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j >= n && j < N) xval[j] = cs.y[q]; }
+        if (lane < m) xval[64 + lane] = cs.ax;
+        wave_lds_fence();
+        double aty[CQ];
+#pragma unroll
+        for (int q = 0; q < CQ; ++q) aty[q] = 0.0;
+#pragma unroll 4
+        for (int i = 0; i < m; ++i) {
+          const double yi = xval[n + i];
+#pragma unroll
+          for (int q = 0; q < CQ; ++q) { const int j = lane + 64 * q; if (j < n) aty[q] = fma(a.A_dense[(size_t)i * n + j], yi, aty[q]); }
+        }
+        KktAcc k;
+#pragma unroll
+        for (int q = 0; q < CQ; ++q) {
+          const int j = lane + 64 * q;
+          if (j < n) {
+            const double d = a.col_scale[j];
+            const double lu = b.var_lb ? b.var_lb[(size_t)s * b.var_lb_stride + j] : -INFINITY;
+            const double uu = b.var_ub ? b.var_ub[(size_t)s * b.var_ub_stride + j] : INFINITY;
+            kkt_column(k, xs[q] * d, b.c[(size_t)s * b.c_stride + j], aty[q] / d, lu, uu);
+          } else if (j < N) {
+            const int i = j - n;
+            const double d = a.row_scale[i];
+            const double l = b.row_lb ? b.row_lb[(size_t)s * b.row_lb_stride + i] : -INFINITY;
+            const double u = b.row_ub ? b.row_ub[(size_t)s * b.row_ub_stride + i] : INFINITY;
+            kkt_row(k, xval[64 + i] / d, cs.y[q] * d, l, u);
+          }
+        }
+        if (!kkt_finish(k, ck.kkt_tol, cs.kk)) okv = false;
+        wave_lds_fence();
+      }
+    }
+    if constexpr (CERT) { if (ck.kkt && lane < 4) ck.kkt[(size_t)s * 4 + lane] = pick4(cs.kk, lane); }
     const bool certified = __ballot(!okv) == 0ull;
     const unsigned long long bad_bounds = __ballot(!okb), bad_any = __ballot(!okv);
     int reason = status == -1 ? 1 : 0;
@@ -953,14 +1163,19 @@ __global__ void __launch_bounds__(64, 2) simplex_reg_kernel(SimplexArgs a) {
     }
     // duals: y_i = reduced cost of slack i with the phase-2 costs
     double dsl[CQ];
+    if constexpr (CERT) {                                    // the y that was certified
 #pragma unroll
-    for (int q = 0; q < CQ; ++q) dsl[q] = cost[q];
-    const double cb2 = (lane < m) ? cbas : 0.0;
+      for (int q = 0; q < CQ; ++q) dsl[q] = cs.y[q];
+    } else {
 #pragma unroll
-    for (int i = 0; i < MR; ++i) {
-      const double cb = readlane_f64(cb2, i);
+      for (int q = 0; q < CQ; ++q) dsl[q] = cost[q];
+      const double cb2 = (lane < m) ? cbas : 0.0;
 #pragma unroll
-      for (int q = 0; q < CQ; ++q) dsl[q] = fma(-cb, T[i][q], dsl[q]);
+      for (int i = 0; i < MR; ++i) {
+        const double cb = readlane_f64(cb2, i);
+#pragma unroll
+        for (int q = 0; q < CQ; ++q) dsl[q] = fma(-cb, T[i][q], dsl[q]);
+      }
     }
 #pragma unroll
     for (int q = 0; q < CQ; ++q) {
@@ -973,7 +1188,7 @@ __global__ void __launch_bounds__(64, 2) simplex_reg_kernel(SimplexArgs a) {
       b.status[s] = status;
       if (b.iters) b.iters[s] = pivots;
       if (b.jumps) b.jumps[s] = 0;
-      if (b.flags) b.flags[s] = 0;
+      if (b.flags) b.flags[s] = CERT ? DSP_FLAG_SIMPLEX_KKT : 0;
     }
     wave_lds_fence();
   }
@@ -989,19 +1204,21 @@ size_t simplex_lds_bytes(int n, int m, int *row_stride) {
   return ((size_t)m * rs + mp + mp + Np + 8 + 8) * sizeof(double);
 }
 
-hipError_t launch_simplex(const SimplexArgs &a, int grid, size_t lds, hipStream_t st) {
+hipError_t launch_simplex(const SimplexArgs &a, const SimplexCertArgs *cert, int grid, size_t lds, hipStream_t st) {
   const int cq = (a.n + a.m + 63) / 64;
   if (cq > 2) return hipErrorInvalidValue;
   SimplexArgs args = a;
-  void *params[] = {&args};
+  SimplexCertArgs cargs = cert ? *cert : SimplexCertArgs{};
+  NoCertArgs none;
+  void *params[] = {&args, cert ? static_cast<void *>(&cargs) : static_cast<void *>(&none)};
   // register-resident tableau where the rows fit (DSP_SX_LDS=1 forces the LDS-tableau kernel: development / comparison)
   static const int force_lds = getenv("DSP_SX_LDS") ? atoi(getenv("DSP_SX_LDS")) : 0;
   if (!force_lds && !a.warm && a.m <= 24 && cq <= 1 && a.b.B <= 2048) {       // (the warm start lives in the LDS-tableau kernel)
-    const void *fr = reinterpret_cast<const void *>(&simplex_reg_kernel<1, 24>);
+    const void *fr = cert ? reinterpret_cast<const void *>(&simplex_reg_kernel<1, 24, true>) : reinterpret_cast<const void *>(&simplex_reg_kernel<1, 24, false>);
     return hipLaunchKernel(fr, dim3(a.b.B < grid ? a.b.B : grid), dim3(64), params, 0, st);
   }
-  const void *fn = cq <= 1 ? reinterpret_cast<const void *>(&simplex_kernel<1>)
-                           : reinterpret_cast<const void *>(&simplex_kernel<2>);
+  const void *fn = cq <= 1 ? (cert ? reinterpret_cast<const void *>(&simplex_kernel<1, true>) : reinterpret_cast<const void *>(&simplex_kernel<1, false>))
+                           : (cert ? reinterpret_cast<const void *>(&simplex_kernel<2, true>) : reinterpret_cast<const void *>(&simplex_kernel<2, false>));
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   return hipLaunchKernel(fn, dim3(grid), dim3(64), params, lds, st);

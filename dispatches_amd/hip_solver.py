@@ -29,7 +29,8 @@ class DspOptions(C.Structure):
                 ("waves_per_block", C.c_int32), ("kkt_every", C.c_int32), ("no_matreg", C.c_int32), ("geo_iters", C.c_int32),
                 ("kkt_gate", C.c_double), ("stall_rescue", C.c_int32), ("no_simplex", C.c_int32),
                 ("jump_rel", C.c_double), ("precision", C.c_int32), ("polish_patience", C.c_int32), ("no_rtc", C.c_int32), ("no_interior_point", C.c_int32),
-                ("eps_infeasible", C.c_double), ("recertify_passes", C.c_int32), ("simplex_warm", C.c_int32), ("warm_patience", C.c_int32)]
+                ("eps_infeasible", C.c_double), ("recertify_passes", C.c_int32), ("simplex_warm", C.c_int32), ("warm_patience", C.c_int32),
+                ("simplex_certify", C.c_int32), ("simplex_kkt_tol", C.c_double)]
 
 
 class DspBatch(C.Structure):
@@ -44,7 +45,8 @@ class DspBatch(C.Structure):
                 ("row_compliance", C.c_void_p), ("row_compliance_stride", C.c_int64),
                 ("x0", C.c_void_p), ("y0", C.c_void_p), ("primal_weight", C.c_void_p),
                 ("x", C.c_void_p), ("y", C.c_void_p), ("obj", C.c_void_p),
-                ("status", C.c_void_p), ("iters", C.c_void_p), ("jumps", C.c_void_p), ("flags", C.c_void_p)]
+                ("status", C.c_void_p), ("iters", C.c_void_p), ("jumps", C.c_void_p), ("flags", C.c_void_p),
+                ("kkt", C.c_void_p)]
 
 
 class DspStats(C.Structure):
@@ -54,7 +56,7 @@ class DspStats(C.Structure):
                 ("matreg", C.c_int32), ("lds_conflicts_identity", C.c_int32), ("lds_conflicts_chosen", C.c_int32),
                 ("simplex", C.c_int32), ("streaming", C.c_int32), ("stream_bytes_per_iteration", C.c_int64),
                 ("quadratic", C.c_int32), ("precision", C.c_int32), ("rtc", C.c_int32), ("stream_form", C.c_int32), ("stream_phases", C.c_int32),
-                ("ipm_solved", C.c_int32), ("reserved1", C.c_int32)]
+                ("ipm_solved", C.c_int32), ("simplex_unsolved", C.c_int32)]
 
 
 class DspLpDesc(C.Structure):
@@ -112,7 +114,7 @@ EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_
                     "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare", "dsp_loop_ledger", "dsp_loop_record")
 
 
-ABI_VERSION = 21        # DSP_VERSION of the include/dsp_hip.h these structures mirror
+ABI_VERSION = 22       # DSP_VERSION of the include/dsp_hip.h these structures mirror
 
 
 BID_MAX_HOURS, BID_MAX_SCENARIOS = 64, 16384
@@ -408,8 +410,10 @@ class DeviceLP:
         return t.data_ptr(), width
 
     def solve(self, B, c, lb=None, ub=None, rlo=None, rhi=None, x0=None, y0=None, options=None, out=None,
-              sync_stats=True, obj_offset=None, primal_weight=None, row_compliance=None):
+              sync_stats=True, obj_offset=None, primal_weight=None, row_compliance=None, kkt=None):
         """All arguments are CUDA(HIP) float64 torch tensors; returns dict of output tensors (+ stats).
+        kkt: a [B, 4] buffer handed to dsp_batch::kkt as it is, whatever the options say (dsp_solve refuses it without
+        simplex_certify); normally left None: the options in force decide, and the certificates come back as out["kkt"].
         obj_offset: [B] objective constants (scale of the eps_obj tests); primal_weight: [B] in/out;
         row_compliance: [m] or [B, m] compliances of the soft rows (convex QP, dsp_batch::row_compliance)."""
         import torch
@@ -445,6 +449,15 @@ class DeviceLP:
         bt.status, bt.iters = out["status"].data_ptr(), out["iters"].data_ptr()
         bt.jumps = out["jumps"].data_ptr() if "jumps" in out else None
         bt.flags = out["flags"].data_ptr() if "flags" in out else None
+        # the in-wave simplex' KKT certificate (dsp_options::simplex_certify): [B, 4] primal, dual_col, dual_row, gap
+        # (an `out` that carries a buffer from an earlier certified call is passed on only while the options in force ask for it)
+        used = options if options is not None else self.options
+        if used is not None and used.simplex_certify == 1:
+            if "kkt" not in out:
+                out["kkt"] = torch.full((B, 4), float("nan"), dtype=torch.float64, device=dev)
+            bt.kkt = out["kkt"].data_ptr()
+        if kkt is not None:
+            bt.kkt = kkt.data_ptr()
         stats = DspStats()
         stream = torch.cuda.current_stream(dev).cuda_stream
         rc = self.lib.dsp_solve(self.handle, C.byref(bt), C.byref(options) if options is not None else None,
@@ -488,6 +501,7 @@ def period_shift_maps(lp, shift: int):
 
 
 FLAG_OBJ_WAIVED = 1          # DSP_FLAG_OBJ_WAIVED of include/dsp_hip.h
+FLAG_SIMPLEX_KKT = 8         # DSP_FLAG_SIMPLEX_KKT: solved by the in-wave simplex, (x, y) passed the KKT certificate against the original LP
 STATUS_PRIMAL_INFEASIBLE, STATUS_DUAL_INFEASIBLE = 2, 3      # DSP_STATUS_* of include/dsp_hip.h
 STATUS_UNCERTIFIED = 5       # host-side report code (Bidder.failed_scenarios, Tracker): the kernel said OPTIMAL with
                              # DSP_FLAG_OBJ_WAIVED set and no re-solve certified the objective accuracy either
@@ -714,7 +728,7 @@ class HipPdlpSolver:
             return h
 
         lazy = self.lazy_solution and getattr(model, "supports_lazy_solution", False)
-        host = {k: down(out[k]) for k in ("obj", "status", "iters", "jumps", "flags") + (() if lazy else ("x", "y"))}
+        host = {k: down(out[k]) for k in ("obj", "status", "iters", "jumps", "flags") + (() if lazy else ("x", "y")) + (("kkt",) if "kkt" in out else ())}
         host["pw"] = down(pw)
         torch.cuda.current_stream(dev).synchronize()
         status = host["status"].numpy()
@@ -734,6 +748,8 @@ class HipPdlpSolver:
         model.jumps = host["jumps"].numpy()
         model.flags = host["flags"].numpy()      # DSP_FLAG_* bits AFTER the re-solves (bit 1 left = objective accuracy not certified)
         model.uncertified = uncertified(status, model.flags)
+        if "kkt" in host:                        # simplex_certify=1: the in-wave simplex' certificate [B, 4] (NaN rows: no vertex of its own)
+            model.kkt = host["kkt"].numpy()
         model.primal_weight = host["pw"].numpy()
         if tee:
             print(f"[dsp_hip] B={B} n={model.lp.n} m={model.lp.m} nnz={model.lp.nnz} optimal={st.n_optimal}/{B} "

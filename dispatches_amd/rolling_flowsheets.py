@@ -128,7 +128,7 @@ def _dense_rows(block, family, n, hours):
 class _Model:
     """One of the three LPs on the device, described without reference to a flowsheet."""
 
-    def __init__(self, model, block_family, B, dev, device_index, power_output, state_init, wind, lp_backend=None, solved=True):
+    def __init__(self, model, block_family, B, dev, device_index, power_output, state_init, wind, lp_backend=None, solved=True, simplex_certify=False):
         import torch
         self.lp = model.lp
         self.T = len(model.HOUR)
@@ -155,7 +155,7 @@ class _Model:
             cols, kw, per_kw, template_sum = wind
             self.wind = (idx(cols), float(kw), float(per_kw))
             self.base_c0 -= float(per_kw) * float(template_sum)           # the template's curtailment constant leaves; the window's enters
-        attach_solver(self, B, dev, device_index, getattr(model, "solver_hints", None), lp_backend, solved)      # (solved=False: parametrized mode never solves its bidding templates)
+        attach_solver(self, B, dev, device_index, getattr(model, "solver_hints", None), lp_backend, solved, simplex_certify)      # (solved=False: parametrized mode never solves its bidding templates)
 
     def couple(self, model, S, B, dev, device_index, lp_backend, mode="non_anticipative"):
         """-> the COUPLED day-ahead model of a batch built on this one-row block model (of `model`, the day-ahead template): B rows of
@@ -477,7 +477,7 @@ class BatchedDoubleLoop(_DeviceLoop):
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
                  market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
                  battery_mwh=None, ruc_hour=None, scenario_coupling="independent", ledger=False, pem_mw=None, tank_kg=None,
-                 h2_price=None, h2_demand=None, record=None, record_max_bytes=2 ** 30):
+                 h2_price=None, h2_demand=None, record=None, record_max_bytes=2 ** 30, simplex_certify=False):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -525,6 +525,12 @@ class BatchedDoubleLoop(_DeviceLoop):
         stochastic mode's.  The day-ahead step replays from a graph where the coupled LP stays in the fused kernels, as the
         self-schedule's.  Refused (ValueError): another value, bidder other than "lp", ruc_hour, per-plant sizes, bid_price /
         storage_mw, forecaster="perfect", n_price_scenarios=1 (no pairs: that is the independent loop).
+        simplex_certify: False (the loops above: same launches, same bits) or True: every model of at most 16 periods - the real-time
+        model, the tracker, the projection tracker - is solved under dsp_options::simplex_certify = 1, also in its first-hour / warm
+        option copies: the in-wave simplex stores an optimum only after the stored (x, y) passed the KKT certificate against the
+        original LP (primal, dual_col, dual_row, gap <= 1e-9; include/dsp_hip.h) and flags it DSP_FLAG_SIMPLEX_KKT; a vertex it
+        rejects is solved by the PDLP pass of the same call, whose status and flags feed `bad` / `uncertified` as ever.  No kernel of
+        the loop changes; each such model's out["kkt"] [rows, 4] holds the last solve's certificates.
         ledger: False (the loops above: same launches, same bits) or True: every implemented hour is BOOKED per plant, after the tracking
         solve and before the hand-off, from the tracker's solution of its period 0 - tot_cost [$] (the flowsheet's own tot_cost[0], its
         constant at this hour's capacity factor and this plant's wind size; nuclear: the hydrogen credit included), under_mwh / over_mwh
@@ -614,7 +620,8 @@ class BatchedDoubleLoop(_DeviceLoop):
             f = getattr(model.block, fam)
             cols = [p["wind"].index for p in f["periods"]]
             return cols, f["wind_kw"], d["per_kw"], f["wind_kw"] * float(np.sum(cf_s[:len(cols)]))
-        mk = lambda model, nb, solved=True: _Model(model, fam, nb, dev, device, power, d["init"](model.block), wind_of(model), lp_backend, solved)
+        self.simplex_certify = bool(simplex_certify) and lp_backend is None      # hourly LPs under dsp_options::simplex_certify = 1 (attach_solver)
+        mk = lambda model, nb, solved=True: _Model(model, fam, nb, dev, device, power, d["init"](model.block), wind_of(model), lp_backend, solved, self.simplex_certify)
         if self.coupled_da:                           # ONE coupled day-ahead LP per plant (module docstring)
             self.da_block = mk(da_model, 1, False)
             self.da_block.pda_cols = idx(da_model.pda_cols)

@@ -48,7 +48,7 @@
 extern "C" {
 #endif
 
-#define DSP_VERSION 21
+#define DSP_VERSION 22
 
 /* return codes (0 = ok, < 0 = API misuse / HIP error; text via dsp_strerror) */
 #define DSP_OK                 0
@@ -83,6 +83,8 @@ extern "C" {
                                      typically objectives that are the small difference of terms ~1e3-1e6 times larger   */
 #define DSP_FLAG_STALL_RESCUE 2   /* the primal weight was reset once by the stall rescue                              */
 #define DSP_FLAG_POLISH       4   /* the weight guard was tightened in the polish phase (dsp_options::polish_patience) */
+#define DSP_FLAG_SIMPLEX_KKT  8   /* ABI 22: status OPTIMAL from the in-wave simplex, and the stored (x, y) passed the full KKT certificate
+                                     against the ORIGINAL LP at dsp_options::simplex_kkt_tol (dsp_options::simplex_certify = 1) */
 
 typedef struct dsp_handle dsp_handle;
 
@@ -235,6 +237,22 @@ typedef struct dsp_options {
                                 (3650 -> 2244 iterations) but a few scenarios per thousand do far worse from yesterday's point than from
                                 zero - one plant-day in 16 384 ran into the iteration limit; with a patience of ~1.5 x the cold mean their cost
                                 is bounded by patience + a cold solve.  0 = off                                           default 0    */
+  int32_t simplex_certify;   /* in-wave simplex (ABI 22): 0 = a vertex the pivot loop calls optimal is checked against its bounds and the original
+                                rows (the residual taken before the last refinement of the basic values); its reduced costs and duals are the
+                                tableau's.  1 = before status 0 is stored, the stored pair (x after refinement, y) passes a full KKT
+                                certificate computed from the ORIGINAL data only - the scaled matrix, the handle's scalings, the caller's c,
+                                bounds and row sides; the tableau is used to read y off its slack columns and for nothing else.  Four
+                                numbers in the caller's units, each relative to 1 + the largest magnitude it compares (dsp_batch::kkt):
+                                  primal    bounds and row_lb <= A x <= row_ub at the stored x (A x recomputed, the slack value is not read)
+                                  dual_col  sign conditions of r = c - A'y against the finite sides of var_lb / var_ub
+                                  dual_row  sign conditions of y against the finite sides of row_lb / row_ub
+                                  gap       |c.x - (y+.row_lb - y-.row_ub + r+.var_lb - r-.var_ub)| over the finite sides
+                                all four <= simplex_kkt_tol: status 0 and DSP_FLAG_SIMPLEX_KKT.  Otherwise the paths of a failed row
+                                certificate: after a warm start once more from the slack basis; from the slack basis no basis is kept and
+                                the PDLP pass takes the scenario and reports its own status and flags.  The row check then uses the
+                                residual of the final vertex too.  It proves that (x, y) is optimal to the tolerance; it does NOT prove
+                                that x is a vertex (basic) solution                                                       default 0    */
+  double  simplex_kkt_tol;   /* tolerance of the four numbers above; 0 = 1e-9, the level of the row certificate        default 0    */
 } dsp_options;
 
 /* The per-call data of B scenarios.  c is required; every other input may be NULL (= no bound: -inf / +inf,
@@ -271,6 +289,10 @@ typedef struct dsp_batch {
   int32_t *iters;           /* [B] or NULL   iterations used                                        */
   int32_t *jumps;           /* [B] or NULL   ray jumps taken                                        */
   int32_t *flags;           /* [B] or NULL   DSP_FLAG_* bits of the scenario's solve                */
+  double  *kkt;             /* [B][4] or NULL (ABI 22, needs dsp_options::simplex_certify = 1): primal, dual_col, dual_row, gap of
+                               the in-wave simplex' certificate for every scenario it gave a verdict on - those it rejected and
+                               left to the PDLP pass included, which does not touch them -, four NaNs where it ended without a
+                               vertex (NaN input, crossed bounds, pivot limit, phase-1 stops, empty ratio tests) or did not run */
 } dsp_batch;
 
 /* Aggregate statistics of one dsp_solve call (filled after the call's stream work completes when
@@ -307,7 +329,7 @@ typedef struct dsp_stats {
                                      ipm_solved < B: the others (given up on: an LP without a solution, a breakdown) were handed - they
                                      alone, packed into as few lane groups as they need - to the PDHG forms, whose statuses and
                                      certificates they carry; iters[] counts Newton iterations for the former, PDHG iterations for the latter */
-  int32_t reserved1;
+  int32_t simplex_unsolved;       /* ABI 22 (was reserved): scenarios the in-wave simplex pass left to the PDLP pass (sync_stats only) */
 } dsp_stats;
 
 /* dsp_stats::stream_form */

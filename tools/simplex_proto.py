@@ -26,8 +26,43 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 BIG = 1e300
 
 
-def simplex_batch(A, c, lb, ub, rlo, rhi, max_pivots=None, tol_p=1e-9, tol_d=1e-9, tol_piv=1e-9):
-    """A [m, n] dense (shared), c/lb/ub [B, n], rlo/rhi [B, m].  Returns x [B, n], y [B, m], status [B], pivots [B]."""
+def kkt_certificate(A, c, lb, ub, rlo, rhi, x, y):
+    """The kernels' KKT certificate (csrc/dsp_simplex.hip, CERT instantiations; dsp_options::simplex_certify) of the pairs (x, y), in
+    double and in the kernels' order of operations: one fused pass per column (x_j, c_j, (A'y)_j, bounds) and per row ((A x)_i, y_i,
+    sides), maxima and the two objectives reduced over all of them.  A [m, n], c/lb/ub/x [B, n], rlo/rhi/y [B, m] -> [B, 4]:
+    primal, dual_col, dual_row, gap - the definitions of tests/_small_lp_cases.py::kkt_residuals (there in long double), each relative to
+    1 + the largest magnitude it compares; a NaN anywhere makes a scenario's four numbers inf.
+    What it proves: (x, y) is a primal-dual optimal pair to the tolerance it is held against.  What it does not: that x is a vertex."""
+    A, c, lb, ub, rlo, rhi, x, y = (np.asarray(v, float) for v in (A, c, lb, ub, rlo, rhi, x, y))
+    fin = lambda v: np.where(np.isfinite(v), v, 0.0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ax, aty = x @ A.T, y @ A
+        r = c - aty
+        # columns
+        pv = np.maximum(0.0, np.fmax(lb - x, x - ub)).max(1, initial=0.0)
+        pm = np.fmax(np.abs(x), np.fmax(np.abs(fin(lb)), np.abs(fin(ub)))).max(1, initial=0.0)
+        dcv = np.fmax(0.0, np.fmax(np.where(np.isfinite(lb), 0.0, r), np.where(np.isfinite(ub), 0.0, -r))).max(1, initial=0.0)
+        dcm = np.fmax(np.abs(c), np.abs(aty)).max(1, initial=0.0)
+        pobj = (c * x).sum(1)
+        dobj = (np.fmax(r, 0.0) * fin(lb) - np.fmax(-r, 0.0) * fin(ub)).sum(1)
+        # rows
+        pv = np.fmax(pv, np.fmax(0.0, np.fmax(rlo - ax, ax - rhi)).max(1, initial=0.0))
+        pm = np.fmax(pm, np.fmax(np.abs(ax), np.fmax(np.abs(fin(rlo)), np.abs(fin(rhi)))).max(1, initial=0.0))
+        drv = np.fmax(0.0, np.fmax(np.where(np.isfinite(rlo), 0.0, y), np.where(np.isfinite(rhi), 0.0, -y))).max(1, initial=0.0)
+        drm = np.abs(y).max(1, initial=0.0)
+        dobj = dobj + (np.fmax(y, 0.0) * fin(rlo) - np.fmax(-y, 0.0) * fin(rhi)).sum(1)
+        out = np.stack([pv / (1.0 + pm), dcv / (1.0 + dcm), drv / (1.0 + drm),
+                        np.abs(pobj - dobj) / (1.0 + np.fmax(np.abs(pobj), np.abs(dobj)))], 1)
+    bad = np.isnan(x).any(1) | np.isnan(r).any(1) | np.isnan(ax).any(1) | np.isnan(y).any(1) | np.isnan(out).any(1)
+    out[bad] = np.inf
+    return out
+
+
+def simplex_batch(A, c, lb, ub, rlo, rhi, max_pivots=None, tol_p=1e-9, tol_d=1e-9, tol_piv=1e-9, certify=False, kkt_tol=1e-9):
+    """A [m, n] dense (shared), c/lb/ub [B, n], rlo/rhi [B, m].  Returns x [B, n], y [B, m], status [B], pivots [B].
+    certify=True (dsp_options::simplex_certify = 1): an optimum whose (x, y) does not pass kkt_certificate at kkt_tol gets status 4 -
+    the kernels hand such a scenario to the PDLP pass - and the certificates [B, 4] are returned as a fifth value (NaN rows where the
+    solve ended without a vertex); x, y and the pivot counts are what certify=False returns."""
     m, n = A.shape
     B = c.shape[0]
     N = n + m
@@ -47,7 +82,7 @@ def simplex_batch(A, c, lb, ub, rlo, rhi, max_pivots=None, tol_p=1e-9, tol_d=1e-
     is_basic = np.zeros((B, N), bool); is_basic[:, n:] = True
     beta = val[:, :n] @ A.T                                              # s = A x_N
     val[:, n:] = beta
-    status = np.full(B, -1)             # -1 running, 0 optimal, 1 pivot limit, 2 infeasible, 3 unbounded
+    status = np.full(B, -1)             # -1 running, 0 optimal, 1 pivot limit, 2 infeasible, 3 unbounded, 4 optimal but not certified (certify)
     pivots = np.zeros(B, int)
     rows = np.arange(B)
     ctol = tol_d * (1.0 + np.abs(c).max(1))
@@ -136,6 +171,12 @@ def simplex_batch(A, c, lb, ub, rlo, rhi, max_pivots=None, tol_p=1e-9, tol_d=1e-
     cB = np.take_along_axis(cost, basis, 1)
     d = cost - np.einsum("bi,bij->bj", cB, T)
     y = d[:, n:]                                                         # multiplier of row i = reduced cost of its slack
+    if certify:
+        kkt = np.full((B, 4), np.nan)
+        opt = status == 0
+        kkt[opt] = kkt_certificate(A, c[opt], lb[opt], ub[opt], rlo[opt], rhi[opt], x[opt, :n], y[opt])
+        status = np.where(opt & ~(kkt <= kkt_tol).all(1), 4, status)
+        return x[:, :n], y, status, pivots, kkt
     return x[:, :n], y, status, pivots
 
 
