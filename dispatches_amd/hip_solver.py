@@ -111,7 +111,7 @@ EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_
                     "dsp_get_scaling", "dsp_destroy", "dsp_strerror", "dsp_last_hip_error", "dsp_version",
                     "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
                     "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step", "dsp_loop_project",
-                    "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare", "dsp_loop_ledger", "dsp_loop_record")
+                    "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare", "dsp_loop_ledger", "dsp_loop_record", "dsp_loop_health")
 
 
 ABI_VERSION = 22       # DSP_VERSION of the include/dsp_hip.h these structures mirror
@@ -219,6 +219,16 @@ class DspLoopRecordDesc(C.Structure):
                 ("segments", DspLoopRecordSegment * RECORD_MAX_SEGMENTS)]
 
 
+HEALTH_KINDS, HEALTH_MAX_ROWS = ("day_ahead", "real_time", "tracking", "projection"), 16
+
+
+class DspLoopHealthState(C.Structure):
+    """include/dsp_hip.h: dsp_loop_health_state (added under ABI 22) - the per-plant solve health counters of the descriptor loop"""
+    _fields_ = [("B", C.c_int32), ("reserved", C.c_int32), ("clock", C.c_void_p),
+                ("solves", C.c_void_p), ("fail", C.c_void_p), ("status_mask", C.c_void_p), ("waived", C.c_void_p),
+                ("iters", C.c_void_p), ("iters_max", C.c_void_p), ("first", C.c_void_p), ("reserved2", C.c_int64 * 4)]
+
+
 def source_hash(root: Optional[str] = None) -> Optional[str]:
     """What dsp_source_hash() of a library built from the sources in this tree returns: the first 16 hex digits of the SHA-256 over
     csrc/*.hip, csrc/*.hpp and include/dsp_hip.h (name order, each preceded by its base name).  None when the sources are not
@@ -318,6 +328,8 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_ledger.restype = C.c_int
     lib.dsp_loop_record.argtypes = [C.POINTER(DspLoopRecordDesc), i32, vp]
     lib.dsp_loop_record.restype = C.c_int
+    lib.dsp_loop_health.argtypes = [C.POINTER(DspLoopHealthState), vp, vp, vp, i32, i32, vp]
+    lib.dsp_loop_health.restype = C.c_int
     lib.dsp_last_hip_error.restype = C.c_int
     if path == _LIB_PATH:
         _lib = lib

@@ -141,7 +141,8 @@ class BatchedWindBatteryDoubleLoop(_DeviceLoop):
                  price_cap=500.0, warm_start=True, lp_backend=None, use_graphs=True, use_fused=True, record=None, simplex_warm=True, warm_patience=10000,
                  n_price_scenarios=1, forecaster="perfect", max_historical_days=10, market="stub"):
         """(This loop reports electricity-market revenue only.  The per-plant ledger - total cost, missed delivery, curtailment, profit -
-        is BatchedDoubleLoop("wind_battery", ..., ledger=True) of rolling_flowsheets.py, the descriptor loop that covers this flowsheet.)
+        is BatchedDoubleLoop("wind_battery", ..., ledger=True) of rolling_flowsheets.py, the descriptor loop that covers this flowsheet.
+        So is the per-plant solve health, health=True: this loop and PipelinedDoubleLoops report `bad` / `uncertified` only.)
         lp_backend: None = the HIP solver on GPU `device`; tests pass a factory lp -> object with DeviceLP.solve's
         signature working on CPU tensors (tests/_highs_solver.py::HighsTensorLP), which runs the SAME window / objective /
         state-hand-off logic without a GPU.

@@ -84,7 +84,12 @@ csrc/dsp_market.hip (dsp_loop_monotone_prepare; dsp_loop_market_clear on a state
 
 Recording (record=(plants, days); loop_record.py): what the reference's four result files per generator are made of - states, solutions,
 curves, dispatches, delivered power - kept hour by hour for up to 64 plants in device buffers, by one gather launch per write
-(dsp_loop_record) inside the captured steps, and written as those files through the host classes' own row builders (write_results)."""
+(dsp_loop_record) inside the captured steps, and written as those files through the host classes' own row builders (write_results).
+
+Solve health (health=True): `bad` and `uncertified` say that SOME row of SOME plant failed or went uncertified; the health counters say
+which plant, in which kind of solve (day-ahead, real-time, tracking, projection), from which hour on, and what the solves cost in
+iterations - one launch per solve (dsp_loop_health, csrc/dsp_health.hip) inside the captured steps, over exactly the rows that feed the
+two global flags.  `_health_book` is the specification as tensor operations; integers, so the two agree exactly."""
 from __future__ import annotations
 
 import numpy as np
@@ -477,7 +482,7 @@ class BatchedDoubleLoop(_DeviceLoop):
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
                  market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
                  battery_mwh=None, ruc_hour=None, scenario_coupling="independent", ledger=False, pem_mw=None, tank_kg=None,
-                 h2_price=None, h2_demand=None, record=None, record_max_bytes=2 ** 30, simplex_certify=False):
+                 h2_price=None, h2_demand=None, record=None, record_max_bytes=2 ** 30, simplex_certify=False, health=False):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -567,7 +572,22 @@ class BatchedDoubleLoop(_DeviceLoop):
         record; hours and days past the span land in the spare row.  recorded() returns host arrays cut to what was run, plus
         `plants`; write_results(path) the reference's files; reset() zeroes the record; record_bytes is its size.  Refused
         (ValueError): plants that are not increasing, not distinct or outside [0, B), more than 64 plants, days < 1, buffers above
-        record_max_bytes (default 2 ** 30: a guard against recording a whole batch by mistake, not a measured figure)."""
+        record_max_bytes (default 2 ** 30: a guard against recording a whole batch by mistake, not a measured figure).
+        health: False (the loops above: same launches, same bits, no new attributes) or True: the solve health PER PLANT beside the two
+        global flags.  Every mode is a sequence of solves of four kinds, health_kinds = ("day_ahead", "real_time", "tracking",
+        "projection"); directly after every solve its rows are booked to the plant they belong to - a solve with R rows per plant books
+        rows b * R .. b * R + R - 1 to plant b; R = S for the independent bidding batches, 1 for a coupled day-ahead row, a
+        self-schedule's hourly LP, the tracker and the projection tracker: exactly the rows whose status and flags feed `bad` and
+        `uncertified` - into persistent device tensors, all zeroed by reset(): health_solves / health_fail / health_waived [4, B] int32
+        (rows solved; rows with status != 0; rows with status 0 and DSP_FLAG_OBJ_WAIVED), health_status [4, B] int32 (the OR of
+        1 << status over the failed rows: bits 1 .. 4), health_iters [4, B] int64 / health_iters_max [4, B] int32 (sum and maximum of
+        dsp_batch::iters: PDHG iterations or simplex pivots, whatever the path reports) and health_first [B] int64 (device clock + 1
+        at the plant's first non-optimal row of any kind, 0 = none).  So bool(bad) == bool(health_fail.sum() > 0) and uncertified ==
+        health_waived.sum() at every point of a run.  The pending bid of ruc_hour is booked as day_ahead at the clock of the hour it
+        is made; the 24 - H solves of its projection chain as projection; bidder="parametrized" books tracking only.  Works in every
+        mode, with ledger and record, eagerly or from graphs: one launch of dsp_loop_health per solve inside the step (csrc/dsp_health.hip;
+        use_fused=False and the CPU stand-in: the same integers as tensor operations, _health_book).  results() gains failed_solves,
+        uncertified_solves, first_failure_hour (-1: none) and valid [B]."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
@@ -682,6 +702,9 @@ class BatchedDoubleLoop(_DeviceLoop):
                 self._param_setup()
             elif self.stochastic:
                 self._market_setup()
+        self.health = bool(health)
+        if self.health:
+            self._health_setup()
         # the mode's day-ahead step, hour step and LP solves per call of day_ahead() / hour_step(), bound once
         if self.parametrized:
             self._da_step, self._hour, self._n_da, self._n_hour = self._day_ahead_step_parametrized, self._hour_step_parametrized, 0, B
@@ -930,6 +953,48 @@ class BatchedDoubleLoop(_DeviceLoop):
                             per_avail_t=t(per_avail))
         self._zeroed += [self.ledger_acc, self.ledger_hour]
 
+    def _health_setup(self):
+        """the health counters (persistent, zeroed by reset()), the operands of the tensor form and - with the kernels - the descriptor"""
+        import torch
+        from .hip_solver import HEALTH_KINDS
+        B, dev = self.B, self.dev
+        z = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)
+        self.health_kinds = HEALTH_KINDS
+        K = len(HEALTH_KINDS)
+        self.health_solves, self.health_fail = z(torch.int32, K, B), z(torch.int32, K, B)
+        self.health_status, self.health_waived = z(torch.int32, K, B), z(torch.int32, K, B)
+        self.health_iters, self.health_iters_max = z(torch.int64, K, B), z(torch.int32, K, B)
+        self.health_first = z(torch.int64, B)
+        self._zeroed += [self.health_solves, self.health_fail, self.health_status, self.health_waived, self.health_iters, self.health_iters_max,
+                         self.health_first]
+        self._result_keys += ["failed_solves", "uncertified_solves", "first_failure_hour", "valid"]
+        # (persistent operands: a captured step creates no tensor from host data)
+        self._health_consts = tuple(torch.full((), v, dtype=torch.int32, device=dev) for v in (0, 1, 30))
+        if self.use_fused:
+            from .hip_solver import DspLoopHealthState
+            h = DspLoopHealthState()
+            h.B, h.clock = B, self.hour_t.data_ptr()
+            h.solves, h.fail, h.status_mask, h.waived = (v.data_ptr() for v in (self.health_solves, self.health_fail, self.health_status, self.health_waived))
+            h.iters, h.iters_max, h.first = self.health_iters.data_ptr(), self.health_iters_max.data_ptr(), self.health_first.data_ptr()
+            self._health_state = h
+
+    # what results() reports of the health counters (the keys _health_setup adds to _result_keys)
+    @property
+    def failed_solves(self):
+        return self.health_fail.sum(0)
+
+    @property
+    def uncertified_solves(self):
+        return self.health_waived.sum(0)
+
+    @property
+    def first_failure_hour(self):
+        return self.health_first - 1
+
+    @property
+    def valid(self):
+        return self.health_fail.sum(0) == 0
+
     def _parametrized_setup(self, d, bid_price, storage_mw, tr_model, fam):
         import torch
         from .flowsheets import parameters as prm
@@ -1118,6 +1183,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         self._set_state(m, self._set_prices(m, da, rt))
         self._free_day_ahead_power(m)
         out = m.solve(self.B)
+        self._health_book("day_ahead", m, 1)
         self._check(out)
         (self.pend_offer if bid else self.da_offer).copy_(out["x"][:, m.pda_cols][:, :24])
         (self.pend_prices if bid else self.da_prices).copy_(da[:, :24])
@@ -1127,8 +1193,10 @@ class BatchedDoubleLoop(_DeviceLoop):
             hour = k if self.simplex_warm else None
             self._fused(0, k)
             self.rt.solve(self.B, hour=hour)            # (status / flags: checked by the kernel's next phase)
+            self._health_book("real_time", self.rt, 1)
             self._fused(1, k)
             self.tr.solve(self.B, hour=hour)
+            self._health_book("tracking", self.tr, 1)
             self._fused(2, k)
             return
         m = self.rt
@@ -1140,6 +1208,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         self._free_day_ahead_power(m, k)
         hour = k if self.simplex_warm else None
         out = m.solve(self.B, hour=hour)
+        self._health_book("real_time", m, 1)
         self._check(out)
         offer = m.power_output(out["x"])                                  # real-time offer = SCED dispatch in the stub market
         tr = self.tr
@@ -1148,6 +1217,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         tr.rlo[:, tr.track_rows] = rhs
         tr.rhi[:, tr.track_rows] = rhs
         out = tr.solve(self.B, hour=hour)
+        self._health_book("tracking", tr, 1)
         self._check(out)
         self._hand_off(out["x"], rt[:, 0], k, exact=False)
 
@@ -1198,6 +1268,39 @@ class BatchedDoubleLoop(_DeviceLoop):
                 v = exact_fma(torch, L["per_avail_t"][f].expand(B), avail0, v)
             self.ledger_hour[f].copy_(v)
             self.ledger_acc[f] += v
+
+    def _health_book(self, kind, m, rows_per_plant):
+        """the solve of model m that has just finished, booked per plant under `kind` (health_kinds), BEFORE the step advances the clock:
+        rows b * R .. b * R + R - 1 of m.out belong to plant b.  With the kernels one launch of dsp_loop_health; otherwise its statement
+        as tensor operations - integers, so the two are equal exactly.  A backend without flags / iters (the CPU stand-in has no
+        flags) leaves the counters that need them untouched, like the kernel's NULL."""
+        if not self.health:
+            return
+        import torch
+        out, B, R, k = m.out, self.B, int(rows_per_plant), self.health_kinds.index(kind)
+        if self.use_fused:
+            import ctypes as C
+            ptr = lambda key: C.c_void_p(out[key].data_ptr()) if out.get(key) is not None else None
+            self._call(self._lib.dsp_loop_health, C.byref(self._health_state), ptr("status"), ptr("flags"), ptr("iters"), R, k)
+            return
+        zero, one, other = self._health_consts
+        status = out["status"].reshape(B, R)
+        failed = status != 0
+        n_failed = failed.sum(1)
+        self.health_solves[k] += R
+        self.health_fail[k] += n_failed.to(torch.int32)
+        bit = torch.where(failed, torch.bitwise_left_shift(one, torch.where((status >= 1) & (status <= 29), status, other)), zero)
+        mask = bit[:, 0]
+        for i in range(1, R):
+            mask = mask | bit[:, i]
+        self.health_status[k] |= mask
+        if out.get("flags") is not None:
+            self.health_waived[k] += (~failed & ((out["flags"].reshape(B, R) & 1) != 0)).sum(1).to(torch.int32)
+        if out.get("iters") is not None:
+            iters = out["iters"].reshape(B, R)
+            self.health_iters[k] += iters.sum(1)
+            self.health_iters_max[k].copy_(torch.maximum(self.health_iters_max[k], iters.amax(1).clamp(min=0)))
+        self.health_first.copy_(torch.where((n_failed > 0) & (self.health_first == 0), self.hour_t + 1, self.health_first))
 
     # -- stochastic mode: backcast scenarios, bid curves from p_min, market clearing (semantics: rolling.py, generalised over the descriptor) --
     def _avail(self, m, offset=0):
@@ -1279,6 +1382,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         if self.use_fused:
             self._market_prepare(self._mk_da, -1, bid)
             m.solve(B * S)
+            self._health_book("day_ahead", m, S)
             self._market_clear(self._mk_da, None, -1, 24, *self._day_ahead_buffers(bid)[:3], bid=bid)
             return self._day_ahead_market(None, bid)
         da = self._forecast(self.da_series, m.T, 0).expand(B, S, m.T)
@@ -1286,6 +1390,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         self._set_rows(m, da.reshape(B * S, m.T), rt.reshape(B * S, m.T))
         self._free_day_ahead_power(m)
         out = m.solve(B * S)
+        self._health_book("day_ahead", m, S)
         self._check(out)
         power = out["x"][:, m.pda_cols[:24]].reshape(B, S, 24)
         self._day_ahead_market(self._curves(power, self._forecast(self.da_series, 24, 0), out["status"]), bid)
@@ -1304,8 +1409,10 @@ class BatchedDoubleLoop(_DeviceLoop):
         if self.use_fused:
             self._market_prepare(self._mk_rt, k)
             m.solve(B * per, hour=hour)
+            self._health_book("real_time", m, per)
             self._market_clear(self._mk_rt, self._loop_tr, k, tr.T, self.rt_dispatch, self.rt_curve, self.rt_count)
             tr.solve(B, hour=hour)
+            self._health_book("tracking", tr, 1)
             self._fused(2, k)                         # delivered power, state hand-off, revenue, energy, clock: unchanged (reads the tracker only)
             return
         rt_f = self._forecast(self.rt_series, m.T, k)[:, :per].expand(B, per, m.T)
@@ -1315,6 +1422,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         self._set_rows(m, da_f.reshape(B * per, m.T), rt_f.reshape(B * per, m.T))
         self._free_day_ahead_power(m, k, per)
         out = m.solve(B * per, hour=hour)
+        self._health_book("real_time", m, per)
         self._check(out)
         x, Tc = out["x"], tr.T
         power = (x[:, m.pt_a[:Tc]] * m.pt_ca[:Tc] + x[:, m.pt_b[:Tc]] * m.pt_cb[:Tc]) + m.PT_const[:Tc]      # two-term elementwise form, not a matmul
@@ -1327,6 +1435,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         self._store_curves(self.rt_curve, self.rt_count, U, M, count)
         self._set_tracker()
         out = tr.solve(B, hour=hour)
+        self._health_book("tracking", tr, 1)
         self._check(out)
         self._hand_off(out["x"], rt0[:, 0], k, exact=self.exact)
 
@@ -1360,10 +1469,12 @@ class BatchedDoubleLoop(_DeviceLoop):
         if self.use_fused:
             self._call(self._lib.dsp_loop_schedule_prepare, C.byref(self._mk_sched), C.byref(self._mk_da))
             m.solve(B)
+            self._health_book("day_ahead", m, 1)
             self._market_clear(self._mk_da, None, -1, 24, *self._day_ahead_buffers()[:3])
             return self._day_ahead_market()
         self._coupled_blocks()
         out = m.solve(B)
+        self._health_book("day_ahead", m, 1)
         self._check(out)
         self._day_ahead_market(self._schedule_curves(out["x"][:, m.pda_cols[:24]], out["status"]))      # (block 0: the block-relative columns)
 
@@ -1380,6 +1491,7 @@ class BatchedDoubleLoop(_DeviceLoop):
             self._call(self._lib.dsp_loop_monotone_prepare, C.byref(self._mk_coupled), C.byref(self._mk_da), C.c_void_p(m.rlo.data_ptr()),
                        C.c_void_p(m.rhi.data_ptr()), m.lp.m, m.first_coupling_row)
             m.solve(B)
+            self._health_book("day_ahead", m, 1)
             self._market_clear(self._mk_da, None, -1, 24, *self._day_ahead_buffers()[:3], state=self._mk_coupled)
             return self._day_ahead_market()
         da = self._coupled_blocks()
@@ -1393,6 +1505,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         m.rlo[:, rows] = torch.where(d > 0, zero, below)
         m.rhi[:, rows] = torch.where(d < 0, zero, above)
         out = m.solve(B)
+        self._health_book("day_ahead", m, 1)
         self._check(out)
         power = out["x"].reshape(B, S, m.n1)[:, :, m.pda_cols[:24]]                  # block i: the block-relative columns
         self._day_ahead_market(self._curves(power, self._forecast(self.da_series, 24, 0), out["status"].repeat_interleave(S)))
@@ -1447,6 +1560,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         hour = k if self.simplex_warm else None
         self._param_dispatch(k)
         out = tr.solve(B, hour=hour)
+        self._health_book("tracking", tr, 1)
         self._param_hydrogen(k)
         if self.use_fused:
             self._fused(2, k)                         # delivered power, state hand-off, revenue, energy, clock: unchanged (reads the tracker only)
@@ -1515,6 +1629,7 @@ class BatchedDoubleLoop(_DeviceLoop):
                 self._project_write(j)
                 hour = (0 if j == 0 else 1) if self.simplex_warm else None         # step 0 from the slack basis, then from the step before
                 out = pj.solve(B, hour=hour)
+                self._health_book("projection", pj, 1)
                 self._project_hand_off(j, out)
         torch.add(self.hour_t, 24 - H, out=self.bid_hour_t)
         self._clk, self._st = self.bid_hour_t, self.proj_state[-1]
@@ -1597,6 +1712,10 @@ class BatchedDoubleLoop(_DeviceLoop):
         write_results(self, path, start_date)
 
     def results(self):
+        """-> (dict of per-plant device tensors, ok): obj / energy_mwh / state, the mode's sums, the ledger's rows and profit (ledger=True),
+        and with health=True failed_solves, uncertified_solves, first_failure_hour (int64, -1: none) and valid = failed_solves == 0 [B].
+        From first_failure_hour on, a plant with valid == False ran on a bid whose failed rows were dropped, or on an unconverged LP.
+        ok: no LP of any plant ended with a status other than 0."""
         res = dict(obj=self.revenue, energy_mwh=self.energy_mwh, state=self.state)
         res.update((key, getattr(self, key)) for key in self._result_keys)
         if self.ledger:

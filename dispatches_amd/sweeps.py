@@ -27,18 +27,26 @@ def _ledger_outputs(loop, res, shape):
     return {key: res[key].cpu().numpy().reshape(shape).copy() for key in list(loop.ledger_keys) + ["profit"]}
 
 
+def _health_outputs(res, shape):
+    """the per-plant solve health of a loop run with health=True, shaped like a sweep's other outputs: which grid points' numbers can be
+    trusted (valid), how many of their LP rows failed, and from which simulated hour on (-1: never)"""
+    return {key: res[key].cpu().numpy().reshape(shape).copy() for key in ("valid", "failed_solves", "first_failure_hour")}
+
+
 def parametrized_sweep(flowsheet, bid_prices, storage_mws, n_windows, n_days, device=0, market="price_taker", lp_backend=None, ledger=False,
-                       **loop_kw):
+                       health=False, **loop_kw):
     """Runs `n_days` simulated days of the (bid price x storage size x window) grid of `flowsheet` ("wind_pem" or "wind_battery").
     -> dict of numpy arrays shaped [len(bid_prices), len(storage_mws), n_windows]: revenue, energy_mwh (delivered), da_energy_mwh
     (cleared day-ahead), offered_mwh (the day-ahead curves' last points), h2_kg (wind + PEM only); and all_optimal (bool).
     ledger=True: also the loop's ledger (BatchedDoubleLoop(ledger=True): tot_cost, under_mwh, over_mwh, curtailed_mwh, pem_mwh for
-    wind + PEM) and profit = revenue - tot_cost, same shape."""
+    wind + PEM) and profit = revenue - tot_cost, same shape.
+    health=True: also valid (bool), failed_solves and first_failure_hour (-1: none) of every grid point (BatchedDoubleLoop(health=True)),
+    same shape: all_optimal == False no longer condemns the whole sweep."""
     from .rolling_flowsheets import BatchedDoubleLoop
     bid, sto, win = grid_layout(bid_prices, storage_mws, n_windows)
     shape = (len(np.ravel(bid_prices)), len(np.ravel(storage_mws)), int(n_windows))
     loop = BatchedDoubleLoop(flowsheet, len(bid), device=device, lp_backend=lp_backend, bidder="parametrized", bid_price=bid, storage_mw=sto,
-                             plant_windows=win, market=market, ledger=ledger, **loop_kw)
+                             plant_windows=win, market=market, ledger=ledger, health=health, **loop_kw)
     for _ in range(int(n_days)):
         loop.run_day()
     res, ok = loop.results()
@@ -47,6 +55,8 @@ def parametrized_sweep(flowsheet, bid_prices, storage_mws, n_windows, n_days, de
                              ("h2_kg", "h2_kg")) if key in res}
     if ledger:
         out.update(_ledger_outputs(loop, res, shape))
+    if health:
+        out.update(_health_outputs(res, shape))
     out["all_optimal"] = bool(ok)
     return out
 
@@ -62,7 +72,7 @@ def design_layout(wind_mws, battery_mws, durations_h, n_windows):
 
 
 def design_sweep(flowsheet, wind_mws, battery_mws, durations_h, n_windows, n_days, n_price_scenarios=1, forecaster="perfect",
-                 market="price_taker", device=0, lp_backend=None, ledger=False, **loop_kw):
+                 market="price_taker", device=0, lp_backend=None, ledger=False, health=False, **loop_kw):
     """Runs `n_days` simulated days of the (wind MW x battery MW x duration h x window) grid of `flowsheet` with the LP bidder, every grid
     point a plant of its own size.  "wind_battery": all axes; "wind_pem": the wind axis only - battery_mws and durations_h must have
     length 1 and are not used (pass [0.0], [0.0]).  -> dict of numpy arrays shaped [len(wind_mws), len(battery_mws), len(durations_h),
@@ -70,7 +80,8 @@ def design_sweep(flowsheet, wind_mws, battery_mws, durations_h, n_windows, n_day
     forecaster="perfect" with market="stub"), throughput_kwh (wind_battery: the final accumulated battery throughput); and all_optimal.
     ledger=True: also the loop's ledger (tot_cost - degradation, fixed O&M and curtailment penalty of the implemented hours, the
     reference's "Total Cost [$]" -, under_mwh, over_mwh, curtailed_mwh; wind_pem: h2_kg, pem_mwh) and profit = revenue - tot_cost, same
-    shape: what ranks designs, where revenue alone always prefers the larger battery."""
+    shape: what ranks designs, where revenue alone always prefers the larger battery.
+    health=True: also valid, failed_solves and first_failure_hour of every grid point, same shape (parametrized_sweep)."""
     from .rolling_flowsheets import BatchedDoubleLoop
     wind, batt, mwh, win = design_layout(wind_mws, battery_mws, durations_h, n_windows)
     shape = tuple(len(np.ravel(a)) for a in (wind_mws, battery_mws, durations_h)) + (int(n_windows),)
@@ -81,7 +92,7 @@ def design_sweep(flowsheet, wind_mws, battery_mws, durations_h, n_windows, n_day
     else:
         sizes = dict(wind_mw=wind, battery_mw=batt, battery_mwh=mwh)
     loop = BatchedDoubleLoop(flowsheet, len(wind), device=device, lp_backend=lp_backend, n_price_scenarios=n_price_scenarios, forecaster=forecaster,
-                             market=market, plant_windows=win, ledger=ledger, **sizes, **loop_kw)
+                             market=market, plant_windows=win, ledger=ledger, health=health, **sizes, **loop_kw)
     for _ in range(int(n_days)):
         loop.run_day()
     res, ok = loop.results()
@@ -92,6 +103,8 @@ def design_sweep(flowsheet, wind_mws, battery_mws, durations_h, n_windows, n_day
         out["throughput_kwh"] = res["state"][:, 1].cpu().numpy().reshape(shape).copy()
     if ledger:
         out.update(_ledger_outputs(loop, res, shape))
+    if health:
+        out.update(_health_outputs(res, shape))
     out["all_optimal"] = bool(ok)
     return out
 
@@ -107,18 +120,20 @@ def nuclear_layout(h2_prices, pem_mws, n_windows):
 
 
 def nuclear_sweep(h2_prices, pem_mws, n_windows, n_days, tank_kg=None, h2_demand=None, n_price_scenarios=3, forecaster="backcast",
-                  market="price_taker", device=0, lp_backend=None, **loop_kw):
+                  market="price_taker", device=0, lp_backend=None, health=False, **loop_kw):
     """Runs `n_days` simulated days of the (hydrogen price $/kg x PEM size MW x window) grid of the nuclear double loop as ONE batch, every
     grid point a plant with its own h2_price and pem_mw (the reference's study reports elec_rev, h2_rev, net_profit and pem_cap_factor
     over such a grid, nuclear_case/report/price_taker_analysis.py); tank_kg / h2_demand: scalars for all plants (None: the flowsheet's).
     The loop keeps its ledger.  -> dict of numpy arrays shaped [len(h2_prices), len(pem_mws), n_windows]: revenue (electricity), h2_revenue,
     tot_cost (operating cost minus hydrogen revenue), profit = revenue - tot_cost, energy_mwh, h2_kg, pem_capacity_factor = PEM MWh /
-    (pem_mw * hours); and all_optimal."""
+    (pem_mw * hours); and all_optimal.  health=True: also valid, failed_solves and first_failure_hour of every grid point, same shape
+    (parametrized_sweep)."""
     from .rolling_flowsheets import BatchedDoubleLoop
     price, pem, win = nuclear_layout(h2_prices, pem_mws, n_windows)
     shape = (len(np.ravel(h2_prices)), len(np.ravel(pem_mws)), int(n_windows))
     loop = BatchedDoubleLoop("nuclear", len(price), device=device, lp_backend=lp_backend, n_price_scenarios=n_price_scenarios, forecaster=forecaster,
-                             market=market, plant_windows=win, h2_price=price, pem_mw=pem, tank_kg=tank_kg, h2_demand=h2_demand, ledger=True, **loop_kw)
+                             market=market, plant_windows=win, h2_price=price, pem_mw=pem, tank_kg=tank_kg, h2_demand=h2_demand, ledger=True,
+                             health=health, **loop_kw)
     for _ in range(int(n_days)):
         loop.run_day()
     res, ok = loop.results()
@@ -126,5 +141,7 @@ def nuclear_sweep(h2_prices, pem_mws, n_windows, n_days, tank_kg=None, h2_demand
            for name, key in (("revenue", "obj"), ("h2_revenue", "h2_revenue"), ("tot_cost", "tot_cost"), ("profit", "profit"), ("energy_mwh", "energy_mwh"),
                              ("h2_kg", "h2_kg"))}
     out["pem_capacity_factor"] = res["pem_mwh"].cpu().numpy().reshape(shape) / (pem.reshape(shape) * float(loop.hour))
+    if health:
+        out.update(_health_outputs(res, shape))
     out["all_optimal"] = bool(ok)
     return out

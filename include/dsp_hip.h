@@ -36,6 +36,9 @@
  * ABI 21 adds the recorder of the descriptor loop: dsp_loop_record copies up to 16 strided segments (states, solutions, curves, ...) of up
  * to 64 chosen plants into the row of the record that the device clock names - one gather launch, so that the record is written by the
  * replayed hipGraphs too.  Nothing else changes.
+ * Added under ABI 22, DSP_VERSION unchanged: dsp_loop_health and dsp_loop_health_state, the per-plant solve health of the descriptor loop
+ * (rows solved / failed / waived, status mask, iteration sum and maximum, first failing hour - per plant and kind of solve).  A new symbol
+ * and a new struct only: no existing struct, entry point or kernel changed, so a caller of ABI 22 that does not know them is unaffected.
  */
 #ifndef DSP_HIP_H
 #define DSP_HIP_H
@@ -518,6 +521,36 @@ typedef struct dsp_loop_record_desc {
  * elem_stride outside 1 .. 2^40.  (That the sources hold B plants at these strides is the caller's statement, as for every buffer of this
  * interface.)  Capturable: one kernel launch on hipStream, no allocation, no synchronisation, no memset. */
 int dsp_loop_record(const dsp_loop_record_desc *rec, int32_t B, void *hipStream);
+
+/* The solve health of the descriptor loop (added under ABI 22; rolling_flowsheets.py::BatchedDoubleLoop(health=True)): after every solve of
+ * the loop, what its rows' status / flags / iters say is booked to the PLANT the rows belong to, under the KIND of the solve.  A solve with
+ * R = rows_per_plant rows per plant books rows b * R .. b * R + R - 1 to plant b (R = S for the independent bidding batches, 1 for a coupled
+ * day-ahead row, a self-schedule's hourly LP and the trackers): the rows whose status and flags feed dsp_loop_state::bad / uncertified.
+ * With at = kind * B + b, over the rows i of plant b in the order of i:
+ *     solves[at] += R ;   fail[at] += #(status != 0) ;   status_mask[at] |= 1 << status   (status 1 .. 29; another non-zero value: bit 30)
+ *     waived[at] += #(status == 0 and flags & DSP_FLAG_OBJ_WAIVED)                          (flags  NULL: untouched)
+ *     iters[at]  += sum of iters ;   iters_max[at] = max(iters_max[at], max of iters)      (iters  NULL: untouched)
+ *     first[b]    = *clock + 1   if first[b] == 0 and a row of b failed                     (0 = none yet: zeroing is the reset)
+ * One lane per plant, 256 lanes per block; a lane reads the clock once and updates its own seven entries with plain vector stores: no
+ * atomics, no LDS, no cross-lane traffic, integer arithmetic only.  The rows of the other kinds are not touched. */
+#define DSP_HEALTH_KINDS 4             /* 0 day_ahead, 1 real_time, 2 tracking, 3 projection                                        */
+#define DSP_HEALTH_MAX_ROWS 16         /* rows per plant of one solve (DSP_MARKET_MAX_S)                                            */
+typedef struct dsp_loop_health_state {
+  int32_t B, reserved;                 /* plants, >= 1; reserved = 0                                                                */
+  const int64_t *clock;                /* [1] device: the loop's clock (dsp_loop_state::hour)                                       */
+  int32_t *solves, *fail, *status_mask, *waived;     /* [DSP_HEALTH_KINDS][B]                                                       */
+  int64_t *iters;                      /* [DSP_HEALTH_KINDS][B] sum of dsp_batch::iters (PDHG iterations or simplex pivots)         */
+  int32_t *iters_max;                  /* [DSP_HEALTH_KINDS][B] their maximum                                                       */
+  int64_t *first;                      /* [B] clock + 1 at the plant's first non-optimal row of any kind; 0 = none                  */
+  int64_t reserved2[4];                /* 0                                                                                         */
+} dsp_loop_health_state;
+
+/* status / flags / iters: DEVICE arrays [B * rows_per_plant] of the solve that has just finished (dsp_batch::status / flags / iters).
+ * DSP_ERR_INVALID, nothing launched and nothing written, for: a NULL h or status; B < 1; rows_per_plant outside 1 .. DSP_HEALTH_MAX_ROWS;
+ * kind outside 0 .. DSP_HEALTH_KINDS - 1; a NULL clock or counter; reserved != 0.  The descriptor travels by value (<= 4 KB).
+ * Capturable: one kernel launch on hipStream, no allocation, no synchronisation, no memset. */
+int dsp_loop_health(const dsp_loop_health_state *h, const int32_t *status, const int32_t *flags, const int32_t *iters,
+                    int32_t rows_per_plant, int32_t kind, void *hipStream);
 
 /* The scenario half of the Bidder's bid assembly ON THE DEVICE (reference: idaes Bidder._assemble_bids as DISPATCHES drives it -
  * dispatches/workflow/coordinator.py hands its bids to Prescient; golden values
