@@ -36,6 +36,10 @@
 // method does not finish (breakdown, 250 Newton iterations, free columns) is left to the PDHG forms - that scenario alone: the ones this
 // file solved are exported and stay solved (round 6; round 5 re-ran the whole batch).  dsp_options::no_interior_point = 1 switches it off; dsp_stats::stream_form = DSP_STREAM_FORM_IPM when it solved the batch,
 // dsp_stats::stream_phases = the time partitions.
+//
+// The host half (end of this file): the plan is built by dsp_ipm_plan.hpp (host-only) and uploaded by ipm_create; ipm_workspace holds a
+// batch's arrays; ipm_settings reads the development variables of a solve once; ipm_geometry sets the launch geometry for the lane groups in
+// use; ipm_loop is the Newton loop, a sequence of the steps above it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,26 +47,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <map>
+#include <utility>
 #include <vector>
 
+#include "dsp_ipm_plan.hpp"
 #include "dsp_ipm_seq.hpp"
 #include "dsp_stream.hpp"
 
 namespace dsp {
 
-constexpr int kIpmMaxW = 8, kIpmMaxK = 4, kIpmSpan = 16, kIpmMaxNewton = 250;
+constexpr int kIpmMaxNewton = 250;         // (kIpmMaxW, kIpmMaxK, kIpmSpan: dsp_ipm_plan.hpp)
 constexpr int kIpmNQ = 16;                 // partial-sum slots (the Woodbury matrix needs K * K)
-constexpr int kIpmMaxBlocks = 1024;        // blocks (of 4 waves) per lane group in the elementwise kernels, at most
-
-// Blocks per lane group of the elementwise kernels for G groups in use: enough waves to hide the gathers' latency (a wave owns a
-// chunk of indices and walks it with a few loads in flight) - 2048 blocks over the groups, at most kIpmMaxBlocks per group.  Round 5
-// stopped at 256: 1024 waves for a single group of 64 scenarios = one wave per SIMD, 7.6 ms per Newton iteration at 64 scenarios
-// against 13.1 ms at 256.  The partial sums are per block (ipm_put), so the finish kernels walk as many as before.
-static inline int ipm_blocks(int G) {
-  static const int cap = getenv("DSP_IPM_MAXBLK") ? std::min(std::max(atoi(getenv("DSP_IPM_MAXBLK")), 16), kIpmMaxBlocks) : kIpmMaxBlocks;      // (development)
-  static const int tot = getenv("DSP_IPM_TOTBLK") ? atoi(getenv("DSP_IPM_TOTBLK")) : 2048;
-  return std::max(16, std::min(cap, tot / std::max(G, 1)));
-}
+constexpr int kIpmMaxBlocks = 1024;        // blocks (of 4 waves) per lane group in the elementwise kernels, at most (ipm_geometry)
 
 struct IpmPlan {                            // shared by all scenarios (device)
   int n, m, W, K, Mp;                       // Mp = m + W rows of the band arrays
@@ -1236,7 +1232,7 @@ __global__ void k_ipm_after_pack(IpmArgs a, int active, int n_new) {
   if (t == 0) a.w.counts[0] = n_new - active;                                      // lanes of the groups in use that take no part
 }
 
-// ---- host --------------------------------------------------------------------------------------------------------------------------------
+// ---- host: the plan on the device ------------------------------------------------------------------------------------------------------
 template <class T>
 static hipError_t ipm_up(std::vector<void *> &allocs, const std::vector<T> &v, const T **out) {
   void *d = nullptr;
@@ -1248,108 +1244,43 @@ static hipError_t ipm_up(std::vector<void *> &allocs, const std::vector<T> &v, c
   return hipSuccess;
 }
 
-// The plan: wide columns by their row span, the band of the rest, the product lists of its entries.  No plan (S->ipm stays null) when
-// the matrix is not banded enough - the PDHG forms are the general path.
+static hipError_t ipm_upload(const IpmHostPlan &H, IpmState *I) {
+  IpmPlan &P = I->P;
+  P.n = H.n; P.m = H.m; P.W = H.W; P.K = H.K; P.Mp = H.m + H.W;
+  P.rw = H.rw; P.cw = H.cw; P.bw = H.bw;
+  for (int k = 0; k < kIpmMaxK; ++k) P.wide_col[k] = k < H.K ? H.wide_col[k] : 0;
+  P.parts = H.parts;
+  hipError_t e = hipSuccess;
+  auto up = [&](const auto &v, auto out) { if (e == hipSuccess) e = ipm_up(I->allocs, v, out); };
+  up(H.rcol, &P.rcol); up(H.rval, &P.rval); up(H.crow, &P.crow); up(H.cval, &P.cval);
+  up(H.wide, &P.wide); up(H.wptr, &P.wptr); up(H.wrow, &P.wrow); up(H.wval, &P.wval);
+  up(H.bcol, &P.bcol); up(H.bval, &P.bval);
+  if (e != hipSuccess) return e;
+  return hipHostMalloc((void **)&I->counts_host, 8 * sizeof(int));
+}
+
+// everything the form holds for a handle (ipm_destroy; ipm_create when an upload fails)
+static void ipm_free(IpmState *I) {
+  for (void *p : I->allocs) (void)hipFree(p);
+  for (void *p : I->work_allocs) (void)hipFree(p);
+  if (I->counts_host) (void)hipHostFree(I->counts_host);
+  if (I->perm_host) (void)hipHostFree(I->perm_host);
+  delete I;
+}
+
+// No plan (S->ipm stays null) when the matrix is not banded enough (dsp_ipm_plan.hpp) - the PDHG forms are the general path.
 hipError_t ipm_create(const HostCSR &A, const HostCSR &AT, StreamSolver *S) {
   S->ipm = nullptr;
   const int off = getenv("DSP_NO_IPM") ? atoi(getenv("DSP_NO_IPM")) : 0;          // (read at every create: tests build handles of every form)
   if (off) return hipSuccess;
-  const int n = A.n, m = A.m;
-  if (m < 64) return hipSuccess;
-  std::vector<uint8_t> wide(n, 0);
-  std::vector<int32_t> wide_col;
-  for (int j = 0; j < n; ++j) {
-    if (AT.ptr[j + 1] == AT.ptr[j]) continue;
-    int lo = m, hi = -1;
-    for (int p = AT.ptr[j]; p < AT.ptr[j + 1]; ++p) { lo = std::min(lo, (int)AT.idx[p]); hi = std::max(hi, (int)AT.idx[p]); }
-    if (hi - lo > kIpmSpan) { wide[j] = 1; wide_col.push_back(j); }
-  }
-  if ((int)wide_col.size() > kIpmMaxK) return hipSuccess;
-  int W = 0;
-  for (int j = 0; j < n; ++j)
-    if (!wide[j] && AT.ptr[j + 1] > AT.ptr[j]) {
-      int lo = m, hi = -1;
-      for (int p = AT.ptr[j]; p < AT.ptr[j + 1]; ++p) { lo = std::min(lo, (int)AT.idx[p]); hi = std::max(hi, (int)AT.idx[p]); }
-      W = std::max(W, hi - lo);
-    }
-  if (W > kIpmMaxW) return hipSuccess;
-  W = W <= 6 ? 6 : 8;
-  const int W1 = W + 1;
-  // B(t, t - k) = sum over the narrow columns j of rows t and t - k: a_tj a_(t-k)j theta_j
-  std::vector<std::vector<std::pair<int32_t, double>>> prod((size_t)m * W1);
-  int bw = 1;
-  for (int t = 0; t < m; ++t)
-    for (int k = 0; k < W1; ++k) {
-      const int r2 = t - k;
-      if (r2 < 0) continue;
-      auto &pl = prod[(size_t)t * W1 + k];
-      for (int p = A.ptr[t]; p < A.ptr[t + 1]; ++p) {
-        const int j = A.idx[p];
-        if (wide[j]) continue;
-        for (int p2 = A.ptr[r2]; p2 < A.ptr[r2 + 1]; ++p2)
-          if (A.idx[p2] == j) pl.push_back({j, A.val[p] * A.val[p2]});
-      }
-      bw = std::max(bw, (int)pl.size());
-    }
-  bw = (bw + 3) / 4 * 4;                                              // (the kernels take the entries four at a time; padding: index 0, value 0)
-  std::vector<int32_t> bcol((size_t)m * W1 * bw, 0);
-  std::vector<double> bval((size_t)m * W1 * bw, 0.0);
-  for (size_t e = 0; e < prod.size(); ++e)
-    for (size_t q = 0; q < prod[e].size(); ++q) { bcol[e * bw + q] = prod[e][q].first; bval[e * bw + q] = prod[e][q].second; }
-  // ELL of the rows (all columns) and of the narrow columns; CSR of the wide columns
-  int rw = 1, cw = 1;
-  for (int i = 0; i < m; ++i) rw = std::max(rw, A.ptr[i + 1] - A.ptr[i]);
-  for (int j = 0; j < n; ++j) if (!wide[j]) cw = std::max(cw, AT.ptr[j + 1] - AT.ptr[j]);
-  if (rw > 16 || cw > 16 || bw > 16) return hipSuccess;              // not the sparse time-banded kind after all
-  rw = (rw + 3) / 4 * 4; cw = (cw + 3) / 4 * 4;
-  std::vector<int32_t> rcol((size_t)m * rw, 0), crow((size_t)n * cw, 0), wptr(1, 0), wrow;
-  std::vector<double> rval((size_t)m * rw, 0.0), cval((size_t)n * cw, 0.0), wval;
-  for (int i = 0; i < m; ++i)
-    for (int p = A.ptr[i], q = 0; p < A.ptr[i + 1]; ++p, ++q) { rcol[(size_t)i * rw + q] = A.idx[p]; rval[(size_t)i * rw + q] = A.val[p]; }
-  for (int j = 0; j < n; ++j)
-    if (!wide[j])
-      for (int p = AT.ptr[j], q = 0; p < AT.ptr[j + 1]; ++p, ++q) { crow[(size_t)j * cw + q] = AT.idx[p]; cval[(size_t)j * cw + q] = AT.val[p]; }
-  for (size_t k = 0; k < wide_col.size(); ++k) {
-    const int j = wide_col[k];
-    wide[j] = (uint8_t)(k + 1);
-    std::vector<std::pair<int32_t, double>> ent;
-    for (int p = AT.ptr[j]; p < AT.ptr[j + 1]; ++p) ent.push_back({(int32_t)AT.idx[p], AT.val[p]});
-    std::sort(ent.begin(), ent.end());                                   // k_ipm_wide_rhs searches them by row
-    for (const auto &en : ent) { wrow.push_back(en.first); wval.push_back(en.second); }
-    wptr.push_back((int32_t)wrow.size());
-  }
+  // DSP_IPM_PARTS = 1: the sequential walks (development, tests: any count the rows allow)
+  const int parts = getenv("DSP_IPM_PARTS") ? std::max(1, atoi(getenv("DSP_IPM_PARTS"))) : 0;
+  IpmHostPlan H;
+  if (!ipm_plan_build(A, AT, parts, H)) return hipSuccess;
   IpmState *I = new IpmState();
-  IpmPlan &P = I->P;
-  P.n = n; P.m = m; P.W = W; P.K = (int)wide_col.size(); P.Mp = m + W;
-  P.rw = rw; P.cw = cw; P.bw = bw;
-  for (int k = 0; k < kIpmMaxK; ++k) P.wide_col[k] = k < P.K ? wide_col[k] : 0;
-  P.col_scale = S->P.col_scale; P.row_scale = S->P.row_scale;
-  {
-    // time-parallel form: partitions of >= 256 rows, 64 at most (the reduced system's 63 sequential blocks then weigh about as much as
-    // a partition's 820 rows at T = 8736); DSP_IPM_PARTS = 1: the sequential walks (development, tests: any count the rows allow)
-    int want = std::min(64, m / 256);
-    if (getenv("DSP_IPM_PARTS")) want = std::max(1, atoi(getenv("DSP_IPM_PARTS")));
-    IpmParts g{};
-    g.m = m; g.W = W; g.P = 1; g.Lp = m;
-    if (want >= 2) {
-      const int Lp = std::max((m + want - 1) / want, 4 * W);
-      int parts = (m + Lp - 1) / Lp;
-      if (parts > 1 && m - (parts - 1) * Lp < 2 * W + 1) parts -= 1;       // a short tail joins the partition before it
-      if (parts >= 2) { g.P = parts; g.Lp = Lp; }
-    }
-    P.parts = g;
-  }
-  hipError_t e;
-  if ((e = ipm_up(I->allocs, rcol, &P.rcol)) != hipSuccess || (e = ipm_up(I->allocs, rval, &P.rval)) != hipSuccess ||
-      (e = ipm_up(I->allocs, crow, &P.crow)) != hipSuccess || (e = ipm_up(I->allocs, cval, &P.cval)) != hipSuccess ||
-      (e = ipm_up(I->allocs, wide, &P.wide)) != hipSuccess || (e = ipm_up(I->allocs, wptr, &P.wptr)) != hipSuccess ||
-      (e = ipm_up(I->allocs, wrow, &P.wrow)) != hipSuccess || (e = ipm_up(I->allocs, wval, &P.wval)) != hipSuccess ||
-      (e = ipm_up(I->allocs, bcol, &P.bcol)) != hipSuccess || (e = ipm_up(I->allocs, bval, &P.bval)) != hipSuccess) {
-    for (void *p : I->allocs) (void)hipFree(p);
-    delete I;
-    return e;
-  }
-  if ((e = hipHostMalloc((void **)&I->counts_host, 8 * sizeof(int))) != hipSuccess) { for (void *p : I->allocs) (void)hipFree(p); delete I; return e; }
+  I->P.col_scale = S->P.col_scale; I->P.row_scale = S->P.row_scale;
+  const hipError_t e = ipm_upload(H, I);
+  if (e != hipSuccess) { ipm_free(I); return e; }
   S->ipm = I;
   return hipSuccess;
 }
@@ -1357,16 +1288,20 @@ hipError_t ipm_create(const HostCSR &A, const HostCSR &AT, StreamSolver *S) {
 int ipm_partitions(const StreamSolver *S) { return S->ipm ? S->ipm->P.parts.P : 0; }
 
 void ipm_destroy(StreamSolver *S) {
-  IpmState *I = S->ipm;
-  if (!I) return;
-  for (void *p : I->allocs) (void)hipFree(p);
-  for (void *p : I->work_allocs) (void)hipFree(p);
-  if (I->counts_host) (void)hipHostFree(I->counts_host);
-  if (I->perm_host) (void)hipHostFree(I->perm_host);
-  delete I;
+  if (S->ipm) ipm_free(S->ipm);
   S->ipm = nullptr;
 }
 
+// ---- host: the workspace of a batch ----------------------------------------------------------------------------------------------------
+template <class T>
+static hipError_t ipm_alloc(std::vector<void *> &allocs, size_t count, T **out) {
+  const hipError_t e = hipMalloc((void **)out, std::max<size_t>(count, 1) * sizeof(T));
+  if (e == hipSuccess) allocs.push_back(*out);
+  return e;
+}
+
+// Grows with the largest batch the handle has seen.  A failure leaves what was allocated in work_allocs: the next call or ipm_destroy
+// releases it, and ipm_run falls through to the PDHG forms.
 static hipError_t ipm_workspace(IpmState *I, int B) {
   if (B <= I->work_B) { I->w.B = B; return hipSuccess; }
   for (void *p : I->work_allocs) (void)hipFree(p);
@@ -1377,60 +1312,124 @@ static hipError_t ipm_workspace(IpmState *I, int B) {
   w.Bp = (size_t)((B + 63) / 64) * 64;
   w.B = B;
   w.G = (int)(w.Bp / 64);
-  w.nch = 4 * kIpmMaxBlocks;               // (capacity of `part`; the solve sets the chunks per group count: ipm_chunks)
-  const size_t N = (size_t)P.n + P.m, M = P.m;
-  hipError_t e;
-  auto alloc = [&](size_t doubles, double **out) {
-    e = hipMalloc((void **)out, std::max<size_t>(doubles, 1) * sizeof(double));
-    if (e == hipSuccess) I->work_allocs.push_back(*out);
-    return e;
-  };
-  double **nv[] = {&w.v, &w.z, &w.f, &w.l, &w.u, &w.cb, &w.th, &w.rd, &w.dv, &w.dz, &w.df, &w.rt, &w.corl, &w.coru, &w.tn};
-  double **mv[] = {&w.y, &w.dy, &w.rp, &w.rhs, &w.q, &w.res};
-  for (double **p : nv) if (alloc(N * w.Bp, p) != hipSuccess) return e;
-  for (double **p : mv) if (alloc(M * w.Bp, p) != hipSuccess) return e;
-  if (alloc((size_t)std::max(P.K, 1) * M * w.Bp, &w.biad) != hipSuccess) return e;
-  if (alloc((size_t)(P.W + 1) * P.Mp * w.Bp, &w.band) != hipSuccess) return e;
+  w.nch = 4 * kIpmMaxBlocks;               // (capacity of `part`; the solve sets the chunks per group count: ipm_geometry)
+  const size_t Bp = w.Bp, N = (size_t)P.n + P.m, M = P.m, parts = P.parts.P;
+  const size_t NT = (size_t)P.W * (P.W + 1) / 2, NR = (size_t)P.W * P.W + NT;
+  std::vector<std::pair<double **, size_t>> doubles;
+  for (double **p : {&w.v, &w.z, &w.f, &w.l, &w.u, &w.cb, &w.th, &w.rd, &w.dv, &w.dz, &w.df, &w.rt, &w.corl, &w.coru, &w.tn}) doubles.push_back({p, N * Bp});
+  for (double **p : {&w.y, &w.dy, &w.rp, &w.rhs, &w.q, &w.res}) doubles.push_back({p, M * Bp});
+  doubles.push_back({&w.biad, (size_t)std::max(P.K, 1) * M * Bp});
+  doubles.push_back({&w.band, (size_t)(P.W + 1) * P.Mp * Bp});
   w.gs = w.sfin = w.cfin = w.redf = w.bd = nullptr;
-  if (P.parts.P > 1) {
-    const size_t NT = (size_t)P.W * (P.W + 1) / 2, NR = (size_t)P.W * P.W + NT;
-    if (alloc((size_t)P.W * P.Mp * w.Bp, &w.gs) != hipSuccess) return e;
-    if (alloc((size_t)P.parts.P * NT * w.Bp, &w.sfin) != hipSuccess) return e;
-    if (alloc((size_t)P.parts.P * NT * w.Bp, &w.cfin) != hipSuccess) return e;
-    if (alloc((size_t)P.parts.P * NR * w.Bp, &w.redf) != hipSuccess) return e;
-    if (alloc((size_t)kIpmBorderSplit * P.parts.P * P.W * w.Bp, &w.bd) != hipSuccess) return e;
+  if (parts > 1) {                         // the time-parallel form's arrays
+    doubles.push_back({&w.gs, (size_t)P.W * P.Mp * Bp});
+    doubles.push_back({&w.sfin, parts * NT * Bp});
+    doubles.push_back({&w.cfin, parts * NT * Bp});
+    doubles.push_back({&w.redf, parts * NR * Bp});
+    doubles.push_back({&w.bd, (size_t)kIpmBorderSplit * parts * P.W * Bp});
   }
-  if (alloc((size_t)SC_COUNT * w.Bp, &w.sc) != hipSuccess) return e;
-  if (alloc((size_t)kIpmNQ * kIpmMaxBlocks * w.Bp, &w.part) != hipSuccess) return e;
-  if (alloc((size_t)kIpmMaxK * kIpmMaxK * w.Bp, &w.sinv) != hipSuccess) return e;
-  if (alloc((size_t)kIpmMaxK * w.Bp, &w.tk) != hipSuccess) return e;
-  if (alloc((size_t)kIpmMaxK * w.Bp, &w.wat) != hipSuccess) return e;
-  if ((e = hipMalloc((void **)&w.state, w.Bp * sizeof(int))) != hipSuccess) return e;
-  I->work_allocs.push_back(w.state);
-  if ((e = hipMalloc((void **)&w.iters, w.Bp * sizeof(int))) != hipSuccess) return e;
-  I->work_allocs.push_back(w.iters);
-  if ((e = hipMalloc((void **)&w.stall, w.Bp * sizeof(int))) != hipSuccess) return e;
-  I->work_allocs.push_back(w.stall);
-  if ((e = hipMalloc((void **)&w.endg, w.Bp * sizeof(int))) != hipSuccess) return e;
-  I->work_allocs.push_back(w.endg);
-  if ((e = hipMalloc((void **)&w.counts, 8 * sizeof(int))) != hipSuccess) return e;
-  I->work_allocs.push_back(w.counts);
-  if ((e = hipMalloc((void **)&w.sid, w.Bp * sizeof(int))) != hipSuccess) return e;
-  I->work_allocs.push_back(w.sid);
-  if ((e = hipMalloc((void **)&w.perm, w.Bp * sizeof(int))) != hipSuccess) return e;
-  I->work_allocs.push_back(w.perm);
+  doubles.push_back({&w.sc, (size_t)SC_COUNT * Bp});
+  doubles.push_back({&w.part, (size_t)kIpmNQ * kIpmMaxBlocks * Bp});
+  doubles.push_back({&w.sinv, (size_t)kIpmMaxK * kIpmMaxK * Bp});
+  doubles.push_back({&w.tk, (size_t)kIpmMaxK * Bp});
+  doubles.push_back({&w.wat, (size_t)kIpmMaxK * Bp});
+  const std::pair<int **, size_t> ints[] = {{&w.state, Bp}, {&w.iters, Bp}, {&w.stall, Bp}, {&w.endg, Bp}, {&w.counts, 8}, {&w.sid, Bp}, {&w.perm, Bp}};
+  hipError_t e;
+  for (const auto &d : doubles) if ((e = ipm_alloc(I->work_allocs, d.second, d.first)) != hipSuccess) return e;
+  for (const auto &d : ints) if ((e = ipm_alloc(I->work_allocs, d.second, d.first)) != hipSuccess) return e;
   if (I->perm_host) { (void)hipHostFree(I->perm_host); I->perm_host = nullptr; }
-  if ((e = hipHostMalloc((void **)&I->perm_host, w.Bp * sizeof(int))) != hipSuccess) return e;
+  if ((e = hipHostMalloc((void **)&I->perm_host, Bp * sizeof(int))) != hipSuccess) return e;
   I->work_B = B;
   return hipSuccess;
 }
 
-static int ipm_seq_mode() { static const int v = getenv("DSP_IPM_SEQ_MODE") ? atoi(getenv("DSP_IPM_SEQ_MODE")) : 0; return v; }
+// ---- host: development settings ---------------------------------------------------------------------------------------------------------
+// Every DSP_IPM_* variable of a solve, read ONCE at its start (ipm_run) and handed down: a test or a tool that sets one between two solves
+// of a process switches it for the next solve, whichever it is.  DSP_NO_IPM and DSP_IPM_PARTS belong to the handle: ipm_create reads them.
+struct IpmSettings {
+  int max_it;                               // DSP_IPM_MAXIT: Newton iterations before the form gives up (1 .. kIpmMaxNewton)
+  double reg, step, step_blocked, step_thr, sigmin, thcap, reftol, reftol_end;      // DSP_IPM_REG, _STEP, ... (IpmArgs)
+  int max_undo;                             // DSP_IPM_MAX_UNDO
+  int max_blocks;                           // DSP_IPM_MAXBLK: blocks per lane group of the elementwise kernels, at most (16 .. kIpmMaxBlocks)
+  int seq_mode;                             // DSP_IPM_SEQ_MODE (SeqArgs::dev_mode)
+  bool compact;                             // DSP_IPM_COMPACT=0: every scenario keeps its lane to the end of the solve (measurement); more than 1024 lanes: not packed
+  int trace;                                // DSP_IPM_TRACE = lane + 1: what the loop decides, and that lane's scalars, on stderr
+  int debug;                                // DSP_IPM_DEBUG: synchronise after every step (2: and name it)
+  int check_pred;                           // DSP_IPM_CHECK_PRED: check / refine the predictor's system never (0), always (1), or (-1, default) once a step was taken back
+};
 
-// one walk: `parts` partitions starting with partition `part0` (grid.y), `rows` rows each (`last_rows` for the last one of the `nparts`)
+static IpmSettings ipm_settings(size_t Bp) {
+  auto num = [](const char *name, double otherwise) { const char *v = getenv(name); return v ? atof(v) : otherwise; };
+  auto whole = [](const char *name, int otherwise) { const char *v = getenv(name); return v ? atoi(v) : otherwise; };
+  IpmSettings s{};
+  s.max_it = std::max(1, std::min(whole("DSP_IPM_MAXIT", kIpmMaxNewton), kIpmMaxNewton));
+  s.reg = num("DSP_IPM_REG", 0.0);
+  s.step = num("DSP_IPM_STEP", 0.99);
+  s.step_blocked = num("DSP_IPM_STEP_BLOCKED", 0.9);
+  s.step_thr = num("DSP_IPM_STEP_THR", 0.5);                                        // (sweep: profiles/r69a_ipm_step_sweep.log)
+  s.sigmin = num("DSP_IPM_SIGMIN", 0.05);
+  s.thcap = num("DSP_IPM_THCAP", 1e11);
+  s.reftol = num("DSP_IPM_REFTOL", 1e-6);
+  s.reftol_end = num("DSP_IPM_REFTOL_END", 1e-6);
+  s.max_undo = whole("DSP_IPM_MAX_UNDO", 3);
+  s.max_blocks = std::min(std::max(whole("DSP_IPM_MAXBLK", kIpmMaxBlocks), 16), kIpmMaxBlocks);
+  s.seq_mode = whole("DSP_IPM_SEQ_MODE", 0);
+  s.compact = whole("DSP_IPM_COMPACT", 1) != 0 && Bp <= 1024;
+  s.trace = whole("DSP_IPM_TRACE", 0);
+  s.debug = whole("DSP_IPM_DEBUG", 0);
+  s.check_pred = whole("DSP_IPM_CHECK_PRED", -1);
+  return s;
+}
+
+// development (DSP_IPM_DEBUG): the stream is synchronised after every step of the loop, so that a failing launch is named
+static hipError_t ipm_dbg(const IpmSettings &s, hipStream_t st, const char *what) {
+  if (!s.debug) return hipSuccess;
+  const hipError_t de = hipStreamSynchronize(st);
+  if (de != hipSuccess) fprintf(stderr, "[ipm] %s: %s\n", what, hipGetErrorString(de));
+  else if (s.debug > 1) fprintf(stderr, "[ipm] %s ok\n", what);
+  return de;
+}
+#define IPM_DBG(what) do { if ((e = ipm_dbg(s, st, what)) != hipSuccess) return e; } while (0)
+
+// ---- host: launch geometry --------------------------------------------------------------------------------------------------------------
+struct IpmGrids { dim3 grid, lanes; };      // the elementwise kernels (blocks of 4 waves x lane groups); one block per lane group
+constexpr dim3 kIpmBlk(256);
+
+// G lane groups in use (Bp / 64 until the lanes are packed: ipm_repack).
+//  nch: blocks per lane group of the elementwise kernels - enough waves to hide the gathers' latency (a wave owns a chunk of indices and
+//    walks it with a few loads in flight): 2048 blocks over the groups, at most kIpmMaxBlocks per group.  Round 5 stopped at 256: 1024 waves
+//    for a single group of 64 scenarios = one wave per SIMD, 7.6 ms per Newton iteration at 64 scenarios against 13.1 ms at 256.  The partial
+//    sums are per block (ipm_put), so the finish kernels walk as many as before.
+//  bz: workgroups per partition of the border kernels - enough of them for the chip while the lane groups are few (the one-wave reduced
+//    solve of half-bandwidth 8 reads partial set 0 only)
+//  ls: workgroups a lane group's walk is split over (IpmWork::ls)
+static IpmGrids ipm_geometry(IpmArgs &a, int G, const IpmSettings &s) {
+  const int P = a.P.parts.P;
+  a.w.G = G;
+  a.w.nch = 4 * std::max(16, std::min(s.max_blocks, 2048 / std::max(G, 1)));
+  a.w.bz = a.P.W <= 6 ? std::min(std::max(256 / (std::max(P - 1, 1) * std::max(G, 1)), 1), kIpmBorderSplit) : 1;
+  a.w.ls = 1;
+  while (a.w.ls < 4 && 2 * a.w.ls * G * std::max(P, 1) <= 256) a.w.ls *= 2;
+  return {dim3((unsigned)(a.w.nch / 4), (unsigned)G), dim3((unsigned)G)};
+}
+
+// ---- host: the banded factorisation and solves ------------------------------------------------------------------------------------------
+// The arguments of one walk: streams 0 .. nband - 1 are band arrays from `band` on, the others `x` (+ xstride each); every partition walks
+// `rows` rows (the last one `last_rows`), the first workgroup's partition is `part0`
+template <int NS>
+static SeqArgs<NS> ipm_seq_args(const IpmArgs &a, const IpmSettings &s, double *band, int nband, double *x, size_t xstride, int rows, int last_rows,
+                                int part0, int reverse, unsigned outmask) {
+  SeqArgs<NS> q{};
+  q.band = band; q.stride = (size_t)a.P.Mp * a.w.Bp; q.nband = nband; q.x = x; q.xstride = xstride;
+  q.rows = rows; q.last_rows = last_rows; q.nparts = a.P.parts.P; q.part0 = part0; q.reverse = reverse;
+  q.outmask = outmask;
+  q.Bp = a.w.Bp; q.state = a.w.state; q.lsplit = a.w.ls; q.dev_mode = s.seq_mode;
+  return q;
+}
+
+// one walk over `parts` partitions (grid.y): WV waves, the movers as SETS sets (k_seq)
 template <int NS, int R, class Body, int WV, int SETS>
-static hipError_t ipm_walk(const IpmArgs &a, SeqArgs<NS> q, const Body &body, int parts, hipStream_t st) {
-  q.Bp = a.w.Bp; q.state = a.w.state; q.lsplit = a.w.ls; q.dev_mode = ipm_seq_mode();
+static hipError_t ipm_walk(const IpmArgs &a, const SeqArgs<NS> &q, const Body &body, int parts, hipStream_t st) {
   const size_t lds = (size_t)2 * R * NS * 64 * sizeof(double);
   auto fn = k_seq<NS, R, Body, WV, SETS>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1442,149 +1441,173 @@ static hipError_t ipm_walk(const IpmArgs &a, SeqArgs<NS> q, const Body &body, in
 // the factorisation of the band in a.w.band (in place).  Time-parallel form (P > 1; dsp_ipm_seq.hpp): the interiors of the P partitions at
 // once, their spikes, then the separators' block-tridiagonal system.
 template <int W>
-static hipError_t ipm_factor(const IpmArgs &a, hipStream_t st) {
+static hipError_t ipm_factor(const IpmArgs &a, const IpmSettings &s, hipStream_t st) {
   const IpmParts &g = a.P.parts;
-  const size_t stride = (size_t)a.P.Mp * a.w.Bp;
   hipError_t e;
   {
     constexpr int NS = W + 1, R = (72 * 1024) / (NS * 512);
-    SeqArgs<NS> q{};
-    q.band = a.w.band; q.stride = stride; q.nband = NS; q.x = nullptr; q.xstride = 0;
-    q.rows = g.P > 1 ? g.Lp : a.P.Mp; q.last_rows = a.P.Mp - (g.P - 1) * g.Lp; q.nparts = g.P; q.part0 = 0; q.reverse = 0;
-    q.outmask = (1u << NS) - 1u;
+    const SeqArgs<NS> q = ipm_seq_args<NS>(a, s, a.w.band, NS, nullptr, 0, g.P > 1 ? g.Lp : a.P.Mp, a.P.Mp - (g.P - 1) * g.Lp, 0, 0, (1u << NS) - 1u);
     if ((e = ipm_walk<NS, R, FactorBody<W>, 8, 1>(a, q, FactorBody<W>{g.P > 1 ? a.w.sfin : nullptr, a.w.Bp, g.P}, g.P, st)) != hipSuccess) return e;
   }
   if (g.P <= 1) return hipSuccess;
   {
     constexpr int NS = 2 * W + 1, R = (72 * 1024) / (NS * 512), WV = W <= 6 ? 8 : 4;      // (W = 8: 100 doubles of state - one wave per SIMD)
-    SeqArgs<NS> q{};
-    q.band = a.w.band + (size_t)W * a.w.Bp; q.stride = stride; q.nband = W + 1; q.x = a.w.gs; q.xstride = stride;      // 1 / d_c, L(c + k, c): factor row c + W
-    q.rows = g.Lp; q.last_rows = g.cols(g.P - 1); q.nparts = g.P; q.part0 = 1; q.reverse = 0;
-    q.outmask = ((1u << W) - 1u) << (W + 1);
+    // 1 / d_c, L(c + k, c): factor row c + W; the spikes
+    const SeqArgs<NS> q = ipm_seq_args<NS>(a, s, a.w.band + (size_t)W * a.w.Bp, W + 1, a.w.gs, (size_t)a.P.Mp * a.w.Bp, g.Lp, g.cols(g.P - 1), 1, 0,
+                                           ((1u << W) - 1u) << (W + 1));
     if ((e = ipm_walk<NS, R, SpikeBody<W>, WV, 1>(a, q, SpikeBody<W>{a.w.cfin, a.w.Bp, g}, g.P - 1, st)) != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k_ipm_red_factor<W>, dim3((unsigned)a.w.G), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 
-static bool ipm_red_fed(int W) {
-  // (0: the one-wave reduced solve - comparison; half-bandwidth 8: 108 doubles per step do not fit a mover's registers)
-  return W <= 6 && !(getenv("DSP_IPM_RED_FED") && atoi(getenv("DSP_IPM_RED_FED")) == 0);
-}
-
 // x := B^-1 x for the [m][Bp] vector `x` (in place)
 template <int W>
-static hipError_t ipm_bsolve(const IpmArgs &a, double *x, hipStream_t st) {
+static hipError_t ipm_bsolve(const IpmArgs &a, const IpmSettings &s, double *x, hipStream_t st) {
   const IpmParts &g = a.P.parts;
-  const size_t stride = (size_t)a.P.Mp * a.w.Bp;
   const dim3 border((unsigned)(std::max(g.P - 1, 1) * a.w.bz), (unsigned)a.w.G);
-  const bool fed = ipm_red_fed(W);
-  static const int one_set = getenv("DSP_IPM_SEQ_SETS") ? atoi(getenv("DSP_IPM_SEQ_SETS")) == 1 : 0;      // development
+  const int rows = g.P > 1 ? g.Lp : a.P.m, last_rows = g.cols(g.P - 1);
   hipError_t e;
   {
     constexpr int NS = W + 1, R = (72 * 1024) / (NS * 512);
-    SeqArgs<NS> q{};
-    q.band = a.w.band + ((size_t)a.P.Mp + W) * a.w.Bp; q.stride = stride; q.nband = W; q.x = x; q.xstride = 0;     // L(i + k + 1, i): factor row i + W
-    q.rows = g.P > 1 ? g.Lp : a.P.m; q.last_rows = g.cols(g.P - 1); q.nparts = g.P; q.part0 = 0; q.reverse = 0;
-    q.outmask = 1u << W;
-    e = one_set ? ipm_walk<NS, R, ForwardBody<W>, 8, 1>(a, q, ForwardBody<W>{}, g.P, st) : ipm_walk<NS, R, ForwardBody<W>, 16, 2>(a, q, ForwardBody<W>{}, g.P, st);
-    if (e != hipSuccess) return e;
+    // L(i + k + 1, i): factor row i + W
+    const SeqArgs<NS> q = ipm_seq_args<NS>(a, s, a.w.band + ((size_t)a.P.Mp + W) * a.w.Bp, W, x, 0, rows, last_rows, 0, 0, 1u << W);
+    if ((e = ipm_walk<NS, R, ForwardBody<W>, 16, 2>(a, q, ForwardBody<W>{}, g.P, st)) != hipSuccess) return e;
   }
   if (g.P > 1) {
     constexpr int DW = W <= 6 ? 16 : 8;
     hipLaunchKernelGGL((k_ipm_border_dot<W, DW>), border, dim3(64 * DW), 0, st, a, (const double *)x);
-    if constexpr (W <= 6) if (fed) hipLaunchKernelGGL(k_ipm_red_solve_fed<W>, dim3((unsigned)(a.w.G * kRedLaneSplit)), dim3(64 * (kRedMovers + 1)), 0, st, a, x);
-    if (!fed) hipLaunchKernelGGL(k_ipm_red_solve<W>, dim3((unsigned)a.w.G), dim3(64), 0, st, a, x);
+    // (half-bandwidth 8: the fed kernel's 108 doubles per step do not fit a mover's registers - the one-wave reduced solve)
+    if constexpr (W <= 6) hipLaunchKernelGGL(k_ipm_red_solve_fed<W>, dim3((unsigned)(a.w.G * kRedLaneSplit)), dim3(64 * (kRedMovers + 1)), 0, st, a, x);
+    else hipLaunchKernelGGL(k_ipm_red_solve<W>, dim3((unsigned)a.w.G), dim3(64), 0, st, a, x);
     hipLaunchKernelGGL(k_ipm_border_apply<W>, border, dim3(64 * kIpmBorderWaves), 0, st, a, x);
   }
   {
     constexpr int NS = W + 2, R = (72 * 1024) / (NS * 512);
-    SeqArgs<NS> q{};
-    q.band = a.w.band + (size_t)W * a.w.Bp; q.stride = stride; q.nband = W + 1; q.x = x; q.xstride = 0;               // 1 / d_i, then L(i + k, i): factor row i + W
-    q.rows = g.P > 1 ? g.Lp : a.P.m; q.last_rows = g.cols(g.P - 1); q.nparts = g.P; q.part0 = 0; q.reverse = 1;
-    q.outmask = 1u << (W + 1);
-    e = one_set ? ipm_walk<NS, R, BackwardBody<W>, 8, 1>(a, q, BackwardBody<W>{}, g.P, st) : ipm_walk<NS, R, BackwardBody<W>, 16, 2>(a, q, BackwardBody<W>{}, g.P, st);
-    if (e != hipSuccess) return e;
+    // 1 / d_i, then L(i + k, i): factor row i + W
+    const SeqArgs<NS> q = ipm_seq_args<NS>(a, s, a.w.band + (size_t)W * a.w.Bp, W + 1, x, 0, rows, last_rows, 0, 1, 1u << (W + 1));
+    if ((e = ipm_walk<NS, R, BackwardBody<W>, 16, 2>(a, q, BackwardBody<W>{}, g.P, st)) != hipSuccess) return e;
   }
   return hipGetLastError();
+}
+
+// ---- host: the pieces of a Newton iteration -----------------------------------------------------------------------------------------------
+// a.w.wat = Abar' vec of the wide columns
+static void ipm_wide_aty(const IpmArgs &a, const IpmGrids &g, hipStream_t st, const double *vec) {
+  if (a.P.K == 0) return;
+  hipLaunchKernelGGL(k_ipm_wide_aty, g.grid, kIpmBlk, 0, st, a, vec);
+  hipLaunchKernelGGL(k_ipm_wide_aty_finish, g.lanes, dim3(64 * kFinW), 0, st, a);
+}
+
+// a.w.q = rhs - N dy: the residual of the full normal equations for the direction in a.w.dy
+static void ipm_newton_residual(const IpmArgs &a, const IpmGrids &g, hipStream_t st) {
+  ipm_wide_aty(a, g, st, a.w.dy);
+  hipLaunchKernelGGL(k_ipm_ref_cols, g.grid, kIpmBlk, 0, st, a);
+  hipLaunchKernelGGL(k_ipm_ref_rows, g.grid, kIpmBlk, 0, st, a);
 }
 
 // dy = (A Theta A')^-1 rhs (a.w.q holds the right-hand side on entry and is overwritten); iterative refinement on the full normal
 // equations while some scenario's residual is above ITS tolerance (k_ipm_resflag; max norms) (at most 3 steps); returns the steps taken
 template <int W>
-static hipError_t ipm_nsolve(StreamSolver *S, const IpmArgs &a, hipStream_t st, int *steps, bool check = true) {
-  const dim3 blk(256), grid((unsigned)(a.w.nch / 4), (unsigned)a.w.G), lanes((unsigned)a.w.G);
+static hipError_t ipm_nsolve(IpmState *I, const IpmArgs &a, const IpmSettings &s, const IpmGrids &g, hipStream_t st, int *steps, bool check) {
   hipError_t e;
   *steps = 0;
   for (int r = 0; r <= (check ? 3 : 0); ++r) {
     if (r > 0) {
-      if (a.P.K > 0) { hipLaunchKernelGGL(k_ipm_wide_aty, grid, blk, 0, st, a, (const double *)a.w.dy); hipLaunchKernelGGL(k_ipm_wide_aty_finish, lanes, dim3(64 * kFinW), 0, st, a); }
-      hipLaunchKernelGGL(k_ipm_ref_cols, grid, blk, 0, st, a);
-      hipLaunchKernelGGL(k_ipm_ref_rows, grid, blk, 0, st, a);
+      ipm_newton_residual(a, g, st);
       if ((e = hipMemsetAsync(a.w.counts + 3, 0, sizeof(int), st)) != hipSuccess) return e;
-      hipLaunchKernelGGL(k_ipm_resflag, lanes, dim3(64 * kFinW), 0, st, a, a.reftol);
-      if ((e = hipMemcpyAsync(S->ipm->counts_host + 3, a.w.counts + 3, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+      hipLaunchKernelGGL(k_ipm_resflag, g.lanes, dim3(64 * kFinW), 0, st, a, a.reftol);
+      if ((e = hipMemcpyAsync(I->counts_host + 3, a.w.counts + 3, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
       if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-      if (S->ipm->counts_host[3] == 0) break;
+      if (I->counts_host[3] == 0) break;
       *steps = r;
     }
-    if ((e = ipm_bsolve<W>(a, a.w.q, st)) != hipSuccess) return e;
+    if ((e = ipm_bsolve<W>(a, s, a.w.q, st)) != hipSuccess) return e;
     if (a.P.K > 0) {
-      hipLaunchKernelGGL(k_ipm_wood_part, grid, blk, 0, st, a, 1);
-      hipLaunchKernelGGL(k_ipm_wood_g, lanes, dim3(64 * kFinW), 0, st, a);
+      hipLaunchKernelGGL(k_ipm_wood_part, g.grid, kIpmBlk, 0, st, a, 1);
+      hipLaunchKernelGGL(k_ipm_wood_g, g.lanes, dim3(64 * kFinW), 0, st, a);
     }
     else if ((e = hipMemsetAsync(a.w.tk, 0, kIpmMaxK * a.w.Bp * sizeof(double), st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ipm_wood_axpy, grid, blk, 0, st, a, r > 0 ? 1 : 0);
+    hipLaunchKernelGGL(k_ipm_wood_axpy, g.grid, kIpmBlk, 0, st, a, r > 0 ? 1 : 0);
   }
   return hipGetLastError();
 }
 
-static int g_ipm_debug = 0;
-// development: one lane of a scenario-minor array as raw doubles under $DSP_IPM_DUMP/
-static void ipm_dump(const char *name, const double *dev, size_t rows, size_t Bp, int lane, hipStream_t st) {
-  const char *dir = getenv("DSP_IPM_DUMP");
-  if (!dir) return;
-  (void)hipStreamSynchronize(st);
-  std::vector<double> h(rows);
-  (void)hipMemcpy2D(h.data(), 8, dev + lane, Bp * 8, 8, rows, hipMemcpyDeviceToHost);
-  char path[512];
-  snprintf(path, sizeof(path), "%s/ipm_%s.bin", dir, name);
-  FILE *f = fopen(path, "wb");
-  if (f) { fwrite(h.data(), 8, rows, f); fclose(f); }
+// the starting point (k_ipm_setup) and the per-lane scalars and counters
+static hipError_t ipm_start(const IpmArgs &a, const IpmGrids &g, hipStream_t st) {
+  const hipError_t e = hipMemsetAsync(a.w.counts, 0, 8 * sizeof(int), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_ipm_begin, g.lanes, dim3(64), 0, st, a, 0);
+  hipLaunchKernelGGL(k_ipm_cmax, g.grid, kIpmBlk, 0, st, a);
+  hipLaunchKernelGGL(k_ipm_cmax_finish, g.lanes, dim3(64 * kFinW), 0, st, a);
+  hipLaunchKernelGGL(k_ipm_setup, g.grid, kIpmBlk, 0, st, a);
+  hipLaunchKernelGGL(k_ipm_begin, g.lanes, dim3(64), 0, st, a, 1);
+  return hipSuccess;
 }
-#define IPM_DBG(what)                                                                                                   \
-  do {                                                                                                                  \
-    if (g_ipm_debug) {                                                                                                  \
-      hipError_t de = hipStreamSynchronize(st);                                                                         \
-      if (de != hipSuccess) { fprintf(stderr, "[ipm] %s: %s\n", what, hipGetErrorString(de)); return de; }             \
-      if (g_ipm_debug > 1) fprintf(stderr, "[ipm] %s ok\n", what);                                                     \
-    }                                                                                                                   \
-  } while (0)
 
-// workgroups per partition of the border kernels: enough of them for the chip while the lane groups are few (IpmWork::bz)
-static int ipm_lane_split(int G, int P) {
-  int ls = 1;
-  if (getenv("DSP_IPM_LS")) ls = atoi(getenv("DSP_IPM_LS"));
-  else while (ls < 4 && 2 * ls * G * std::max(P, 1) <= 256) ls *= 2;
-  return ls == 2 || ls == 4 ? ls : 1;
+// the residuals of the iterate AND its KKT sums (k_ipm_resid): the termination test rides on the residual kernel's gathers
+static void ipm_residual(const IpmArgs &a, const IpmGrids &g, hipStream_t st) {
+  ipm_wide_aty(a, g, st, a.w.y);
+  hipLaunchKernelGGL(k_ipm_resid, g.grid, kIpmBlk, 0, st, a);
+  hipLaunchKernelGGL(k_ipm_mu, g.lanes, dim3(64 * kFinW), 0, st, a);
 }
-static int ipm_border_split(int G, int P, int W) {
-  if (!ipm_red_fed(W)) return 1;                                                          // (the one-wave reduced solve reads partial set 0 only)
-  if (getenv("DSP_IPM_BZ")) return std::min(std::max(atoi(getenv("DSP_IPM_BZ")), 1), kIpmBorderSplit);
-  return std::min(std::max(256 / (std::max(P - 1, 1) * std::max(G, 1)), 1), kIpmBorderSplit);
+
+// k_ipm_decide on those sums; counts_host = finished, solved, lanes in the end game, (refinement flag), steps to take back
+static hipError_t ipm_decide(IpmState *I, const IpmArgs &a, const IpmSettings &s, const IpmGrids &g, hipStream_t st) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(a.w.counts + 2, 0, 3 * sizeof(int), st)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_ipm_decide, g.lanes, dim3(64 * kFinW), 0, st, a);
+  IPM_DBG("decide");
+  if ((e = hipMemcpyAsync(I->counts_host, a.w.counts, 5 * sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+  return hipStreamSynchronize(st);
+}
+
+// the wide columns: Bbar^-1 Abar_k per column, then the K x K matrix of Sherman-Morrison-Woodbury per scenario
+template <int W>
+static hipError_t ipm_woodbury(const IpmArgs &a, const IpmSettings &s, const IpmGrids &g, hipStream_t st) {
+  hipError_t e;
+  for (int k = 0; k < a.P.K; ++k) {
+    hipLaunchKernelGGL(k_ipm_wide_rhs, g.grid, kIpmBlk, 0, st, a, k);
+    if ((e = ipm_bsolve<W>(a, s, a.w.q, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ipm_copy_m, g.grid, kIpmBlk, 0, st, a, (const double *)a.w.q, a.w.biad + (size_t)k * a.P.m * a.w.Bp);
+  }
+  if (a.P.K > 0) {
+    hipLaunchKernelGGL(k_ipm_wood_part, g.grid, kIpmBlk, 0, st, a, 0);
+    hipLaunchKernelGGL(k_ipm_wood_s, g.lanes, kIpmBlk, 0, st, a);
+  }
+  return hipSuccess;
+}
+
+static void ipm_trace_newton_residual(const IpmArgs &a, const IpmSettings &s, const IpmGrids &g, hipStream_t st, int mode);
+
+// One direction and its step lengths: the predictor (mode 0: it only sets sigma and the second-order terms) or the corrector (mode 1).
+// `check`: the solve is checked against the full normal equations and refined; *refine = the most refinement steps a solve of this pass took
+template <int W>
+static hipError_t ipm_direction(IpmState *I, const IpmArgs &a, const IpmSettings &s, const IpmGrids &g, hipStream_t st, int mode, bool check, int *refine) {
+  hipError_t e;
+  hipLaunchKernelGGL(k_ipm_rhs, g.grid, kIpmBlk, 0, st, a, mode);                   // (rt / tn: mode 0 by k_ipm_resid, mode 1 by k_ipm_dir's mode 0)
+  IPM_DBG("rhs");
+  int steps = 0;
+  if ((e = ipm_nsolve<W>(I, a, s, g, st, &steps, check)) != hipSuccess) return e;
+  *refine = std::max(*refine, steps);
+  IPM_DBG("nsolve");
+  if (s.trace && s.debug) ipm_trace_newton_residual(a, s, g, st, mode);
+  ipm_wide_aty(a, g, st, a.w.dy);
+  hipLaunchKernelGGL(k_ipm_dir, g.grid, kIpmBlk, 0, st, a, mode);
+  hipLaunchKernelGGL(k_ipm_steps, g.lanes, dim3(64 * kFinW), 0, st, a, mode);
+  return hipSuccess;
 }
 
 // The scenarios still iterating (`active` of them) are packed into the first lanes: a Newton iteration costs what its lane groups cost, and
 // the members of a batch finish over a 3 x range of iteration counts (40 .. 144 on the year-long wind + battery family).  What persists
 // from one iteration to the next is packed - the iterate (v, z, f, y), the problem data (l, u, cb), the objective scale, the per-lane
 // counters and the lane -> scenario map; everything else (Theta, residuals, the band and its factor, the directions) is recomputed.
-// Solved lanes are exported first; the stride of the arrays (Bp) stays.
-static hipError_t ipm_repack(IpmState *I, IpmArgs &a, hipStream_t st, int active) {
+// Solved lanes are exported first; the stride of the arrays (Bp) stays.  `g`: the grids before, on return those of the groups left.
+static hipError_t ipm_repack(IpmState *I, IpmArgs &a, const IpmSettings &s, IpmGrids &g, hipStream_t st, int active) {
   const int n_old = a.w.G * 64, G_new = (active + 63) / 64, n_new = G_new * 64;
-  const dim3 blk(256), grid((unsigned)(a.w.nch / 4), (unsigned)a.w.G);
   hipError_t e;
-  hipLaunchKernelGGL(k_ipm_export, grid, blk, 0, st, a);
-  hipLaunchKernelGGL(k_ipm_exported, dim3((unsigned)a.w.G), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_ipm_export, g.grid, kIpmBlk, 0, st, a);
+  hipLaunchKernelGGL(k_ipm_exported, g.lanes, dim3(64), 0, st, a);
   if ((e = hipMemcpyAsync(I->perm_host, a.w.state, (size_t)n_old * sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
   if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
   std::vector<int> perm((size_t)n_new, -1);
@@ -1601,161 +1624,106 @@ static hipError_t ipm_repack(IpmState *I, IpmArgs &a, hipStream_t st, int active
   for (int *arr : {a.w.iters, a.w.stall, a.w.endg, a.w.sid}) hipLaunchKernelGGL(k_ipm_pack<int>, dim3(1), tb, 0, st, arr, a.w.Bp, (const int *)a.w.perm, n_new);
   hipLaunchKernelGGL(k_ipm_after_pack, dim3((unsigned)G_new), dim3(64), 0, st, a, active, n_new);
   if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;                      // (perm_host is reused by the next repack)
-  a.w.G = G_new;
-  a.w.nch = 4 * ipm_blocks(G_new);
-  a.w.bz = ipm_border_split(G_new, a.P.parts.P, a.P.W);
-  a.w.ls = ipm_lane_split(G_new, a.P.parts.P);
+  g = ipm_geometry(a, G_new, s);
   return hipGetLastError();
 }
 
+// ---- host: development output (DSP_IPM_TRACE; tests/test_hip_ipm.py and tools/gpu_ipm_*.py read these lines) -------------------------------
+// the traced lane's scalars and the batch's counters as pass `it` found them
+static void ipm_trace_lane(const IpmState *I, const IpmArgs &a, const IpmSettings &s, int it, int refine) {
+  double sc[SC_COUNT];
+  for (int q = 0; q < SC_COUNT; ++q) (void)hipMemcpy(&sc[q], a.w.sc + (size_t)q * a.w.Bp + (s.trace - 1), sizeof(double), hipMemcpyDeviceToHost);
+  StreamCtrl c0{};
+  (void)hipMemcpy(&c0, a.sw.ctrl + (s.trace - 1), sizeof(StreamCtrl), hipMemcpyDeviceToHost);
+  fprintf(stderr, "[ipm] it %d lane %d: mu %.3e sigma*mu %.3e ap %.3f ad %.3f rp %.2e rd %.2e rg %.2e | finished %d solved %d endgame %d refine %d\n", it - 1, s.trace - 1,
+          sc[SC_MU], sc[SC_SIGMU], sc[SC_AP], sc[SC_AD], c0.last_rp, c0.last_rd, c0.last_rg, I->counts_host[0], I->counts_host[1], I->counts_host[2], refine);
+}
+
+// (with DSP_IPM_DEBUG) relative residual of the Newton system for the traced lane
+static void ipm_trace_newton_residual(const IpmArgs &a, const IpmSettings &s, const IpmGrids &g, hipStream_t st, int mode) {
+  ipm_newton_residual(a, g, st);
+  std::vector<double> hq(a.P.m), hr(a.P.m), hd(a.P.m);
+  (void)hipStreamSynchronize(st);
+  (void)hipMemcpy2D(hq.data(), 8, a.w.q + (s.trace - 1), a.w.Bp * 8, 8, a.P.m, hipMemcpyDeviceToHost);
+  (void)hipMemcpy2D(hr.data(), 8, a.w.rhs + (s.trace - 1), a.w.Bp * 8, 8, a.P.m, hipMemcpyDeviceToHost);
+  (void)hipMemcpy2D(hd.data(), 8, a.w.dy + (s.trace - 1), a.w.Bp * 8, 8, a.P.m, hipMemcpyDeviceToHost);
+  double nq = 0, nr = 0, nd = 0;
+  for (int i = 0; i < a.P.m; ++i) { nq += hq[i] * hq[i]; nr += hr[i] * hr[i]; nd += hd[i] * hd[i]; }
+  fprintf(stderr, "[ipm]   mode %d: |rhs| %.3e |dy| %.3e |rhs - N dy| / |rhs| %.3e\n", mode, sqrt(nr), sqrt(nd), sqrt(nq) / fmax(sqrt(nr), 1e-300));
+}
+
+// how every lane ended
+static void ipm_trace_lanes(const IpmArgs &a, int undone) {
+  std::vector<int> hs(a.w.Bp), hi(a.w.Bp);
+  (void)hipMemcpy(hs.data(), a.w.state, a.w.Bp * sizeof(int), hipMemcpyDeviceToHost);
+  (void)hipMemcpy(hi.data(), a.w.iters, a.w.Bp * sizeof(int), hipMemcpyDeviceToHost);
+  fprintf(stderr, "[ipm] steps taken back: %d\n", undone);
+  fprintf(stderr, "[ipm] lanes (state:newton iterations):");
+  for (int q = 0; q < a.w.B; ++q) fprintf(stderr, " %d:%d", hs[q], hi[q]);
+  fprintf(stderr, "\n");
+}
+
+// ---- host: the Newton loop ---------------------------------------------------------------------------------------------------------------
+// Pass `it` opens with the residuals of the iterate that `it - 1` steps have left AND its KKT sums, decides on them - a scenario that passes
+// leaves here -, and only then takes step `it`.  A step taken back or a packing of the lanes changes what the residual kernel saw: it runs again.
 template <int W>
-static hipError_t ipm_loop(StreamSolver *S, IpmArgs &a, hipStream_t st, bool *all_solved, int *newton, int *n_solved) {
+static hipError_t ipm_loop(StreamSolver *S, IpmArgs &a, const IpmSettings &s, hipStream_t st, bool *all_solved, int *newton, int *n_solved) {
   IpmState *I = S->ipm;
-  a.w.G = (int)(a.w.Bp / 64);
-  a.w.nch = 4 * ipm_blocks(a.w.G);
-  a.w.bz = ipm_border_split(a.w.G, a.P.parts.P, a.P.W);
-  a.w.ls = ipm_lane_split(a.w.G, a.P.parts.P);
-  const dim3 blk(256);
-  dim3 grid((unsigned)(a.w.nch / 4), (unsigned)a.w.G), lanes((unsigned)a.w.G);
-  // DSP_IPM_COMPACT=0: every scenario keeps its lane to the end of the solve (measurement); groups of more than 1024 lanes: not packed
-  const bool compact = !(getenv("DSP_IPM_COMPACT") && atoi(getenv("DSP_IPM_COMPACT")) == 0) && a.w.Bp <= 1024;
-  int repacks = 0;
-  const int trace = getenv("DSP_IPM_TRACE") ? atoi(getenv("DSP_IPM_TRACE")) : 0;      // (development; read at every solve: tests switch it on)
-  g_ipm_debug = getenv("DSP_IPM_DEBUG") ? atoi(getenv("DSP_IPM_DEBUG")) : 0;
+  IpmGrids g = ipm_geometry(a, (int)(a.w.Bp / 64), s);
   hipError_t e;
-  if ((e = hipMemsetAsync(a.w.counts, 0, 8 * sizeof(int), st)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_ipm_begin, lanes, dim3(64), 0, st, a, 0);
-  hipLaunchKernelGGL(k_ipm_cmax, grid, blk, 0, st, a);
-  hipLaunchKernelGGL(k_ipm_cmax_finish, lanes, dim3(64 * kFinW), 0, st, a);
-  hipLaunchKernelGGL(k_ipm_setup, grid, blk, 0, st, a);
-  hipLaunchKernelGGL(k_ipm_begin, lanes, dim3(64), 0, st, a, 1);
+  if ((e = ipm_start(a, g, st)) != hipSuccess) return e;
   IPM_DBG("setup");
-  int refine = 0, it = 0, undone = 0;
-  // the predictor's system (it only sets sigma and the second-order terms) is checked / refined once some scenario runs under the strict
-  // tolerances, not before: its check is 3 - 4 % of the solve and has never asked for a step (profiles/r70i_check_pred.log)
-  const int check_pred_env = getenv("DSP_IPM_CHECK_PRED") ? atoi(getenv("DSP_IPM_CHECK_PRED")) : -1;
-  int lanes_total = (int)a.w.Bp;
-  // Pass `it` opens with the residuals of the iterate that `it - 1` steps have left AND its KKT sums (k_ipm_resid), decides on them - a
-  // scenario that passes leaves here -, and only then takes step `it`: the test rides on the residual kernel's gathers instead of a pass
-  // of its own after the update.  A step taken back or a packing of the lanes changes what the residual kernel saw: it runs again.
-  auto residual = [&]() {
-    if (a.P.K > 0) { hipLaunchKernelGGL(k_ipm_wide_aty, grid, blk, 0, st, a, (const double *)a.w.y); hipLaunchKernelGGL(k_ipm_wide_aty_finish, lanes, dim3(64 * kFinW), 0, st, a); }
-    hipLaunchKernelGGL(k_ipm_resid, grid, blk, 0, st, a);
-    hipLaunchKernelGGL(k_ipm_mu, lanes, dim3(64 * kFinW), 0, st, a);
-  };
+  int refine = 0, it = 0, undone = 0, repacks = 0, lanes_total = (int)a.w.Bp;
   for (it = 1; it <= a.max_it + 1; ++it) {
     a.it = it;
-    residual();
+    ipm_residual(a, g, st);
     IPM_DBG("resid");
-    if ((e = hipMemsetAsync(a.w.counts + 2, 0, 3 * sizeof(int), st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ipm_decide, lanes, dim3(64 * kFinW), 0, st, a);
-    IPM_DBG("decide");
-    if ((e = hipMemcpyAsync(I->counts_host, a.w.counts, 5 * sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+    if ((e = ipm_decide(I, a, s, g, st)) != hipSuccess) return e;
     bool again = false;
     if (I->counts_host[4] > 0) {                        // steps taken back (k_ipm_decide; the directions of the previous pass are still in place)
-      hipLaunchKernelGGL(k_ipm_undo, grid, blk, 0, st, a);
-      hipLaunchKernelGGL(k_ipm_undone, lanes, dim3(64), 0, st, a);
+      hipLaunchKernelGGL(k_ipm_undo, g.grid, kIpmBlk, 0, st, a);
+      hipLaunchKernelGGL(k_ipm_undone, g.lanes, dim3(64), 0, st, a);
       undone += I->counts_host[4];
       again = true;
-      if (trace) fprintf(stderr, "[ipm] it %d: %d step(s) taken back\n", it - 1, I->counts_host[4]);
+      if (s.trace) fprintf(stderr, "[ipm] it %d: %d step(s) taken back\n", it - 1, I->counts_host[4]);
     }
-    if (trace) {
-      double sc[SC_COUNT];
-      for (int q = 0; q < SC_COUNT; ++q) (void)hipMemcpy(&sc[q], a.w.sc + (size_t)q * a.w.Bp + (trace - 1), sizeof(double), hipMemcpyDeviceToHost);
-      StreamCtrl c0{};
-      (void)hipMemcpy(&c0, a.sw.ctrl + (trace - 1), sizeof(StreamCtrl), hipMemcpyDeviceToHost);
-      fprintf(stderr, "[ipm] it %d lane %d: mu %.3e sigma*mu %.3e ap %.3f ad %.3f rp %.2e rd %.2e rg %.2e | finished %d solved %d endgame %d refine %d\n", it - 1, trace - 1,
-              sc[SC_MU], sc[SC_SIGMU], sc[SC_AP], sc[SC_AD], c0.last_rp, c0.last_rd, c0.last_rg, I->counts_host[0], I->counts_host[1], I->counts_host[2], refine);
-    }
+    if (s.trace) ipm_trace_lane(I, a, s, it, refine);
     if (I->counts_host[0] >= lanes_total || it > a.max_it) break;
     refine = 0;
-    {
-      const int active = lanes_total - I->counts_host[0];
-      if (compact && a.w.G > 1 && active <= 64 * (a.w.G - 1)) {
-        if ((e = ipm_repack(I, a, st, active)) != hipSuccess) return e;
-        lanes_total = a.w.G * 64;
-        grid = dim3((unsigned)(a.w.nch / 4), (unsigned)a.w.G); lanes = dim3((unsigned)a.w.G);
-        ++repacks;
-        again = true;
-        if (trace) fprintf(stderr, "[ipm] it %d: %d scenarios still iterating packed into %d group(s)\n", it - 1, active, a.w.G);
-      }
+    const int active = lanes_total - I->counts_host[0];
+    if (s.compact && a.w.G > 1 && active <= 64 * (a.w.G - 1)) {
+      if ((e = ipm_repack(I, a, s, g, st, active)) != hipSuccess) return e;
+      lanes_total = a.w.G * 64;
+      ++repacks;
+      again = true;
+      if (s.trace) fprintf(stderr, "[ipm] it %d: %d scenarios still iterating packed into %d group(s)\n", it - 1, active, a.w.G);
     }
-    if (again) residual();
-    hipLaunchKernelGGL(k_ipm_assemble, grid, blk, 0, st, a);
+    if (again) ipm_residual(a, g, st);
+    hipLaunchKernelGGL(k_ipm_assemble, g.grid, kIpmBlk, 0, st, a);
     IPM_DBG("assemble");
-    if (it == 1 && trace) {
-      const size_t N = (size_t)a.P.n + a.P.m;
-      ipm_dump("th", a.w.th, N, a.w.Bp, trace - 1, st); ipm_dump("band_in", a.w.band, (size_t)(W + 1) * a.P.Mp, a.w.Bp, trace - 1, st);
-      ipm_dump("rp", a.w.rp, a.P.m, a.w.Bp, trace - 1, st); ipm_dump("rd", a.w.rd, N, a.w.Bp, trace - 1, st);
-      ipm_dump("v", a.w.v, N, a.w.Bp, trace - 1, st); ipm_dump("l", a.w.l, N, a.w.Bp, trace - 1, st); ipm_dump("u", a.w.u, N, a.w.Bp, trace - 1, st);
-      ipm_dump("cb", a.w.cb, N, a.w.Bp, trace - 1, st);
-    }
-    if ((e = ipm_factor<W>(a, st)) != hipSuccess) return e;
+    if ((e = ipm_factor<W>(a, s, st)) != hipSuccess) return e;
     IPM_DBG("factor");
-    for (int k = 0; k < a.P.K; ++k) {
-      hipLaunchKernelGGL(k_ipm_wide_rhs, grid, blk, 0, st, a, k);
-      if ((e = ipm_bsolve<W>(a, a.w.q, st)) != hipSuccess) return e;
-      hipLaunchKernelGGL(k_ipm_copy_m, grid, blk, 0, st, a, (const double *)a.w.q, a.w.biad + (size_t)k * a.P.m * a.w.Bp);
-    }
-    if (a.P.K > 0) {
-      hipLaunchKernelGGL(k_ipm_wood_part, grid, blk, 0, st, a, 0);
-      hipLaunchKernelGGL(k_ipm_wood_s, lanes, blk, 0, st, a);
-    }
+    if ((e = ipm_woodbury<W>(a, s, g, st)) != hipSuccess) return e;
     IPM_DBG("woodbury");
-    if (it == 1 && trace) {
-      ipm_dump("band_out", a.w.band, (size_t)(W + 1) * a.P.Mp, a.w.Bp, trace - 1, st);
-      ipm_dump("biad", a.w.biad, (size_t)std::max(a.P.K, 1) * a.P.m, a.w.Bp, trace - 1, st);
-      ipm_dump("sinv", a.w.sinv, (size_t)kIpmMaxK * kIpmMaxK, a.w.Bp, trace - 1, st);
-    }
-    for (int mode = 0; mode < 2; ++mode) {
-      hipLaunchKernelGGL(k_ipm_rhs, grid, blk, 0, st, a, mode);                     // (rt / tn: mode 0 by k_ipm_resid, mode 1 by k_ipm_dir's mode 0)
-      IPM_DBG("rhs");
-      { int steps = 0; if ((e = ipm_nsolve<W>(S, a, st, &steps, mode == 1 || (check_pred_env >= 0 ? check_pred_env != 0 : undone > 0))) != hipSuccess) return e; refine = std::max(refine, steps); }
-      IPM_DBG("nsolve");
-      if (it == 1 && trace && mode == 0) {
-        ipm_dump("rhs", a.w.rhs, a.P.m, a.w.Bp, trace - 1, st); ipm_dump("dy", a.w.dy, a.P.m, a.w.Bp, trace - 1, st);
-        ipm_dump("rt", a.w.rt, (size_t)a.P.n + a.P.m, a.w.Bp, trace - 1, st);
-      }
-      if (trace && g_ipm_debug) {                       // development: relative residual of the Newton system for the traced lane
-        if (a.P.K > 0) { hipLaunchKernelGGL(k_ipm_wide_aty, grid, blk, 0, st, a, (const double *)a.w.dy); hipLaunchKernelGGL(k_ipm_wide_aty_finish, lanes, dim3(64 * kFinW), 0, st, a); }
-        hipLaunchKernelGGL(k_ipm_ref_cols, grid, blk, 0, st, a);
-        hipLaunchKernelGGL(k_ipm_ref_rows, grid, blk, 0, st, a);
-        std::vector<double> hq(a.P.m), hr(a.P.m), hd(a.P.m);
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy2D(hq.data(), 8, a.w.q + (trace - 1), a.w.Bp * 8, 8, a.P.m, hipMemcpyDeviceToHost);
-        (void)hipMemcpy2D(hr.data(), 8, a.w.rhs + (trace - 1), a.w.Bp * 8, 8, a.P.m, hipMemcpyDeviceToHost);
-        (void)hipMemcpy2D(hd.data(), 8, a.w.dy + (trace - 1), a.w.Bp * 8, 8, a.P.m, hipMemcpyDeviceToHost);
-        double nq = 0, nr = 0, nd = 0;
-        for (int i = 0; i < a.P.m; ++i) { nq += hq[i] * hq[i]; nr += hr[i] * hr[i]; nd += hd[i] * hd[i]; }
-        fprintf(stderr, "[ipm]   mode %d: |rhs| %.3e |dy| %.3e |rhs - N dy| / |rhs| %.3e\n", mode, sqrt(nr), sqrt(nd), sqrt(nq) / fmax(sqrt(nr), 1e-300));
-      }
-      if (a.P.K > 0) { hipLaunchKernelGGL(k_ipm_wide_aty, grid, blk, 0, st, a, (const double *)a.w.dy); hipLaunchKernelGGL(k_ipm_wide_aty_finish, lanes, dim3(64 * kFinW), 0, st, a); }
-      hipLaunchKernelGGL(k_ipm_dir, grid, blk, 0, st, a, mode);
-      hipLaunchKernelGGL(k_ipm_steps, lanes, dim3(64 * kFinW), 0, st, a, mode);
-    }
+    // the predictor's system is checked / refined once some scenario runs under the strict tolerances, not before: its check is 3 - 4 % of
+    // the solve and has never asked for a step (profiles/r70i_check_pred.log)
+    const bool check_pred = s.check_pred >= 0 ? s.check_pred != 0 : undone > 0;
+    if ((e = ipm_direction<W>(I, a, s, g, st, 0, check_pred, &refine)) != hipSuccess) return e;
+    if ((e = ipm_direction<W>(I, a, s, g, st, 1, true, &refine)) != hipSuccess) return e;
     IPM_DBG("direction");
-    hipLaunchKernelGGL(k_ipm_update, grid, blk, 0, st, a);
+    hipLaunchKernelGGL(k_ipm_update, g.grid, kIpmBlk, 0, st, a);
     IPM_DBG("update");
   }
   I->last_repacks = repacks;
   *newton = std::min(it - 1, a.max_it);
   IPM_DBG("loop");
-  if (trace) {
-    std::vector<int> hs(a.w.Bp), hi(a.w.Bp);
-    (void)hipMemcpy(hs.data(), a.w.state, a.w.Bp * sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipMemcpy(hi.data(), a.w.iters, a.w.Bp * sizeof(int), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[ipm] steps taken back: %d\n", undone);
-    fprintf(stderr, "[ipm] lanes (state:newton iterations):");
-    for (int q = 0; q < a.w.B; ++q) fprintf(stderr, " %d:%d", hs[q], hi[q]);
-    fprintf(stderr, "\n");
-  }
+  if (s.trace) ipm_trace_lanes(a, undone);
   // Per scenario: what this method solved is exported (ctrl.done = 1, x+ / y+ in the scenario-major workspace) and stays solved; the
   // scenarios it gave up on (state 2: breakdown, steps that stay tiny - an LP without a solution -, the iteration limit, free columns)
   // are untouched, and the caller hands exactly those to the PDHG forms, which carry the certificates (stream_solve_locked).
   *all_solved = I->counts_host[1] >= a.w.B;
   *n_solved = I->counts_host[1];
-  hipLaunchKernelGGL(k_ipm_export, grid, blk, 0, st, a);        // (lanes exported before a packing are in states 4 / 6; nothing to do: returns)
+  hipLaunchKernelGGL(k_ipm_export, g.grid, kIpmBlk, 0, st, a);   // (lanes exported before a packing are in states 4 / 6; nothing to do: returns)
   IPM_DBG("export");
   return hipGetLastError();
 }
@@ -1766,21 +1734,15 @@ hipError_t ipm_run(StreamSolver *S, StreamArgs &sa, hipStream_t st, bool *all_so
   if (!I) return hipSuccess;
   hipError_t e = ipm_workspace(I, sa.b.B);
   if (e != hipSuccess) { (void)hipGetLastError(); return hipSuccess; }      // no memory for this form: the PDHG forms run
+  const IpmSettings s = ipm_settings(I->w.Bp);
   IpmArgs a{};
   a.P = I->P; a.w = I->w; a.sw = sa.W; a.opt = sa.opt; a.it = 0;
-  a.max_it = getenv("DSP_IPM_MAXIT") ? std::max(1, std::min(atoi(getenv("DSP_IPM_MAXIT")), kIpmMaxNewton)) : kIpmMaxNewton;
-  a.max_it = std::max(1, std::min(a.max_it, sa.opt.max_iter));            // (dsp_options::max_iter caps the Newton iterations too)
-  a.reg = getenv("DSP_IPM_REG") ? atof(getenv("DSP_IPM_REG")) : 0.0;
-  a.step = getenv("DSP_IPM_STEP") ? atof(getenv("DSP_IPM_STEP")) : 0.99;
-  a.step_blocked = getenv("DSP_IPM_STEP_BLOCKED") ? atof(getenv("DSP_IPM_STEP_BLOCKED")) : 0.9;
-  a.step_thr = getenv("DSP_IPM_STEP_THR") ? atof(getenv("DSP_IPM_STEP_THR")) : 0.5;      // (sweep: profiles/r69a_ipm_step_sweep.log)
-  a.sigmin = getenv("DSP_IPM_SIGMIN") ? atof(getenv("DSP_IPM_SIGMIN")) : 0.05;
-  a.thcap = getenv("DSP_IPM_THCAP") ? atof(getenv("DSP_IPM_THCAP")) : 1e11;
-  a.reftol = getenv("DSP_IPM_REFTOL") ? atof(getenv("DSP_IPM_REFTOL")) : 1e-6;
-  a.reftol_end = getenv("DSP_IPM_REFTOL_END") ? atof(getenv("DSP_IPM_REFTOL_END")) : 1e-6;
+  a.max_it = std::max(1, std::min(s.max_it, sa.opt.max_iter));            // (dsp_options::max_iter caps the Newton iterations too)
+  a.reg = s.reg; a.step = s.step; a.step_blocked = s.step_blocked; a.step_thr = s.step_thr; a.sigmin = s.sigmin; a.thcap = s.thcap;
+  a.reftol = s.reftol; a.reftol_end = s.reftol_end;
   a.reftol_strict = 1e-8; a.reftol_strict_end = 1e-11;
-  a.max_undo = getenv("DSP_IPM_MAX_UNDO") ? atoi(getenv("DSP_IPM_MAX_UNDO")) : 3;
-  return I->P.W == 6 ? ipm_loop<6>(S, a, st, all_solved, newton, n_solved) : ipm_loop<8>(S, a, st, all_solved, newton, n_solved);
+  a.max_undo = s.max_undo;
+  return I->P.W == 6 ? ipm_loop<6>(S, a, s, st, all_solved, newton, n_solved) : ipm_loop<8>(S, a, s, st, all_solved, newton, n_solved);
 }
 
 }  // namespace dsp

@@ -192,6 +192,7 @@ def test_full_year_double_loop_8192_plants_against_the_oracle():
          from the slack basis; 2793 plant-days, 4.1e-3 and 1.4e-4 with the simplex started from the previous hour's basis and the day-ahead solve from
          yesterday's shifted solution (other sequences of optimal points; `profiles/r69a_rolling_tests.log`).  The test reports the agreeing days and requires the annual totals within 6e-3 /
          5e-4: a check of the aggregate, the parity claim is check 1."""
+    import gc
     import multiprocessing as mp
     import os
     import time
@@ -227,6 +228,9 @@ def test_full_year_double_loop_8192_plants_against_the_oracle():
             part = {key: (v[d0:d1] if key.startswith("da_") else v[max(h0 - 1, 0):h1]) for key, v in mine.items()}
             tasks.append((k, j, d0, d1, part, h0))
     t1 = time.perf_counter()
+    # The loop objects of earlier tests are reference cycles (they bind their own step methods) that own solver handles: whatever of them
+    # the cycle collector has not freed yet must go HERE, not in a forked worker, whose copy of the GPU runtime cannot destroy a handle.
+    gc.collect()
     with mp.get_context("fork").Pool(min(len(tasks), max(1, (os.cpu_count() or 2) - 2))) as pool:
         outs = pool.map(_year_block, [(t, maps) for t in tasks], chunksize=1)
     check_wall = time.perf_counter() - t1
