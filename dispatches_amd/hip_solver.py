@@ -111,7 +111,8 @@ EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_
                     "dsp_get_scaling", "dsp_destroy", "dsp_strerror", "dsp_last_hip_error", "dsp_version",
                     "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
                     "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step", "dsp_loop_project",
-                    "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare", "dsp_loop_ledger", "dsp_loop_record", "dsp_loop_health")
+                    "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare", "dsp_loop_ledger", "dsp_loop_record", "dsp_loop_health",
+                    "dsp_loop_profile", "dsp_days_assign", "dsp_days_update", "dsp_days_frequency", "dsp_days_work_doubles")
 
 
 ABI_VERSION = 22       # DSP_VERSION of the include/dsp_hip.h these structures mirror
@@ -229,6 +230,22 @@ class DspLoopHealthState(C.Structure):
                 ("iters", C.c_void_p), ("iters_max", C.c_void_p), ("first", C.c_void_p), ("reserved2", C.c_int64 * 4)]
 
 
+DAYS_MAX_K, DAYS_MAX_DAYS, DAYS_MAX_PLANTS, DAYS_MAX_POINTS, DAYS_CHUNK = 64, 65536, 1 << 24, 2 ** 31 - 1, 1024      # DSP_DAYS_* of include/dsp_hip.h
+
+
+class DspLoopProfileDesc(C.Structure):
+    """include/dsp_hip.h: dsp_loop_profile_desc (added under ABI 22) - every plant's delivered power, kept hour by hour"""
+    _fields_ = [("B", C.c_int32), ("days", C.c_int32), ("clock", C.c_void_p), ("delivered", C.c_void_p), ("profile", C.c_void_p),
+                ("reserved", C.c_int64 * 4)]
+
+
+class DspDaysDesc(C.Structure):
+    """include/dsp_hip.h: dsp_days_desc (added under ABI 22) - the day points over a profile: scaling range, channels, filter"""
+    _fields_ = [("B", C.c_int32), ("days", C.c_int32), ("channels", C.c_int32), ("filter", C.c_int32), ("profile", C.c_void_p),
+                ("p_min", C.c_void_p), ("p_max", C.c_void_p), ("cf_series", C.c_void_p), ("start", C.c_void_p), ("N", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
 def source_hash(root: Optional[str] = None) -> Optional[str]:
     """What dsp_source_hash() of a library built from the sources in this tree returns: the first 16 hex digits of the SHA-256 over
     csrc/*.hip, csrc/*.hpp and include/dsp_hip.h (name order, each preceded by its base name).  None when the sources are not
@@ -330,6 +347,16 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_record.restype = C.c_int
     lib.dsp_loop_health.argtypes = [C.POINTER(DspLoopHealthState), vp, vp, vp, i32, i32, vp]
     lib.dsp_loop_health.restype = C.c_int
+    lib.dsp_loop_profile.argtypes = [C.POINTER(DspLoopProfileDesc), vp]
+    lib.dsp_loop_profile.restype = C.c_int
+    lib.dsp_days_assign.argtypes = [C.POINTER(DspDaysDesc), vp, i32, vp, vp, vp]
+    lib.dsp_days_assign.restype = C.c_int
+    lib.dsp_days_update.argtypes = [C.POINTER(DspDaysDesc), vp, vp, i32, vp, vp, vp, vp, C.c_int64, vp]
+    lib.dsp_days_update.restype = C.c_int
+    lib.dsp_days_work_doubles.argtypes = [C.c_int64, i32, i32]
+    lib.dsp_days_work_doubles.restype = C.c_int64
+    lib.dsp_days_frequency.argtypes = [C.POINTER(DspDaysDesc), vp, i32, vp, vp]
+    lib.dsp_days_frequency.restype = C.c_int
     lib.dsp_last_hip_error.restype = C.c_int
     if path == _LIB_PATH:
         _lib = lib

@@ -89,7 +89,12 @@ curves, dispatches, delivered power - kept hour by hour for up to 64 plants in d
 Solve health (health=True): `bad` and `uncertified` say that SOME row of SOME plant failed or went uncertified; the health counters say
 which plant, in which kind of solve (day-ahead, real-time, tracking, projection), from which hour on, and what the solves cost in
 iterations - one launch per solve (dsp_loop_health, csrc/dsp_health.hip) inside the captured steps, over exactly the rows that feed the
-two global flags.  `_health_book` is the specification as tensor operations; integers, so the two agree exactly."""
+two global flags.  `_health_book` is the specification as tensor operations; integers, so the two agree exactly.
+
+Day profiles (profiles=days): the delivered power of EVERY plant, hour by hour, in `profile` [days + 1, 24, B] - what the reference's
+market-surrogate workflow cuts into days, clusters into representative days and turns into each simulation's dispatch frequency
+(representative_days.py).  One launch per hour step after the hand-off (dsp_loop_profile, csrc/dsp_days.hip) inside the captured step;
+`_profile_write_tensors` is the specification as tensor operations, a copy, so the two agree bit for bit."""
 from __future__ import annotations
 
 import numpy as np
@@ -482,7 +487,8 @@ class BatchedDoubleLoop(_DeviceLoop):
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
                  market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
                  battery_mwh=None, ruc_hour=None, scenario_coupling="independent", ledger=False, pem_mw=None, tank_kg=None,
-                 h2_price=None, h2_demand=None, record=None, record_max_bytes=2 ** 30, simplex_certify=False, health=False):
+                 h2_price=None, h2_demand=None, record=None, record_max_bytes=2 ** 30, simplex_certify=False, health=False,
+                 profiles=None, profile_max_bytes=2 ** 30):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -587,11 +593,22 @@ class BatchedDoubleLoop(_DeviceLoop):
         is made; the 24 - H solves of its projection chain as projection; bidder="parametrized" books tracking only.  Works in every
         mode, with ledger and record, eagerly or from graphs: one launch of dsp_loop_health per solve inside the step (csrc/dsp_health.hip;
         use_fused=False and the CPU stand-in: the same integers as tensor operations, _health_book).  results() gains failed_solves,
-        uncertified_solves, first_failure_hour (-1: none) and valid [B]."""
+        uncertified_solves, first_failure_hour (-1: none) and valid [B].
+        profiles: None (the loops above: same launches, same bits, no `profile` attribute) or an integer days >= 1: the loop keeps the
+        delivered power of EVERY plant, hour by hour, in `profile` [days + 1, 24, B] float64 MW - plant-minor, so that one wave's stores
+        and the later loads of representative_days.py are consecutive; the last row is the spare row for hours past the span (the
+        recorder's rule).  Written after the hand-off of every hour step, at h = clock - 1: profile[min(h // 24, days), h % 24, :] =
+        delivered - one launch of dsp_loop_profile (csrc/dsp_days.hip) inside the captured step, so the graphs stay as many;
+        use_fused=False and the CPU stand-in: index_copy_ at the same row rule, the same bits.  Works in every mode and with sizes,
+        nuclear operands, ledger, health and record, since every mode ends an hour by writing `delivered`.  reset() zeroes the buffer;
+        profiles_host() returns [B, whole days run (at most days), 24]; profile_bytes is its size.  Refused (ValueError): days that is
+        not an integer >= 1, a buffer above profile_max_bytes (default 2 ** 30: a guard like record_max_bytes, not a measured figure).
+        What the profiles are for: representative_days.DayPoints."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
         self._rec, self.record_bytes = None, 0
+        self._profile_days = None if profiles is None else self._check_profiles(profiles, B, int(profile_max_bytes))
         if record is not None:
             from .loop_record import check_record
             record = check_record(record, B)
@@ -705,6 +722,8 @@ class BatchedDoubleLoop(_DeviceLoop):
         self.health = bool(health)
         if self.health:
             self._health_setup()
+        if self._profile_days is not None:
+            self._profile_setup()
         # the mode's day-ahead step, hour step and LP solves per call of day_ahead() / hour_step(), bound once
         if self.parametrized:
             self._da_step, self._hour, self._n_da, self._n_hour = self._day_ahead_step_parametrized, self._hour_step_parametrized, 0, B
@@ -1103,6 +1122,57 @@ class BatchedDoubleLoop(_DeviceLoop):
             bid.rt_history_lag_days = 1
             self._mk_bid = bid
 
+    @staticmethod
+    def _check_profiles(days, B, max_bytes):
+        if isinstance(days, bool) or not isinstance(days, (int, np.integer)) or days < 1:
+            raise ValueError(f"profiles is None or an integer number of days >= 1, not {days!r}")
+        total = (int(days) + 1) * 24 * B * 8
+        if total > max_bytes:
+            raise ValueError(f"profiles: the buffer of {B} plants over {int(days)} days takes {total} bytes, more than profile_max_bytes = {max_bytes}")
+        return int(days)
+
+    def _profile_setup(self):
+        """the profile buffer (persistent, zeroed by reset()), the operand of the tensor form and - with the kernels - the descriptor"""
+        import torch
+        B, days, dev = self.B, self._profile_days, self.dev
+        self.profile = torch.zeros((days + 1, 24, B), dtype=torch.float64, device=dev)
+        self.profile_bytes = self.profile.numel() * 8
+        self._zeroed.append(self.profile)
+        self._profile_days_t = torch.full((), days, dtype=torch.int64, device=dev)
+        if self.use_fused:
+            from .hip_solver import DspLoopProfileDesc
+            d = DspLoopProfileDesc()
+            d.B, d.days, d.clock = B, days, self.hour_t.data_ptr()
+            d.delivered, d.profile = self.delivered.data_ptr(), self.profile.data_ptr()
+            self._profile_desc = d
+
+    def _profile_write(self):
+        """the hour that just ended (clock - 1), AFTER the hand-off: every plant's delivered power into the row the device clock names;
+        hours past the span go to the spare row.  With the kernels one launch of dsp_loop_profile; otherwise its statement as tensor
+        operations - a copy, so the two are equal bit for bit."""
+        if self._profile_days is None:
+            return
+        if self.use_fused:
+            import ctypes as C
+            self._call(self._lib.dsp_loop_profile, C.byref(self._profile_desc))
+            return
+        self._profile_write_tensors(self.profile)
+
+    def _profile_write_tensors(self, profile):
+        """the specification of dsp_loop_profile on a buffer [days + 1, 24, B]"""
+        import torch
+        h, days = self.hour_t - 1, self._profile_days_t
+        day = torch.minimum(torch.div(h, 24, rounding_mode="floor"), days)
+        row = torch.where(h < 0, days * 24, day * 24 + h % 24).view(1)
+        profile.view(-1, self.B).index_copy_(0, row, self.delivered.unsqueeze(0))
+
+    def profiles_host(self):
+        """-> numpy [B, D, 24], D = whole days run so far (at most the span): plant b's delivered MW of day d, hour h"""
+        if self._profile_days is None:
+            raise RuntimeError("this loop keeps no profiles: construct it with profiles=days")
+        D = min(self.hour // 24, self._profile_days)
+        return np.ascontiguousarray(self.profile[:D].cpu().numpy().transpose(2, 0, 1))
+
     def _record_setup(self, record, max_bytes):
         """the recorder (loop_record.LoopRecorder: buffers, segments, descriptors) and the day-ahead step that ends with its daily write"""
         from .loop_record import LoopRecorder
@@ -1128,6 +1198,8 @@ class BatchedDoubleLoop(_DeviceLoop):
         self._call(self._lib.dsp_loop_update, C.byref(self._loop_state), C.byref(self._loop_rt), C.byref(self._loop_tr), phase, k)
         if phase == 2 and self._rec is not None:       # after the hand-off: delivered power of the hour that just ended (clock - 1)
             self._rec.write("after")
+        if phase == 2:
+            self._profile_write()
 
     def _param(self, phase, k):
         import ctypes as C
@@ -1247,6 +1319,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         self.hour_t += 1
         if self._rec is not None:
             self._rec.write("after")
+        self._profile_write()
 
     def _ledger_book(self, x):
         """the ledger of the implemented hour on the tracker's solution x [B, n], BEFORE the hand-off (the clock is still the hour's), in

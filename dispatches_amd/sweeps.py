@@ -33,16 +33,51 @@ def _health_outputs(res, shape):
     return {key: res[key].cpu().numpy().reshape(shape).copy() for key in ("valid", "failed_solves", "first_failure_hour")}
 
 
+def _want_profiles(representative_days, n_days, loop_kw):
+    """representative_days checked before anything runs; the loop then keeps the sweep's day profiles"""
+    if representative_days is None:
+        return
+    if isinstance(representative_days, (int, np.integer)) and not isinstance(representative_days, bool):
+        if not 1 <= representative_days <= 64:
+            raise ValueError(f"representative_days: K is in 1 .. 64, not {representative_days}")
+    else:
+        centers = np.asarray(representative_days, np.float64)
+        if centers.ndim != 2 or centers.shape[1] not in (24, 48) or not 1 <= centers.shape[0] <= 64:
+            raise ValueError(f"representative_days is a number of clusters K or centres [K, 24] / [K, 48] with K in 1 .. 64, not an array of shape {list(centers.shape)}")
+    loop_kw.setdefault("profiles", int(n_days))
+
+
+def _representative_days(loop, representative_days, shape):
+    """the second label of the reference's market surrogates for a loop run with profiles= (representative_days.py): an int K fits K
+    representative days on the sweep's own days (seed 42, k-means++), a centre array [K, 24] or [K, 48] only labels.  One channel
+    (dispatch) for the nuclear flowsheet, two (dispatch and the day's capacity factors) for the wind flowsheets, as in the reference,
+    unless a centre array says otherwise.  -> dispatch_frequency, grid shape + (K + 2,) = [zero days, days at centre 0 .. K - 1, full
+    days] / days, and day_centers [K, 24 * channels]"""
+    from .representative_days import DayPoints
+    if isinstance(representative_days, (int, np.integer)) and not isinstance(representative_days, bool):
+        points = DayPoints(loop, channels=1 if loop.flowsheet == "nuclear" else 2)
+        centers = points.fit(int(representative_days)).centers
+    else:
+        centers = np.asarray(representative_days, np.float64)
+        points = DayPoints(loop, channels=centers.shape[1] // 24)
+    freq = points.frequency(centers).cpu().numpy()
+    return {"dispatch_frequency": freq.reshape(tuple(shape) + (freq.shape[1],)).copy(), "day_centers": np.array(centers)}
+
+
 def parametrized_sweep(flowsheet, bid_prices, storage_mws, n_windows, n_days, device=0, market="price_taker", lp_backend=None, ledger=False,
-                       health=False, **loop_kw):
+                       health=False, representative_days=None, **loop_kw):
     """Runs `n_days` simulated days of the (bid price x storage size x window) grid of `flowsheet` ("wind_pem" or "wind_battery").
     -> dict of numpy arrays shaped [len(bid_prices), len(storage_mws), n_windows]: revenue, energy_mwh (delivered), da_energy_mwh
     (cleared day-ahead), offered_mwh (the day-ahead curves' last points), h2_kg (wind + PEM only); and all_optimal (bool).
     ledger=True: also the loop's ledger (BatchedDoubleLoop(ledger=True): tot_cost, under_mwh, over_mwh, curtailed_mwh, pem_mwh for
     wind + PEM) and profit = revenue - tot_cost, same shape.
     health=True: also valid (bool), failed_solves and first_failure_hour (-1: none) of every grid point (BatchedDoubleLoop(health=True)),
-    same shape: all_optimal == False no longer condemns the whole sweep."""
+    same shape: all_optimal == False no longer condemns the whole sweep.
+    representative_days=K or centres: the loop keeps every plant's day profiles (BatchedDoubleLoop(profiles=n_days)) and the sweep also
+    returns dispatch_frequency, shape + (K + 2,), and day_centers (_representative_days): with revenue, the two labels the reference's
+    market surrogates are trained on."""
     from .rolling_flowsheets import BatchedDoubleLoop
+    _want_profiles(representative_days, n_days, loop_kw)
     bid, sto, win = grid_layout(bid_prices, storage_mws, n_windows)
     shape = (len(np.ravel(bid_prices)), len(np.ravel(storage_mws)), int(n_windows))
     loop = BatchedDoubleLoop(flowsheet, len(bid), device=device, lp_backend=lp_backend, bidder="parametrized", bid_price=bid, storage_mw=sto,
@@ -57,6 +92,8 @@ def parametrized_sweep(flowsheet, bid_prices, storage_mws, n_windows, n_days, de
         out.update(_ledger_outputs(loop, res, shape))
     if health:
         out.update(_health_outputs(res, shape))
+    if representative_days is not None:
+        out.update(_representative_days(loop, representative_days, shape))
     out["all_optimal"] = bool(ok)
     return out
 
@@ -72,7 +109,7 @@ def design_layout(wind_mws, battery_mws, durations_h, n_windows):
 
 
 def design_sweep(flowsheet, wind_mws, battery_mws, durations_h, n_windows, n_days, n_price_scenarios=1, forecaster="perfect",
-                 market="price_taker", device=0, lp_backend=None, ledger=False, health=False, **loop_kw):
+                 market="price_taker", device=0, lp_backend=None, ledger=False, health=False, representative_days=None, **loop_kw):
     """Runs `n_days` simulated days of the (wind MW x battery MW x duration h x window) grid of `flowsheet` with the LP bidder, every grid
     point a plant of its own size.  "wind_battery": all axes; "wind_pem": the wind axis only - battery_mws and durations_h must have
     length 1 and are not used (pass [0.0], [0.0]).  -> dict of numpy arrays shaped [len(wind_mws), len(battery_mws), len(durations_h),
@@ -81,8 +118,10 @@ def design_sweep(flowsheet, wind_mws, battery_mws, durations_h, n_windows, n_day
     ledger=True: also the loop's ledger (tot_cost - degradation, fixed O&M and curtailment penalty of the implemented hours, the
     reference's "Total Cost [$]" -, under_mwh, over_mwh, curtailed_mwh; wind_pem: h2_kg, pem_mwh) and profit = revenue - tot_cost, same
     shape: what ranks designs, where revenue alone always prefers the larger battery.
-    health=True: also valid, failed_solves and first_failure_hour of every grid point, same shape (parametrized_sweep)."""
+    health=True: also valid, failed_solves and first_failure_hour of every grid point, same shape (parametrized_sweep).
+    representative_days=K or centres: also dispatch_frequency, shape + (K + 2,), and day_centers (parametrized_sweep)."""
     from .rolling_flowsheets import BatchedDoubleLoop
+    _want_profiles(representative_days, n_days, loop_kw)
     wind, batt, mwh, win = design_layout(wind_mws, battery_mws, durations_h, n_windows)
     shape = tuple(len(np.ravel(a)) for a in (wind_mws, battery_mws, durations_h)) + (int(n_windows),)
     if flowsheet == "wind_pem":
@@ -105,6 +144,8 @@ def design_sweep(flowsheet, wind_mws, battery_mws, durations_h, n_windows, n_day
         out.update(_ledger_outputs(loop, res, shape))
     if health:
         out.update(_health_outputs(res, shape))
+    if representative_days is not None:
+        out.update(_representative_days(loop, representative_days, shape))
     out["all_optimal"] = bool(ok)
     return out
 
@@ -120,15 +161,17 @@ def nuclear_layout(h2_prices, pem_mws, n_windows):
 
 
 def nuclear_sweep(h2_prices, pem_mws, n_windows, n_days, tank_kg=None, h2_demand=None, n_price_scenarios=3, forecaster="backcast",
-                  market="price_taker", device=0, lp_backend=None, health=False, **loop_kw):
+                  market="price_taker", device=0, lp_backend=None, health=False, representative_days=None, **loop_kw):
     """Runs `n_days` simulated days of the (hydrogen price $/kg x PEM size MW x window) grid of the nuclear double loop as ONE batch, every
     grid point a plant with its own h2_price and pem_mw (the reference's study reports elec_rev, h2_rev, net_profit and pem_cap_factor
     over such a grid, nuclear_case/report/price_taker_analysis.py); tank_kg / h2_demand: scalars for all plants (None: the flowsheet's).
     The loop keeps its ledger.  -> dict of numpy arrays shaped [len(h2_prices), len(pem_mws), n_windows]: revenue (electricity), h2_revenue,
     tot_cost (operating cost minus hydrogen revenue), profit = revenue - tot_cost, energy_mwh, h2_kg, pem_capacity_factor = PEM MWh /
     (pem_mw * hours); and all_optimal.  health=True: also valid, failed_solves and first_failure_hour of every grid point, same shape
+    (parametrized_sweep).  representative_days=K or centres: also dispatch_frequency, shape + (K + 2,), and day_centers
     (parametrized_sweep)."""
     from .rolling_flowsheets import BatchedDoubleLoop
+    _want_profiles(representative_days, n_days, loop_kw)
     price, pem, win = nuclear_layout(h2_prices, pem_mws, n_windows)
     shape = (len(np.ravel(h2_prices)), len(np.ravel(pem_mws)), int(n_windows))
     loop = BatchedDoubleLoop("nuclear", len(price), device=device, lp_backend=lp_backend, n_price_scenarios=n_price_scenarios, forecaster=forecaster,
@@ -143,5 +186,7 @@ def nuclear_sweep(h2_prices, pem_mws, n_windows, n_days, tank_kg=None, h2_demand
     out["pem_capacity_factor"] = res["pem_mwh"].cpu().numpy().reshape(shape) / (pem.reshape(shape) * float(loop.hour))
     if health:
         out.update(_health_outputs(res, shape))
+    if representative_days is not None:
+        out.update(_representative_days(loop, representative_days, shape))
     out["all_optimal"] = bool(ok)
     return out

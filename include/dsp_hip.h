@@ -39,6 +39,8 @@
  * Added under ABI 22, DSP_VERSION unchanged: dsp_loop_health and dsp_loop_health_state, the per-plant solve health of the descriptor loop
  * (rows solved / failed / waived, status mask, iteration sum and maximum, first failing hour - per plant and kind of solve).  A new symbol
  * and a new struct only: no existing struct, entry point or kernel changed, so a caller of ABI 22 that does not know them is unaffected.
+ * Added the same way, DSP_VERSION still 22: dsp_loop_profile (every plant's delivered power kept hour by hour) and the representative
+ * days over it - dsp_days_assign, dsp_days_update, dsp_days_frequency, dsp_days_work_doubles with dsp_loop_profile_desc / dsp_days_desc.
  */
 #ifndef DSP_HIP_H
 #define DSP_HIP_H
@@ -551,6 +553,73 @@ typedef struct dsp_loop_health_state {
  * Capturable: one kernel launch on hipStream, no allocation, no synchronisation, no memset. */
 int dsp_loop_health(const dsp_loop_health_state *h, const int32_t *status, const int32_t *flags, const int32_t *iters,
                     int32_t rows_per_plant, int32_t kind, void *hipStream);
+
+/* The day profiles of the descriptor loop (added under ABI 22; rolling_flowsheets.py::BatchedDoubleLoop(profiles=days)): the delivered
+ * power of EVERY plant, hour by hour, plant-minor - what the reference's market-surrogate workflow cuts into days and clusters
+ * (dispatches/workflow/train_market_surrogates/dynamic/).  Launched once after the hand-off of every hour step:
+ *     h = *clock - 1 ;  day = min(h / 24, days) ;  profile[(day * 24 + h % 24) * B + b] = delivered[b]
+ * Row `days` is the spare row for hours past the span (and for a clock < 1: hour 0 of the spare row) - the recorder's rule.  One lane per
+ * plant, 256 lanes per block, one load and one store per lane: no arithmetic, no atomics, no LDS. */
+typedef struct dsp_loop_profile_desc {
+  int32_t B, days;                     /* plants, >= 0; days of the span, >= 1                                                      */
+  const int64_t *clock;                /* [1] device: the loop's clock (dsp_loop_state::hour), already advanced by the hand-off     */
+  const double *delivered;             /* [B] device: dsp_loop_state::delivered                                                     */
+  double *profile;                     /* [days + 1][24][B] device, MW                                                              */
+  int64_t reserved[4];                 /* 0                                                                                         */
+} dsp_loop_profile_desc;
+
+/* DSP_ERR_INVALID, nothing launched and nothing written, for: a NULL descriptor, clock, delivered or profile; B < 0; days < 1 or
+ * days > DSP_DAYS_MAX_DAYS; B above DSP_DAYS_MAX_PLANTS; reserved != 0.  B == 0: DSP_OK, nothing launched.
+ * Capturable: one kernel launch on hipStream, no allocation, no synchronisation, no memset. */
+int dsp_loop_profile(const dsp_loop_profile_desc *p, void *hipStream);
+
+/* Representative days (added under ABI 22; dispatches_amd/representative_days.py): the profile cut into day POINTS, one per (day, plant),
+ * point p = day * B + b, with F = 24 * channels features.  Every operation is rounded on its own, nothing is contracted into an fma:
+ *     channel 1   cf[h] = (profile[day][h][b] - p_min[b]) / (p_max[b] - p_min[b])                          h = 0 .. 23
+ *     channel 2   w[h]  = cf_series[(start[b] + 24 * day + h) mod N]   (the realised window; computed on the fly)
+ *     class       only with filter: s = ((cf[0] + cf[1]) + ...) + cf[23];  s == 0.0: a zero day, label -1;  s == 24.0: a full day, label -2
+ *     distance    for k = 0 .. K - 1: acc = 0; for j = 0 .. F - 1: d = x[j] - c[k][j]; acc = acc + d * d.   label = the first k with the
+ *                 smallest acc (strict <); dist2 = that acc.  A zero or full day gets dist2 = 0.
+ * p_max[b] > p_min[b] is the caller's contract (a device array cannot be checked on the host). */
+#define DSP_DAYS_MAX_K 64              /* centres: K * F doubles are staged in LDS, at most 24 KiB                                   */
+#define DSP_DAYS_MAX_DAYS 65536
+#define DSP_DAYS_MAX_PLANTS (1 << 24)
+#define DSP_DAYS_MAX_POINTS 2147483647 /* B * days                                                                                  */
+#define DSP_DAYS_CHUNK 1024            /* points per partial sum of dsp_days_update                                                 */
+typedef struct dsp_days_desc {
+  int32_t B, days;                     /* plants, >= 0; days, >= 1: the first `days` rows of the profile                            */
+  int32_t channels, filter;            /* 1 or 2; 0 or 1                                                                            */
+  const double *profile;               /* [>= days][24][B] device, MW                                                               */
+  const double *p_min, *p_max;         /* [B] device, MW                                                                            */
+  const double *cf_series;             /* [N] device (channels == 2; else ignored)                                                  */
+  const int64_t *start;                /* [B] device (channels == 2; else ignored)                                                  */
+  int64_t N;                           /* >= 1 (channels == 2; else ignored)                                                        */
+  int64_t reserved[4];                 /* 0                                                                                         */
+} dsp_days_desc;
+
+/* Every entry point below returns DSP_ERR_INVALID, nothing launched and nothing written, for: a NULL descriptor, profile, p_min or p_max;
+ * B < 0 or above DSP_DAYS_MAX_PLANTS; days < 1 or above DSP_DAYS_MAX_DAYS; B * days above DSP_DAYS_MAX_POINTS; channels outside 1 .. 2;
+ * filter outside 0 .. 1; channels == 2 with a NULL cf_series or start or N < 1; reserved != 0; K outside 1 .. DSP_DAYS_MAX_K; a NULL
+ * array argument.  B == 0: DSP_OK, nothing launched.  All arrays are DEVICE arrays.  No allocation, no synchronisation.
+ *
+ * dsp_days_assign: one lane per point, plants fastest (the loads of one hour are consecutive); the centres [K][F] are staged once per
+ * workgroup in LDS and read as a broadcast; the point stays in registers.  Writes label [days][B] and dist2 [days][B]. */
+int dsp_days_assign(const dsp_days_desc *d, const double *centers, int32_t K, int32_t *label, double *dist2, void *hipStream);
+
+/* dsp_days_update: the centres as the means of their members (labels >= 0; the others are skipped), the member counts and the inertia
+ * = sum(dist2 of labelled points) / n_labelled (0 without a labelled point).  No floating-point atomics: the points of chunk q,
+ * [q * DSP_DAYS_CHUNK, (q + 1) * DSP_DAYS_CHUNK), are added in the order of p into work[q][K * F + K + 2] (sums, counts, dist2, labelled points), then the
+ * chunks in the order of q, and centre = sum / count - the same bits on every run.  A cluster without a member keeps its centre.
+ * centers [K][F] in / out; count [K]; inertia [1]; work: at least dsp_days_work_doubles(B * days, K, channels) doubles.
+ * Labels outside -2 .. K - 1 are the caller's fault and are skipped.  Two launches. */
+int dsp_days_update(const dsp_days_desc *d, const int32_t *label, const double *dist2, int32_t K, double *centers, int64_t *count,
+                    double *inertia, double *work, int64_t work_doubles, void *hipStream);
+int64_t dsp_days_work_doubles(int64_t points, int32_t K, int32_t channels);      /* -1 for arguments outside their ranges            */
+
+/* dsp_days_frequency: one lane per plant walks its `days` labels (Train_NN_Surrogates._generate_label_data).  filter == 1:
+ * freq [B][K + 2] = [zero days, members of centre 0 .. K - 1, full days] / days;  filter == 0: freq [B][K] = members / days.  Counts are
+ * integers, each entry one division.  No atomics. */
+int dsp_days_frequency(const dsp_days_desc *d, const int32_t *label, int32_t K, double *freq, void *hipStream);
 
 /* The scenario half of the Bidder's bid assembly ON THE DEVICE (reference: idaes Bidder._assemble_bids as DISPATCHES drives it -
  * dispatches/workflow/coordinator.py hands its bids to Prescient; golden values
