@@ -218,6 +218,22 @@ int dsp_loop_monotone_prepare(const dsp_loop_market_state *st, const dsp_loop_ma
   return DSP_OK;
 }
 
+// the coupled real-time LP of a look-ahead hour past midnight (added under ABI 22): the blocks of dsp_loop_schedule_prepare at hour k of
+// the day, and - rlo / rhi given - the bounds of the P T ordered-pair rows as dsp_loop_monotone_prepare's, from the real-time prices
+int dsp_loop_midnight_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, double *rlo, double *rhi, int32_t m_rows,
+                              int32_t first_coupling_row, int32_t k, void *hipStream) {
+  if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < 0 || k > 23 || 24 - k >= m->T) return DSP_ERR_INVALID;
+  if (!st->da_offer || !st->da_prices || !rlo != !rhi) return DSP_ERR_INVALID;
+  if ((long long)m->row_stride < (long long)st->S * m->n) return DSP_ERR_INVALID;
+  if (rlo && (st->S < 2 || first_coupling_row < 0 ||
+              (long long)first_coupling_row + (long long)(st->S * (st->S - 1) / 2) * m->T > (long long)m_rows))
+    return DSP_ERR_INVALID;
+  if (!loop_market_prepare_ok(st, m) || m->wind_kw_plant || m->c0_base_plant) return DSP_ERR_INVALID;
+  if (st->B == 0) return DSP_OK;
+  HIP_TRY(launch_loop_midnight_prepare(*st, *m, rlo, rhi, (int)m_rows, (int)first_coupling_row, (int)k, (hipStream_t)hipStream));
+  return DSP_OK;
+}
+
 int dsp_loop_market_clear(const dsp_loop_market_state *st, const dsp_loop_market_model *m, const dsp_loop_model *tr, int32_t k, int32_t T,
                           double *dispatch, int32_t *curve, int32_t *count, void *hipStream) {
   if (!loop_market_state_ok(st) || !loop_market_model_ok(m) || k < -1 || k > 23 || T < 1 || T > m->T) return DSP_ERR_INVALID;

@@ -228,6 +228,8 @@ hipError_t launch_loop_market_prepare(const dsp_loop_market_state &st, const dsp
 hipError_t launch_loop_schedule_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, hipStream_t stream);
 hipError_t launch_loop_monotone_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, double *rlo, double *rhi, int m_rows,
                                         int first, hipStream_t stream);
+hipError_t launch_loop_midnight_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, double *rlo, double *rhi, int m_rows,
+                                        int first, int k, hipStream_t stream);
 hipError_t launch_loop_market_clear(const dsp_loop_market_state &st, const dsp_loop_market_model &m, const dsp_loop_model *tr, int k, int T,
                                     double *dispatch, int32_t *curve, int32_t *count, hipStream_t stream);
 // parametrized two-tier bidding of the descriptor loop (dsp_param.hip): phase 0 day-ahead, 1 real time + tracker, 2 hydrogen

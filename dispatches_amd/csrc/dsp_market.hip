@@ -21,6 +21,8 @@
 //                           (dsp_loop_monotone_prepare, idaes' Bidder): the same blocks through the same lmk_coupled_block, and the
 //                           bounds of the S (S - 1) / 2 * T ordered-pair rows from the order of the day-ahead scenario prices, one lane
 //                           per (plant, pair, period).  The clearing reads such a row with dsp_loop_market_state::coupled = 1.
+//   loop_midnight_prepare_kernel   the coupled REAL-TIME LP of the last T - 1 hours of a day (dsp_loop_midnight_prepare): the blocks of hour
+//                           k through the same lmk_coupled_block, the pair rows' bounds from the order of the real-time scenario prices.
 //   loop_market_prepare_kernel / loop_market_clear_kernel   the same two for ANY flowsheet, by descriptor (dsp_loop_market_*; rolling_flowsheets.py):
 //                           power P_T = (x[a] ca + x[b] cb) + const, curves that start at the generator's p_min, <= 2 state columns,
 //                           optional wind; the clearing lanes also write the tracker's LP (a dsp_loop_model).  VGPRs / scratch of every
@@ -258,21 +260,22 @@ __global__ void __launch_bounds__(256) loop_market_prepare_kernel(dsp_loop_marke
 }
 
 // Lane r = b * S + i of a coupled day-ahead LP: S scenario blocks of m.n columns side by side in row b (m.row_stride doubles apart).
-// Block i is the block that loop_market_prepare_kernel writes into row b * S + i with k = -1; the lane of scenario 0 also sums the S
-// objective constants in the order of i - alone, so that the order is the tensor form's (BatchedDoubleLoop._coupled_blocks).  One
-// block writer and one constant summer for the self-schedule's rows and the monotone Bidder's.
-__device__ __forceinline__ void lmk_coupled_block(const dsp_loop_market_state &s, const dsp_loop_market_model &m, int r) {
+// Block i is the block that loop_market_prepare_kernel writes into row b * S + i at hour k of the day (-1: the day-ahead bid); the lane
+// of scenario 0 also sums the S objective constants in the order of i - alone, so that the order is the tensor form's
+// (BatchedDoubleLoop._coupled_blocks / _tied_blocks).  One block writer and one constant summer for the self-schedule's rows and the
+// monotone Bidder's, day-ahead and - the look-ahead hours past midnight - real-time.
+__device__ __forceinline__ void lmk_coupled_block(const dsp_loop_market_state &s, const dsp_loop_market_model &m, int r, int k) {
   const int b = r / s.S, i = r - b * s.S;
   const bool wind = m.wind_cols[0] >= 0;
   const size_t at0 = (size_t)b * m.row_stride + (size_t)i * m.n;
-  const lmk_sums sums = lmk_write_block(s, m, m.c + at0, m.lb + at0, m.ub + at0, b, i, -1, m.wind_kw);
+  const lmk_sums sums = lmk_write_block(s, m, m.c + at0, m.lb + at0, m.ub + at0, b, i, k, m.wind_kw);
   if (i != 0) return;
   // ---- the row's objective constant: the S scenario constants added in the order of i ----
   const long long h = *s.hour, st0 = s.start[b];
   const double waste = wind ? loop_opaque(__dmul_rn(m.waste_per_kw, sums.avail)) : 0.0;
   double total = 0.0;
   for (int j = 0; j < s.S; ++j) {
-    const double c0 = lmk_c0(m.c0_base, lmk_price_sum(s, m, st0, h, j, 0), wind, waste);
+    const double c0 = lmk_c0(m.c0_base, lmk_price_sum(s, m, st0, h, j, k < 0 ? 0 : k), wind, waste);
     total = j ? __dadd_rn(total, c0) : c0;
   }
   m.c0[b] = total;
@@ -283,7 +286,7 @@ __device__ __forceinline__ void lmk_coupled_block(const dsp_loop_market_state &s
 __global__ void __launch_bounds__(256) loop_schedule_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= s.B * s.S) return;
-  lmk_coupled_block(s, m, r);
+  lmk_coupled_block(s, m, r, -1);
 }
 
 // The coupled day-ahead LP of a plant that bids a MONOTONE curve (dsp_loop_monotone_prepare, ABI 19; idaes' Bidder): the same S blocks,
@@ -298,7 +301,7 @@ __global__ void __launch_bounds__(256) loop_monotone_prepare_kernel(dsp_loop_mar
   const int S = s.S, T = m.T;
   const long long blocks = (long long)s.B * S;
   if (g < blocks) {
-    lmk_coupled_block(s, m, (int)g);
+    lmk_coupled_block(s, m, (int)g, -1);
     return;
   }
   const int per_plant = S * (S - 1) / 2 * T;
@@ -311,6 +314,38 @@ __global__ void __launch_bounds__(256) loop_monotone_prepare_kernel(dsp_loop_mar
   const int k = j + 1 + rest;
   const long long h = *s.hour, st0 = s.start[b];
   const double d = __dsub_rn(s.da_series[loop_scenario_index(s, st0, h, k, 0, t)], s.da_series[loop_scenario_index(s, st0, h, j, 0, t)]);
+  const size_t at = (size_t)b * m_rows + first + pt;
+  rlo[at] = d > 0.0 ? 0.0 : -INFINITY;
+  rhi[at] = d < 0.0 ? 0.0 : INFINITY;
+}
+
+// The coupled REAL-TIME LP of hour k of the day, in the last T - 1 hours of a day (dsp_loop_midnight_prepare; BatchedDoubleLoop with
+// past_midnight="coupled"): the S blocks of row b are the rows b * S + i that loop_market_prepare_kernel writes at hour k - day_ahead_power
+// fixed to the cleared offer inside the day, free past midnight - and c0[b] their constants summed in the order of i.  The monotone
+// Bidder's pair rows cover ALL T periods and follow the order of the hour's REAL-TIME scenario prices (the backcast asked at hour-of-day
+// k, through lmk_rt): one lane per (b, pair, t), t fastest, exactly loop_monotone_prepare_kernel's second lane range.  rlo == NULL: a
+// self-schedule, whose coupling rows are static.  No atomics, no cross-lane traffic; every lane writes addresses of its own.
+__global__ void __launch_bounds__(256) loop_midnight_prepare_kernel(dsp_loop_market_state s, dsp_loop_market_model m, double *rlo, double *rhi,
+                                                                    int m_rows, int first, int k) {
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int S = s.S, T = m.T;
+  const long long blocks = (long long)s.B * S;
+  if (g < blocks) {
+    lmk_coupled_block(s, m, (int)g, k);
+    return;
+  }
+  if (!rlo) return;
+  const int per_plant = S * (S - 1) / 2 * T;
+  const long long q = g - blocks;
+  if (q >= (long long)s.B * per_plant) return;
+  const int b = (int)(q / per_plant), pt = (int)(q - (long long)b * per_plant);
+  const int p = pt / T, t = pt - p * T;
+  int j = 0, rest = p;                           // p -> (j, kk): pairs (0, 1) .. (0, S - 1), (1, 2) ..: at most 15 values of j
+  while (rest >= S - 1 - j) { rest -= S - 1 - j; ++j; }
+  const int kk = j + 1 + rest;
+  const long long h = *s.hour, st0 = s.start[b];
+  const double d = __dsub_rn(s.rt_series[lmk_rt(s, loop_scenario_index(s, st0, h, kk, k, t))],
+                             s.rt_series[lmk_rt(s, loop_scenario_index(s, st0, h, j, k, t))]);
   const size_t at = (size_t)b * m_rows + first + pt;
   rlo[at] = d > 0.0 ? 0.0 : -INFINITY;
   rhi[at] = d < 0.0 ? 0.0 : INFINITY;
@@ -397,6 +432,13 @@ hipError_t launch_loop_monotone_prepare(const dsp_loop_market_state &st, const d
                                         int first, hipStream_t stream) {
   const long long lanes = (long long)st.B * st.S + (long long)st.B * (st.S * (st.S - 1) / 2) * m.T;
   hipLaunchKernelGGL(loop_monotone_prepare_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, st, m, rlo, rhi, m_rows, first);
+  return hipGetLastError();
+}
+
+hipError_t launch_loop_midnight_prepare(const dsp_loop_market_state &st, const dsp_loop_market_model &m, double *rlo, double *rhi, int m_rows,
+                                        int first, int k, hipStream_t stream) {
+  const long long lanes = (long long)st.B * st.S + (rlo ? (long long)st.B * (st.S * (st.S - 1) / 2) * m.T : 0);
+  hipLaunchKernelGGL(loop_midnight_prepare_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, st, m, rlo, rhi, m_rows, first, k);
   return hipGetLastError();
 }
 

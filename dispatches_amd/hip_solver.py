@@ -112,7 +112,7 @@ EXPORTED_SYMBOLS = ("dsp_default_options", "dsp_create", "dsp_solve", "dsp_spmv_
                     "dsp_rtc_compile_check", "dsp_rtc_message", "dsp_wb_rolling_update", "dsp_loop_update", "dsp_bid_points", "dsp_source_hash",
                     "dsp_market_prepare", "dsp_market_clear", "dsp_loop_market_prepare", "dsp_loop_market_clear", "dsp_loop_param_step", "dsp_loop_project",
                     "dsp_loop_schedule_prepare", "dsp_loop_monotone_prepare", "dsp_loop_ledger", "dsp_loop_record", "dsp_loop_health",
-                    "dsp_loop_profile", "dsp_days_assign", "dsp_days_update", "dsp_days_frequency", "dsp_days_work_doubles")
+                    "dsp_loop_midnight_prepare", "dsp_loop_profile", "dsp_days_assign", "dsp_days_update", "dsp_days_frequency", "dsp_days_work_doubles")
 
 
 ABI_VERSION = 22       # DSP_VERSION of the include/dsp_hip.h these structures mirror
@@ -337,6 +337,8 @@ def load_library(path: Optional[str] = None):
     lib.dsp_loop_schedule_prepare.restype = C.c_int
     lib.dsp_loop_monotone_prepare.argtypes = [C.POINTER(DspLoopMarketState), C.POINTER(DspLoopMarketModel), vp, vp, i32, i32, vp]
     lib.dsp_loop_monotone_prepare.restype = C.c_int
+    lib.dsp_loop_midnight_prepare.argtypes = [C.POINTER(DspLoopMarketState), C.POINTER(DspLoopMarketModel), vp, vp, i32, i32, i32, vp]
+    lib.dsp_loop_midnight_prepare.restype = C.c_int
     lib.dsp_loop_param_step.argtypes = [C.POINTER(DspLoopParamState), C.POINTER(DspLoopModel), i32, i32, vp]
     lib.dsp_loop_param_step.restype = C.c_int
     lib.dsp_loop_project.argtypes = [C.POINTER(DspLoopProjectState), C.POINTER(DspLoopModel), i32, i32, vp]

@@ -59,7 +59,7 @@ integer cents where the reference rounds to 4 dp - so a price taker runs at its 
 Inside the cleared day every day_ahead_power column of the hourly problem is fixed to the cleared offer in all scenarios, the coupling
 rows are vacuous and the coupled LP separates: the hourly step solves B real-time LPs, scenario 0 only, and bids (P_T[t], 0).  OURS:
 in the last T_rt - 1 hours of a day the look-ahead periods past midnight have a free day_ahead_power which the host would still tie
-across scenarios; this loop does not.  `_day_ahead_step_self_schedule` / `_hour_step_bid` (the one hourly bidding step, here with
+across scenarios; this loop does not unless past_midnight="coupled" (__init__'s docstring; `_hour_step_past_midnight`).  `_day_ahead_step_self_schedule` / `_hour_step_bid` (the one hourly bidding step, here with
 one row per plant and pairs priced at 0) are the specification as tensor operations; csrc/dsp_market.hip (dsp_loop_schedule_prepare; dsp_loop_market_prepare / _clear on an S = 1 state with
 row_stride / self_schedule / curve_slots) is the same arithmetic, bit for bit.
 
@@ -77,7 +77,7 @@ solve stand for all its S pairs, `uncertified` counts a flagged plant once.  Rea
 column is fixed to the same cleared offer in all scenarios, and the host's coupled real-time problem puts its rows on those columns: they
 are vacuous there, so the hourly step is the stochastic mode's `_hour_step_bid` with B * S rows, unchanged.  OURS (the self-schedule's
 third choice again): in the last T_rt - 1 hours of a day the look-ahead periods past midnight have a free day_ahead_power, which the host
-would still order across scenarios; this loop does not.  Not settled here: whether upstream idaes additionally orders the real-time power
+would still order across scenarios; this loop does not unless past_midnight="coupled".  Not settled here: whether upstream idaes additionally orders the real-time power
 output across scenarios - idaes is not available to this project; the loop follows this project's host Bidder.
 `_day_ahead_step_monotone` (on `_coupled_blocks`, shared with the self-schedule) is the specification as tensor operations;
 csrc/dsp_market.hip (dsp_loop_monotone_prepare; dsp_loop_market_clear on a state with coupled = 1) is the same arithmetic, bit for bit.
@@ -167,7 +167,7 @@ class _Model:
             self.base_c0 -= float(per_kw) * float(template_sum)           # the template's curtailment constant leaves; the window's enters
         attach_solver(self, B, dev, device_index, getattr(model, "solver_hints", None), lp_backend, solved, simplex_certify)      # (solved=False: parametrized mode never solves its bidding templates)
 
-    def couple(self, model, S, B, dev, device_index, lp_backend, mode="non_anticipative"):
+    def couple(self, model, S, B, dev, device_index, lp_backend, mode="non_anticipative", simplex_certify=False):
         """-> the COUPLED day-ahead model of a batch built on this one-row block model (of `model`, the day-ahead template): B rows of
         the LP of CoupledScenarioModel(model, mode) - S blocks of this LP side by side and its coupling rows from row
         `first_coupling_row` = S * m1 on.  mode "non_anticipative" (a self-schedule): (S - 1) T rows pda[s, t] - pda[0, t] with bounds
@@ -194,7 +194,7 @@ class _Model:
         side = lambda v: torch.full((Tc,), 0.0 if mode == "non_anticipative" else v, dtype=torch.float64, device=dev)
         cm.rlo = torch.cat([self.rlo[0, :m1].repeat(S), side(float("-inf"))]).repeat(B, 1)
         cm.rhi = torch.cat([self.rhi[0, :m1].repeat(S), side(float("inf"))]).repeat(B, 1)
-        attach_solver(cm, B, dev, device_index, coupled.solver_hints, lp_backend)      # (a day-ahead horizon: a T > 16 model's options)
+        attach_solver(cm, B, dev, device_index, coupled.solver_hints, lp_backend, True, simplex_certify)      # (a day-ahead horizon: a T > 16 model's options; the hourly coupled model of past_midnight="coupled": a T <= 16 model's)
         self.c,self.lb, self.ub = (v.view(B * S, n1) for v in (cm.c, cm.lb, cm.ub))
         self.c0 = torch.zeros(B * S, dtype=torch.float64, device=dev)
         return cm
@@ -483,12 +483,14 @@ def _objective_constant(model_object, horizon, weighted_family, per_kw, cf):
 
 
 class BatchedDoubleLoop(_DeviceLoop):
+    past_midnight = "free"                             # (class default: the loop sets the attribute only where it is "coupled")
+
     def __init__(self, flowsheet, n_scenarios, device=0, first_scenario=0, day_ahead_horizon=48, tracking_horizon=4, lp_backend=None,
                  use_graphs=True, use_fused=True, simplex_warm=True, n_price_scenarios=1, forecaster="perfect", max_historical_days=10,
                  market="stub", bidder="lp", bid_price=None, storage_mw=None, plant_windows=None, wind_mw=None, battery_mw=None,
                  battery_mwh=None, ruc_hour=None, scenario_coupling="independent", ledger=False, pem_mw=None, tank_kg=None,
                  h2_price=None, h2_demand=None, record=None, record_max_bytes=2 ** 30, simplex_certify=False, health=False,
-                 profiles=None, profile_max_bytes=2 ** 30):
+                 profiles=None, profile_max_bytes=2 ** 30, past_midnight="free"):
         """flowsheet: "wind_battery", "wind_pem" or "nuclear".  Plant k sees the year that starts at hour (stride * k) mod N of its bus's
         series (strides 17 / 37 / 29).  lp_backend: tests pass tests/_highs_solver.py::HighsTensorLP to run the same logic on CPU tensors.
         use_fused: on the GPU the ~100 element-wise tensor operations of an hour step are THREE launches of one HIP kernel driven by the
@@ -603,7 +605,22 @@ class BatchedDoubleLoop(_DeviceLoop):
         nuclear operands, ledger, health and record, since every mode ends an hour by writing `delivered`.  reset() zeroes the buffer;
         profiles_host() returns [B, whole days run (at most days), 24]; profile_bytes is its size.  Refused (ValueError): days that is
         not an integer >= 1, a buffer above profile_max_bytes (default 2 ** 30: a guard like record_max_bytes, not a measured figure).
-        What the profiles are for: representative_days.DayPoints."""
+        What the profiles are for: representative_days.DayPoints.
+        past_midnight: "free" (the default: the loops above, same launches, same bits, no new attribute) or "coupled"
+        (bidder="self_schedule" or scenario_coupling="monotone"; all three flowsheets, both markets; with ledger, health, record,
+        profiles, simplex_warm, simplex_certify, eagerly or from graphs): the last T_rt - 1 hours of a day - whose real-time look-ahead
+        reaches past midnight, where day_ahead_power is free - solve ONE coupled real-time LP per plant, as the host bidders do
+        (workflow/bidder.py::compute_real_time_bids on CoupledScenarioModel(energy_prices=rt)): self.rtc, B rows of S blocks of the
+        real-time LP (block i of row b = row b * S + i of the stochastic mode's hourly batch at that hour; self.rt_block is that view)
+        plus the coupling rows over ALL T_rt periods - static 0, 0 for a self-schedule, for the monotone Bidder bounds that follow the
+        order of the hour's REAL-TIME scenario prices.  Curves: block i's P_T[t] with scenario i's real-time forecast, the plant's one
+        status for its S pairs (a self-schedule: the one pair (block 0's P_T[t], 0)); clearing, tracking, hand-off, ledger and profile
+        are unchanged; health books one real_time solve per plant and `solves` counts B + B in those hours; the coupled handle's
+        warm-start chain begins at the day's first such hour.  A recorded late hour hands the coupled solve to the real-time batch's
+        buffers (_tied_record).  The earlier hours are unchanged.  csrc/dsp_market.hip (dsp_loop_midnight_prepare; dsp_loop_market_clear
+        on the coupled rows with k >= 0) is the same arithmetic as _tied_blocks, bit for bit.  A coupled hourly LP that the solver
+        streams keeps its hours' steps eager (hour_step); the project's shapes stay in the fused kernels or the in-wave simplex.
+        Refused (ValueError): another value; "coupled" with a bidder that does not couple its scenarios."""
         import torch
         self.flowsheet = flowsheet
         self.B = B = int(n_scenarios)
@@ -617,6 +634,7 @@ class BatchedDoubleLoop(_DeviceLoop):
         bid_price, storage_mw, ruc_hour, sizes, plant_windows = self._validate(
             forecaster, market, bidder, tracking_horizon, bid_price, storage_mw, ruc_hour, wind_mw, battery_mw, battery_mwh, plant_windows,
             scenario_coupling)
+        self._check_past_midnight(past_midnight)
         nuclear = self._nuclear_operands(pem_mw, tank_kg, h2_price, h2_demand)
         self.nuclear_sized = nuclear is not None
         if self.nuclear_sized:
@@ -705,6 +723,8 @@ class BatchedDoubleLoop(_DeviceLoop):
                 if set(cols[cols >= 0].tolist()) & set(m.pda_cols.cpu().tolist()):
                     raise ValueError("a column is both a term of the power output and day_ahead_power: the prices' objective entries would collide")
             self._market_buffers(S + 1)
+            if self.past_midnight == "coupled":
+                self._past_midnight_setup(rt_model, mk, idx(rt_model.pda_cols), lp_backend, device)
         if self.ruc_hour is not None:
             self._ruc_setup(mk(tr_model, B))
         self.p_min_cents_plant = None
@@ -735,6 +755,8 @@ class BatchedDoubleLoop(_DeviceLoop):
             self._da_step = self._day_ahead_step_stochastic if self.stochastic else self._day_ahead_step
             self._hour = self._hour_step_bid if self.stochastic else self._hour_step
             self._n_da, self._n_hour = B * S, B * S + B
+        if self.past_midnight == "coupled":            # the last T_rt - 1 hours of a day: ONE coupled real-time LP per plant
+            self._hour = self._hour_step_past_midnight
         if record is not None:
             self._record_setup(record, int(record_max_bytes))
 
@@ -814,6 +836,38 @@ class BatchedDoubleLoop(_DeviceLoop):
                 raise ValueError(f"plant_windows is an int array of length {B}")
             plant_windows = plant_windows.astype(np.int64)
         return bid_price, storage_mw, ruc_hour, sizes, plant_windows
+
+    def _check_past_midnight(self, past_midnight):
+        """past_midnight (ValueError; __init__'s docstring); "coupled" becomes an attribute of the loop, "free" leaves the class's"""
+        if past_midnight not in ("free", "coupled"):
+            raise ValueError(f"past_midnight is 'free' or 'coupled', not {past_midnight!r}")
+        if past_midnight == "coupled":
+            if not self.coupled_da:
+                raise ValueError("past_midnight='coupled' ties the real-time look-ahead hours of a bidder that couples its price scenarios: "
+                                 "bidder='self_schedule' or scenario_coupling='monotone'")
+            self.past_midnight = "coupled"
+
+    def _past_midnight_setup(self, rt_model, mk, pda_cols, lp_backend, device):
+        """the coupled REAL-TIME model of past_midnight="coupled": self.rtc, B rows of S blocks of the real-time template plus the
+        coupling rows over all T_rt periods (_Model.couple, as self.da on the day-ahead template), with a handle, output buffers and a
+        warm-start chain of its own; self.rt_block is its [B * S, n1] view, which _set_rows writes; the pair index operands of the
+        monotone rows' bounds (persistent: a captured step creates no tensor from host data)"""
+        import torch
+        B, S, dev = self.B, self.S, self.dev
+        self.rt_block = mk(rt_model, 1, False)
+        self.rt_block.pda_cols = pda_cols
+        self.rtc = self.rt_block.couple(rt_model, S, B, dev, device, lp_backend, "monotone" if self.monotone else "non_anticipative",
+                                        self.simplex_certify)
+        self.rt_block.set_terms(dev)
+        self._first_tied_hour = 24 - self.rt.T + 1
+        at = lambda v: torch.as_tensor(v, dtype=torch.int64, device=dev)
+        self._rtc_pair_j, self._rtc_pair_k = at([j for j, _ in self.rtc.pairs]), at([k for _, k in self.rtc.pairs])
+        self._rtc_side = tuple(torch.full((), v, dtype=torch.float64, device=dev) for v in (0.0, float("-inf"), float("inf")))
+        self._rtc_capturable = None                    # may a late hour's step be a graph node (hour_step; as day_ahead's _da_capturable)
+
+    def _tied_hour(self, k):
+        """hour k of the day is one of the last T_rt - 1, whose real-time look-ahead reaches past midnight, and the loop ties them"""
+        return self.past_midnight == "coupled" and 24 - k < self.rt.T
 
     def _plant_sizes(self, flowsheet, B, wind_mw, battery_mw, battery_mwh):
         """validated sizes -> dict of float64 arrays [B] (wind_mw; wind_battery: battery_mw, battery_mwh too), or None without sizes"""
@@ -1115,6 +1169,9 @@ class BatchedDoubleLoop(_DeviceLoop):
             one = DspLoopMarketState.from_buffer_copy(mk)
             one.S, one.self_schedule, one.curve_slots = 1, 1, self.S + 1
             self._mk_state = one
+        if self.past_midnight == "coupled":            # the coupled real-time rows: one block described, blocks S * n1 apart, as the day-ahead ones
+            self._mk_rtc = _describe(DspLoopMarketModel, self.rtc, len(self.scale))
+            self._mk_rtc.row_stride = self.rtc.lp.n
         if self.ruc_hour is not None:                  # the bid made at the RUC hour: its own clock, the projected state, the pending buffers
             bid = DspLoopMarketState.from_buffer_copy(mk)
             bid.hour, bid.state = self.bid_hour_t.data_ptr(), self.proj_state[-1].data_ptr() if len(self.scale) else None
@@ -1512,6 +1569,97 @@ class BatchedDoubleLoop(_DeviceLoop):
         self._check(out)
         self._hand_off(out["x"], rt0[:, 0], k, exact=self.exact)
 
+    # -- past_midnight="coupled": the last T_rt - 1 hours of a day tie their look-ahead periods across the price scenarios ---------------------
+    def _tied_blocks(self, k):
+        """the S blocks of the B coupled real-time rows at hour k: block i of row b is what _set_rows / _free_day_ahead_power(m, k, S) give
+        row b * S + i of the stochastic mode's real-time batch, c0[b] = sum_i c0(b, i) in the order of i; the monotone Bidder's pair rows
+        follow the order of the hour's REAL-TIME scenario prices in every period (CoupledScenarioModel.load(energy_prices=rt))
+        -> the real-time scenario prices [B, S, T]"""
+        import torch
+        m, blk, B, S = self.rtc, self.rt_block, self.B, self.S
+        rt_f = self._forecast(self.rt_series, m.T, k).expand(B, S, m.T)
+        da_f = self._forecast(self.da_series, m.T, k).expand(B, S, m.T).clone()
+        known = 24 - k
+        da_f[:, :, :known] = self.da_prices[:, None, k:k + known]
+        self._set_rows(blk, da_f.reshape(B * S, m.T), rt_f.reshape(B * S, m.T))
+        self._free_day_ahead_power(blk, k, S)
+        each = blk.c0.view(B, S)
+        total = each[:, 0]
+        for i in range(1, S):
+            total = total + each[:, i]
+        m.c0.copy_(total)
+        if self.monotone:
+            zero, below, above = self._rtc_side
+            d = (rt_f[:, self._rtc_pair_k, :] - rt_f[:, self._rtc_pair_j, :]).reshape(B, -1)      # [B, P * T]: pair p, period t at p * T + t
+            rows = slice(m.first_coupling_row, m.first_coupling_row + d.shape[1])
+            m.rlo[:, rows] = torch.where(d > 0, zero, below)
+            m.rhi[:, rows] = torch.where(d < 0, zero, above)
+        return rt_f
+
+    def _tied_record(self):
+        """a recorded late hour: the recorder reads the real-time batch's buffers, so the coupled solve is handed to them - rt_x the
+        blocks (a self-schedule: block 0), rt_status the plant's one status on all its rows, rt_obj block i's c . x, rt_c0 the coupled
+        constant in the plant's first row and 0 in the others"""
+        m, rt, B, S = self.rtc, self.rt, self.B, self.S
+        per = rt.per_plant or S
+        x, c = m.out["x"].view(B, S, m.n1)[:, :per], m.c.view(B, S, m.n1)[:, :per]
+        rt.out["x"].view(B, per, m.n1).copy_(x)
+        rt.out["obj"].view(B, per).copy_((c * x).sum(2))
+        rt.out["status"].view(B, per).copy_(m.out["status"][:, None].expand(B, per))
+        rt.c0.zero_()
+        rt.c0.view(B, per)[:, 0] = m.c0
+
+    def _hour_step_past_midnight(self, k):
+        """Hour k of the day with past_midnight="coupled".  While the whole horizon lies inside the cleared day (24 - k >= T_rt) every
+        day_ahead_power column is fixed, the coupled problem separates and the step is _hour_step_bid's, unchanged.  In the last T_rt - 1
+        hours the look-ahead periods past midnight have a free day_ahead_power, which the host bidders tie across the scenarios
+        (workflow/bidder.py::compute_real_time_bids on CoupledScenarioModel): B coupled LPs (_tied_blocks) instead of B * S / B
+        independent ones, on a handle whose warm-start chain begins at the first such hour of the day.  Curves: block i's P_T[t] and
+        scenario i's real-time forecast, the plant's one status standing for its S pairs (a self-schedule: the one pair (block 0's
+        P_T[t], 0)); clearing, tracking and hand-off as _hour_step_bid."""
+        import torch
+        if not self._tied_hour(k):
+            return self._hour_step_bid(k)
+        m, tr, B, S = self.rtc, self.tr, self.B, self.S
+        hour = k if self.simplex_warm else None
+        first = (k - self._first_tied_hour) if self.simplex_warm else None        # 0: the slack basis / cold point, then hour k - 1's
+        if self.use_fused:
+            import ctypes as C
+            bounds = (C.c_void_p(m.rlo.data_ptr()), C.c_void_p(m.rhi.data_ptr())) if self.monotone else (None, None)
+            self._call(self._lib.dsp_loop_midnight_prepare, C.byref(self._mk_coupled if self.monotone else self._mk_sched), C.byref(self._mk_rtc),
+                       *bounds, m.lp.m, m.first_coupling_row, k)
+            m.solve(B, hour=first)
+            self._health_book("real_time", m, 1)
+            if self._rec is not None:
+                self._tied_record()
+            self._market_clear(self._mk_rtc, self._loop_tr, k, tr.T, self.rt_dispatch, self.rt_curve, self.rt_count,
+                               state=self._mk_coupled if self.monotone else self._mk_state)
+            tr.solve(B, hour=hour)
+            self._health_book("tracking", tr, 1)
+            self._fused(2, k)
+            return
+        rt_f = self._tied_blocks(k)
+        out = m.solve(B, hour=first)
+        self._health_book("real_time", m, 1)
+        self._check(out)
+        if self._rec is not None:
+            self._tied_record()
+        rt, Tc = self.rt, tr.T
+        x = out["x"].reshape(B * S, m.n1)              # block i of row b: the block-relative columns
+        power = ((x[:, rt.pt_a[:Tc]] * rt.pt_ca[:Tc] + x[:, rt.pt_b[:Tc]] * rt.pt_cb[:Tc]) + rt.PT_const[:Tc]).view(B, S, Tc)
+        if self.self_schedule:
+            U, M, count = self._schedule_curves(power[:, 0], out["status"])
+        else:
+            U, M, count = self._curves(power, rt_f[:, :, :Tc], out["status"].repeat_interleave(S))
+        rt0 = self._window(self.rt_series, 1)
+        self.rt_dispatch.copy_(self._clear(U, M, count, torch.cat([rt0, rt_f[:, 0, 1:Tc]], dim=1)))
+        self._store_curves(self.rt_curve, self.rt_count, U, M, count)
+        self._set_tracker()
+        out = tr.solve(B, hour=hour)
+        self._health_book("tracking", tr, 1)
+        self._check(out)
+        self._hand_off(out["x"], rt0[:, 0], k, exact=self.exact)
+
     # -- self-scheduling: one coupled day-ahead LP per plant, the schedule offered at cost 0 (module docstring); its hours: _hour_step_bid --
     def _schedule_curves(self, power, status):
         """power [B, Tc] MW, status [B] -> the curves of the ONE pair (power, 0 $/MWh) per plant and period (plant_curves with S = 1)"""
@@ -1755,9 +1903,18 @@ class BatchedDoubleLoop(_DeviceLoop):
             self._pending = True
             if self._rec is not None:                  # the bid of the next day sits in its daily row
                 self._rec.days_bid = max(self._rec.days_bid, self.hour // 24 + 2)
+        elif self._tied_hour(k):
+            # a coupled hourly LP that the solver streams is driven from the host, like such a day-ahead LP (day_ahead): its step stays
+            # eager.  The first - eager - day's solve reports which of the two the handle is (dsp_stats::streaming).
+            if self._rtc_capturable is None and self._warm:
+                self._rtc_capturable = self.use_graphs and not self.rtc.dlp.last_stats.streaming
+            if self._rtc_capturable:
+                self._run(k, lambda: self._hour(k))
+            else:
+                self._hour(k)
         else:
             self._run(k, lambda: self._hour(k))
-        self.solves += self._n_hour
+        self.solves += 2 * self.B if self._tied_hour(k) else self._n_hour
         self.hour += 1
         return self.delivered.clone()
 

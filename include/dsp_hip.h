@@ -838,6 +838,26 @@ int dsp_loop_schedule_prepare(const dsp_loop_market_state *st, const dsp_loop_ma
 int dsp_loop_monotone_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, double *rlo, double *rhi, int32_t m_rows,
                               int32_t first_coupling_row, void *hipStream);
 
+/* The coupled REAL-TIME LP of a look-ahead hour past midnight (added under ABI 22; BatchedDoubleLoop with past_midnight="coupled").  In
+ * the last T - 1 hours of a day (24 - k < T) the real-time problem of hour k has periods past midnight whose day_ahead_power is free, and
+ * the host bidders tie those across the price scenarios (workflow/bidder.py::compute_real_time_bids on CoupledScenarioModel).  `m`
+ * describes ONE block of a coupled row as for dsp_loop_schedule_prepare (row_stride >= S * n, c0 is [B]).  Lane (b, i) writes block i of
+ * row b exactly as dsp_loop_market_prepare writes row b * S + i at hour k - scenario i's backcast prices asked at hour-of-day k, the
+ * realised day-ahead prices and the cleared day_ahead_power in the 24 - k periods inside the day, day_ahead_power on (0, inf) past
+ * midnight, plant b's state and wind - and the lane of scenario 0 writes c0[b], the S block constants added in the order of i.
+ * rlo / rhi != NULL (the monotone Bidder): the next B * P * T lanes, P = S (S - 1) / 2, write the bounds of the ordered-pair rows
+ * first_coupling_row + p * T + t of ALL T periods from the order of the hour's REAL-TIME scenario prices (through rt_history_lag_days):
+ *   d = rt[k', t] - rt[j, t],   rlo = 0 if d > 0 else -inf,   rhi = 0 if d < 0 else +inf,
+ * pairs and lane order as dsp_loop_monotone_prepare.  rlo == rhi == NULL: a self-schedule, whose coupling rows are static (0, 0).
+ * No atomics, no cross-lane traffic; bit-identical to the tensor form (BatchedDoubleLoop._tied_blocks).  dsp_loop_market_clear reads such
+ * a row with k >= 0 as it reads the day-ahead one (coupled = 1, or block 0 through row_stride).
+ * DSP_ERR_INVALID, nothing launched and nothing written, for: everything dsp_loop_schedule_prepare refuses; k outside 0 .. 23 or an hour
+ * whose horizon stays inside the day (24 - k >= T); a NULL da_offer / da_prices; one of rlo / rhi NULL and the other not; with rlo / rhi:
+ * S < 2, first_coupling_row < 0, first_coupling_row + P * T > m_rows.
+ * Capturable: one kernel launch on hipStream, no allocation, no synchronisation, no memset. */
+int dsp_loop_midnight_prepare(const dsp_loop_market_state *st, const dsp_loop_market_model *m, double *rlo, double *rhi, int32_t m_rows,
+                              int32_t first_coupling_row, int32_t k, void *hipStream);
+
 /* Parametrized two-tier bidding in the descriptor loop (ABI 15; dispatches_amd/rolling_flowsheets.py: BatchedDoubleLoop with
  * bidder="parametrized").  The reference's wind + PEM and wind + battery sweeps bid without an LP (PEM_parametrized_bidder.py:50-122,
  * battery_parametrized_bidder.py:47-123): with w = wind_mw * capacity factor of the period, the pairs of a (plant, period) are
